@@ -10,11 +10,21 @@ continuity + Burgers -> spectral Poisson; the rollout records every state
 (as HybridSolver.run does).  N GPUs: weak scaling, 4096 ICs per rank, no
 communication while stepping, one RCCL all_gather of per-IC metrics inside the
 timed region — at N = 1 too (a one-rank RCCL group); the line reports the
-calls and bytes that exchange actually moved.  The timed rollout's first 16
-ICs are checked against the reference's committed trajectories ("parity"),
-and a library built with diagnostic flags is refused.
+calls and bytes that exchange actually moved.  A library built with
+diagnostic flags is refused.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--ics-per-gpu B] [--no-cpu-baseline]
+A plain run does only what the headline needs: set up, one warmup rollout of
+W steps, the timed rollout of K steps, the result line.  More than 50 steps
+(MAX_ROLLOUT_STEPS) run as back-to-back rollouts from the same ICs, each with
+its exchange, so that the states stay finite; the outputs are the last one's.  --dump-outputs DIR
+also writes what the timed rollout returned (DIR/<name>.npy).  Everything
+else is behind --full: the timed rollout's first 16 ICs checked against the
+reference's committed trajectories ("parity"), the same rollout once more at
+the warm clock, the other precisions, Poisson mode, radii, BASELINE configs,
+PureGNN / PINN, the training line and the CPU baseline (each of which
+--also / --no-other-configs / --no-train / --no-cpu-baseline still drops).
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--ics-per-gpu B] [--dump-outputs DIR] [--full]
 """
 import argparse
 import datetime
@@ -316,11 +326,11 @@ def train_line(dev, batch=2000, steps=20, cfg_name="physics", warm_s=0.3, more=(
     return out
 
 
-def pmc_traffic(K, B, nx, traj, build):
+def pmc_traffic(K, B, nx, traj, build, launches=1):
     """HBM bytes per launch of the headline kernel from the committed PMC passes
     (tools/gpu_pmc_traffic.sh + tools/pmc_traffic.py): FETCH_SIZE / WRITE_SIZE at two
     step counts give a fixed part and a per-step part, so the figure applies to
-    any --steps of the same workload.  The record names the src: hash of the
+    any --steps of the same workload (`launches` rollouts of K steps in all).  The record names the src: hash of the
     library it was measured on; for any other build the figure is not this
     binary's, and the traffic is reported as null with the reason."""
     path = os.path.join(ROOT, "profiles", "pmc_traffic.json")
@@ -333,7 +343,7 @@ def pmc_traffic(K, B, nx, traj, build):
         return None, "profiles/pmc_traffic.json is for another workload"
     if t.get("build") != build:
         return None, f"stale: profiles/pmc_traffic.json was measured on src:{t.get('build')}, this is src:{build}"
-    return {"traffic_bytes": t["fixed_bytes"] + t["per_step_bytes"] * K, "source": t["source"],
+    return {"traffic_bytes": t["fixed_bytes"] * launches + t["per_step_bytes"] * K, "source": t["source"],
             "fixed_bytes": t["fixed_bytes"], "per_step_bytes": t["per_step_bytes"], "build": t["build"]}, None
 
 
@@ -360,6 +370,48 @@ def headline_parity(traj_buf, nx, K, weights_path, precision):
             "gate": "|gpu - ref| <= 2e-6 + 2e-6*|ref| (tests/test_gpu_parity.py ROLL_ATOL/ROLL_RTOL)",
             "within_gate": bool(excess <= 0.0 and np.isfinite(got).all()),
             "reference": "tests/golden/hybrid_W1_r3_nx64.npz (seeds 1000..1015, reference CPU HybridSolver)"}
+
+
+# The longest single rollout of the headline: the default --steps (BASELINE cfg3's T = 50).  With
+# the 1-epoch fixture weights every rollout of these ICs turns non-finite eventually (the first
+# of the 4096 at step 93, all by step 500), as the reference's own long rollouts do, so more
+# steps than this run as back-to-back rollouts from the ICs: the outputs stay finite and every
+# step costs what a step of a finite state costs.
+MAX_ROLLOUT_STEPS = 50
+
+
+def split_steps(K):
+    """K steps as the fewest rollouts of at most MAX_ROLLOUT_STEPS each, lengths within one
+    step of each other, longer first: 50 -> [50], 120 -> [40, 40, 40], 101 -> [34, 34, 33]."""
+    n = max(1, -(-K // MAX_ROLLOUT_STEPS))
+    q, r = divmod(K, n)
+    return [q + 1] * r + [q] * (n - r)
+
+
+DUMP_BUDGET_BYTES = 60 << 20  # of the 64 MB a dump may take in all
+
+
+def dump_outputs(path, arrays):
+    """Write what the timed rollout returned as path/<name>.npy (float32).
+    arrays: {name: tensor [n_ics, ...]}, rows in IC order.  Small arrays are
+    written whole; when all of them together exceed DUMP_BUDGET_BYTES, the
+    largest ones keep a fixed sample of their ICs (numpy default_rng(0), sorted,
+    the same for the same shapes), whose indices go to <name>_ics.npy."""
+    os.makedirs(path, exist_ok=True)
+    todo = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    left = DUMP_BUDGET_BYTES
+    for i, (name, t) in enumerate(todo):
+        share = left // (len(todo) - i)  # what the smaller arrays did not use goes to the larger
+        row_bytes = max(1, t[0].numel() * 4 + 8)
+        n = t.shape[0]
+        if n * row_bytes > share:
+            keep = max(1, share // row_bytes)
+            idx = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+            t = t[torch.as_tensor(idx, device=t.device)]
+            np.save(os.path.join(path, f"{name}_ics.npy"), idx.astype(np.float64))
+        a = np.ascontiguousarray(t.detach().to(torch.float32).cpu().numpy())
+        np.save(os.path.join(path, f"{name}.npy"), a)
+        left -= t.shape[0] * row_bytes
 
 
 def rank_report(wall, ics, group=None):
@@ -470,7 +522,8 @@ def launch_ranks(n):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=50,
+                    help="timed steps: one rollout up to 50, equal back-to-back rollouts of at most 50 beyond")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--ics-per-gpu", type=int, default=4096)
     ap.add_argument("--nx", type=int, default=64)
@@ -491,7 +544,15 @@ def main():
                     help="skip the other single-GPU BASELINE configs (cfg2: 256 ICs f32; cfg4: 4096 ICs x 1024 "
                          "cells bf16), reported under 'other_configs' at N=1")
     ap.add_argument("--no-train", action="store_true", help="skip the training side line (SURVEY 8(f2))")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed rollout returned (final, traj, metrics) as DIR/<name>.npy: "
+                         "float32, at most 64 MB in all (a fixed sample of the ICs of an array too large for that)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: parity against the reference's "
+                         "trajectories, the next rollout at the warm clock, --also precisions, the other configs, "
+                         "models and radii, the training line and the CPU baseline (off by default)")
     args = ap.parse_args()
+    extras = args.full and not args.no_other_configs  # the side lines of a --full run
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: start the N rank processes here,
@@ -542,78 +603,103 @@ def main():
     solver = HybridSolver(weights, radius=3, nx=nx, dt=dt, device=dev, precision=args.precision)
     ics = solver.baseline.initial_conditions(shard_seeds(1000, n_total, world, rank), as_tensor=True)
     stream = torch.cuda.current_stream(dev)
-    ws, _ = engine.workspace(HF_OP_RUN, B, nx, K, dev, model=solver._dm(), traj=not args.no_traj)
-
-    # every buffer of the warmup and of the timed rollout is allocated first, so
-    # the timed launch follows the warmup with no allocation in between
+    # K steps are one rollout up to MAX_ROLLOUT_STEPS, back-to-back rollouts from the ICs beyond
     Wr = max(W, 1)
+    segs, wsegs = split_steps(K), split_steps(Wr)
+    ws, _ = engine.workspace(HF_OP_RUN, B, nx, max(segs + wsegs), dev, model=solver._dm(), traj=not args.no_traj)
+
+    # every buffer of the warmup and of the timed rollouts is allocated first, so
+    # the timed launch follows the warmup with no allocation in between
+    def buffers(lengths):  # {T: (trajectory [B,T+1,3,nx] or None, metric series [B,T+1,4])}
+        return {T: (None if args.no_traj else torch.empty(B, T + 1, 3, nx, device=dev),
+                    torch.empty(B, T + 1, 4, device=dev)) for T in sorted(set(lengths))}
+
     final = torch.empty_like(ics)
-    traj_buf = None if args.no_traj else torch.empty(B, K + 1, 3, nx, device=dev)
-    met_buf = torch.empty(B, K + 1, 4, device=dev)
-    warm_traj = None if args.no_traj else torch.empty(B, Wr + 1, 3, nx, device=dev)
-    warm_met = torch.empty(B, Wr + 1, 4, device=dev)
+    bufs, warm_bufs = buffers(segs), buffers(wsegs)
     warm_final = torch.empty_like(ics)
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    evs = [tuple(torch.cuda.Event(enable_timing=True) for _ in range(3)) for _ in segs]
     if os.environ.get("HF_BENCH_TOUCH", "0") == "1":  # A/B only: first-touch the output buffers before the warmup
-        for t in (final, traj_buf, met_buf):
+        for t in (final,) + tuple(b for pair in bufs.values() for b in pair):
             if t is not None:
                 t.zero_()
     torch.cuda.synchronize(dev)
 
-    # warmup: one rollout of W steps (compiles nothing; faults the code objects
-    # in) and its metric exchange
+    def rollouts(s, out, ws_=None):
+        """The K timed steps once more on solver s (same segments, same buffers); the last rollout's result."""
+        for T in segs:
+            r = s.run_batch(ics, T, traj=bufs[T][0] if bufs[T][0] is not None else False, metrics=bufs[T][1],
+                            out=out, ws=ws_)
+        return r
+
+    # warmup: W steps the same way (compiles nothing; faults the code objects
+    # in), each rollout with its metric exchange
     progress(f"headline warmup ({B} ICs x {nx} cells, {Wr} steps)")
-    warm = solver.run_batch(ics, Wr, traj=warm_traj if warm_traj is not None else False, metrics=warm_met,
-                            out=warm_final, ws=ws)
-    gather_rollout(warm, n_total)
-    ev_g = torch.cuda.Event(enable_timing=True)
+    for T in wsegs:
+        warm = solver.run_batch(ics, T, traj=warm_bufs[T][0] if warm_bufs[T][0] is not None else False,
+                                metrics=warm_bufs[T][1], out=warm_final, ws=ws)
+        gather_rollout(warm, n_total)
     if world > 1:  # a one-rank group has no one to wait for
         dist.barrier()
     torch.cuda.synchronize(dev)
     reset_collective_stats()
     t0 = time.perf_counter()
-    ev0.record(stream)
-    res = solver.run_batch(ics, K, traj=traj_buf if traj_buf is not None else False, metrics=met_buf, out=final,
-                           ws=ws)
-    ev1.record(stream)
-    # per-IC summaries (first non-finite step, drifts) on the device,
-    # then ONE exchange of the full metric series [B_rank, T+1, K] + summaries
-    # (a real all_gather whenever a group exists: RCCL at every N by default)
-    gathered = gather_rollout(res, n_total)
-    ev_g.record(stream)
+    for T, (ev0, ev1, ev_g) in zip(segs, evs):
+        ev0.record(stream)
+        res = solver.run_batch(ics, T, traj=bufs[T][0] if bufs[T][0] is not None else False, metrics=bufs[T][1],
+                               out=final, ws=ws)
+        ev1.record(stream)
+        # SURVEY 8(e): per-IC summaries (first non-finite step, drifts) on the device,
+        # then ONE exchange per rollout of the full metric series [B_rank, T+1, K] + summaries
+        # (a real all_gather whenever a group exists: RCCL at every N by default)
+        gathered = gather_rollout(res, n_total)
+        ev_g.record(stream)
     torch.cuda.synchronize(dev)
     if world > 1:
         dist.barrier()
     wall = time.perf_counter() - t0
-    kernel_ms = ev0.elapsed_time(ev1)
-    exchange_ms = ev1.elapsed_time(ev_g)
+    kernel_ms = sum(e0.elapsed_time(e1) for e0, e1, _ in evs)
+    exchange_ms = sum(e1.elapsed_time(eg) for _, e1, eg in evs)
     coll = dict(COLLECTIVES)
+    T_last = segs[-1]
+    traj_buf, met_buf = bufs[T_last]  # of the last rollout
+    # what the timed rollout returned (before anything below reuses its buffers):
+    # this rank's final states and trajectory and the gathered metric series (not the
+    # per-IC summaries derived from that series: their unused columns are NaN by design,
+    # which a plain comparison of two dumps would report as a difference)
+    if args.dump_outputs and rank == 0:
+        progress(f"headline timed; writing its outputs to {args.dump_outputs}")
+        dump = {"final": res["final"], "metrics": gathered["metrics"]}
+        if res.get("traj") is not None:
+            dump["traj"] = res["traj"]
+        dump_outputs(args.dump_outputs, dump)
     # the timed rollout's own states against the reference's (before anything
     # below reuses traj_buf)
-    parity = headline_parity(traj_buf, nx, K, args.weights, args.precision) if rank == 0 else None
+    parity = headline_parity(traj_buf, nx, T_last, args.weights, args.precision) if rank == 0 and args.full else None
 
     # diagnostic only (not the value): the same K-step rollout once more, right
     # behind the timed one, i.e. at the clock the chip holds once it is warm;
     # the gap to kernel_ms is the clock ramp after the short warmup
-    ev2, ev3 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ev2.record(stream)
-    solver.run_batch(ics, K, traj=traj_buf if traj_buf is not None else False, metrics=met_buf, out=final, ws=ws)
-    ev3.record(stream)
-    torch.cuda.synchronize(dev)
-    kernel_ms_again = ev2.elapsed_time(ev3)
+    kernel_ms_again = None
+    if args.full:
+        ev2, ev3 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev2.record(stream)
+        rollouts(solver, final, ws)
+        ev3.record(stream)
+        torch.cuda.synchronize(dev)
+        kernel_ms_again = ev2.elapsed_time(ev3)
 
     # other precisions, same ICs / K / warmup, timed the same way (reported, not the headline)
-    progress("headline timed; alternates")
+    progress("headline timed" + ("; alternates" if args.full else ""))
     alt = {}
-    for prec in [p for p in args.also.split(",") if p and p != args.precision]:
+    for prec in [p for p in args.also.split(",") if p and p != args.precision] if args.full else []:
         s2 = HybridSolver(weights, radius=3, nx=nx, dt=dt, device=dev, precision=prec)
-        s2.run_batch(ics, max(W, 1), traj=not args.no_traj)
+        s2.run_batch(ics, min(max(W, 1), MAX_ROLLOUT_STEPS), traj=not args.no_traj)
         final2 = torch.empty_like(ics)
         torch.cuda.synchronize(dev)
         a0, a1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ta = time.perf_counter()
         a0.record(stream)
-        r2 = s2.run_batch(ics, K, traj=traj_buf if traj_buf is not None else False, metrics=met_buf, out=final2)
+        r2 = rollouts(s2, final2)
         a1.record(stream)
         torch.cuda.synchronize(dev)
         wall2 = time.perf_counter() - ta
@@ -625,16 +711,16 @@ def main():
     # the north star's tridiagonal Poisson (opt-in, NOT the reference's operator:
     # include/hybridflux.h HF_POISSON_TRIDIAG), fused into the same persistent
     # kernel, same ICs / K / precision, timed the same way
-    if not args.no_other_configs:
+    if extras:
         s2 = HybridSolver(weights, radius=3, nx=nx, dt=dt, device=dev, precision=args.precision,
                           poisson="tridiagonal")
-        s2.run_batch(ics, max(W, 1), traj=not args.no_traj)
+        s2.run_batch(ics, min(max(W, 1), MAX_ROLLOUT_STEPS), traj=not args.no_traj)
         final2 = torch.empty_like(ics)
         torch.cuda.synchronize(dev)
         a0, a1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ta = time.perf_counter()
         a0.record(stream)
-        s2.run_batch(ics, K, traj=traj_buf if traj_buf is not None else False, metrics=met_buf, out=final2)
+        rollouts(s2, final2)
         a1.record(stream)
         torch.cuda.synchronize(dev)
         wall2 = time.perf_counter() - ta
@@ -650,18 +736,18 @@ def main():
     # cfg3 names "all ablation radii": the other two checkpoints (W1_r1, W1_r2)
     # on the same ICs, timed the same way (the radius only selects the weights)
     radii = None
-    if world == 1 and not args.no_other_configs and nx == 64 and args.precision == "f32":
+    if world == 1 and extras and nx == 64 and args.precision == "f32":
         radii = {}
         for r in (1, 2):
             wr = dict(np.load(os.path.join(ROOT, "tests", "golden", f"weights_W1_r{r}.npz"), allow_pickle=False))
             s2 = HybridSolver(wr, radius=r, nx=nx, dt=dt, device=dev, precision=args.precision)
-            s2.run_batch(ics, max(W, 1), traj=not args.no_traj)
+            s2.run_batch(ics, min(max(W, 1), MAX_ROLLOUT_STEPS), traj=not args.no_traj)
             final_r = torch.empty_like(ics)
             torch.cuda.synchronize(dev)
             a0, a1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ta = time.perf_counter()
             a0.record(stream)
-            s2.run_batch(ics, K, traj=traj_buf if traj_buf is not None else False, metrics=met_buf, out=final_r)
+            rollouts(s2, final_r)
             a1.record(stream)
             torch.cuda.synchronize(dev)
             wall2 = time.perf_counter() - ta
@@ -669,7 +755,7 @@ def main():
             del s2
 
     others = None
-    if world == 1 and not args.no_other_configs:
+    if world == 1 and extras:
         progress("cfg2 / cfg4")
         # cfg4's first ICs (seeds 1000..1003) against committed vectors: the bf16
         # kernels' emulation and the f32 forward on bf16 weights (tests/golden/
@@ -688,12 +774,12 @@ def main():
                   other_config(w_r2, dev, "cfg4: 1024-cell chain, 4096-IC batch, r=2, bf16 MLP weights, dt=3.125e-4",
                                4096, 1024, "bf16", 30, 30, 2, fixture=fx, tridiag=True)]
 
-    if world == 1 and not args.no_other_configs:
+    if world == 1 and extras:
         progress("PureGNN / PINN")
-    models = other_models(dev, 4096, 30) if world == 1 and not args.no_other_configs else None
-    if world == 1 and not args.no_other_configs and not args.no_train:
+    models = other_models(dev, 4096, 30) if world == 1 and extras else None
+    if world == 1 and extras and not args.no_train:
         progress("training line")
-    train = train_line(dev) if world == 1 and not args.no_other_configs and not args.no_train else None
+    train = train_line(dev) if world == 1 and extras and not args.no_train else None
 
     ranks = rank_report(wall, B)  # one all_gather: the max over ranks and each rank's wall / ICs
     wall_max = ranks["wall_s_max"]
@@ -701,7 +787,7 @@ def main():
     exploded = int((gathered["summary"][:, 0] >= 0).sum().item())
 
     if rank == 0:
-        traffic, traffic_why = pmc_traffic(K, B, nx, not args.no_traj, build_hash())
+        traffic, traffic_why = pmc_traffic(K, B, nx, not args.no_traj, build_hash(), len(segs))
         value = n_total * K / wall_max
         flop = GNN_FLOP_PER_CELL_STEP * B * nx * K
         achieved = flop / (kernel_ms * 1e-3) / 1e12
@@ -710,7 +796,7 @@ def main():
         kernel = (f"chain_rollout_kernel<{args.precision},MT={nx // 16}> (one persistent launch)" if fused else
                   f"chain_flux_kernel<{args.precision},window> + fv_step_kernel<hybrid> per step")
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             # the GPU box's CPU share is 16 cores (os.cpu_count() there shows the whole host)
             cores = pinned(min(16, len(os.sched_getaffinity(0))))
             keep = os.sched_getaffinity(0)
@@ -749,7 +835,9 @@ def main():
                       "bf16": "bf16 (f32 accumulate)"}[args.precision],
             "data": "synthetic: reference IC generator seeds 1000.., fixture weights W1_r3 (1-epoch reference trainer)",
             "config": {"workload": f"{'cfg3' if (nx == 64 and B == 4096) else 'cfg2' if (nx == 64 and B == 256) else 'cfg4' if nx == 1024 else 'custom'}: {nx}-cell periodic chain, {B}-IC batch per GPU, FluxGNN(4,128,4) {args.precision}, "
-                                   f"{K}-step persistent rollout{'' if args.no_traj else ' recording every state'}",
+                                   f"{K}-step persistent rollout{'' if args.no_traj else ' recording every state'}"
+                                   + (f" (as {len(segs)} rollouts of <= {MAX_ROLLOUT_STEPS} steps)" if len(segs) > 1
+                                      else ""),
                        "nx": nx, "dt": dt, "ics_per_gpu": B, "global_ics": n_total, "parallelism": f"ic-shard x{world}",
                        "collective": (collective_entry(coll, world, exchange_ms) if coll["calls"] else
                                       ({"backend": "none", "error": group_error} if group_error else None)),
@@ -763,11 +851,11 @@ def main():
                          "traffic_build": traffic["build"] if traffic else None,
                          "traffic_model": ({"fixed_bytes": traffic["fixed_bytes"],
                                             "per_step_bytes": traffic["per_step_bytes"]} if traffic else None),
-                         "algorithmic_bytes": (12 * B * nx * (K + 1) if not args.no_traj else 0)
-                                              + 24 * B * nx + 4 * B * (K + 1) * 4,
+                         "algorithmic_bytes": (12 * B * nx * (K + len(segs)) if not args.no_traj else 0)
+                                              + 24 * B * nx * len(segs) + 4 * B * (K + len(segs)) * 4,
                          "kernel": kernel, "kernel_ms": round(kernel_ms, 3),
-                         "kernel_ms_next_rollout": round(kernel_ms_again, 3),
-                         "flop_per_launch": flop,
+                         "kernel_ms_next_rollout": round(kernel_ms_again, 3) if kernel_ms_again is not None else None,
+                         "launches": len(segs), "flop_per_launch": flop // len(segs),
                          "hbm_state_frac": round(STATE_BYTES_PER_CELL_STEP * B * nx * K / (kernel_ms * 1e-3)
                                                  / (PEAK_HBM_GBS * 1e9), 6)},
             "cpu_baseline": cpu,

@@ -169,6 +169,36 @@ def test_bench_group_setup_times_out_without_peer():
     assert float(res[0].split()[-1]) < 60, res
 
 
+def test_bench_dump_outputs_sample_is_bounded_and_fixed(tmp_path, monkeypatch):
+    """bench.dump_outputs: float32 .npy files, small arrays whole; when all of
+    them exceed the budget the largest keeps a fixed, sorted sample of its ICs
+    (indices in <name>_ics.npy), the same on every call, and the files stay
+    within the budget."""
+    import sys
+    monkeypatch.setenv("HSA_ENABLE_IPC_MODE_LEGACY", os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    import bench
+    # --steps beyond one rollout: the fewest rollouts of at most 50 steps, K steps in all
+    assert [bench.split_steps(k) for k in (1, 50, 51, 101, 120)] == [[1], [50], [26, 25], [34, 34, 33], [40, 40, 40]]
+    assert all(sum(bench.split_steps(k)) == k and max(bench.split_steps(k)) <= 50 for k in range(1, 400))
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 64 << 10)
+    g = torch.Generator().manual_seed(0)
+    arrays = {"final": torch.randn(100, 3, 16, generator=g), "traj": torch.randn(100, 9, 3, 16, generator=g),
+              "metrics": torch.randn(100, 9, 4, generator=g, dtype=torch.float64)}
+    a, b = tmp_path / "a", tmp_path / "b"
+    bench.dump_outputs(str(a), arrays)
+    bench.dump_outputs(str(b), arrays)
+    assert sorted(os.listdir(a)) == ["final.npy", "metrics.npy", "traj.npy", "traj_ics.npy"]
+    assert sum(os.path.getsize(a / f) for f in os.listdir(a)) <= 64 << 10
+    for f in os.listdir(a):
+        assert np.array_equal(np.load(a / f), np.load(b / f)), f
+    assert np.array_equal(np.load(a / "final.npy"), arrays["final"].numpy())
+    assert np.load(a / "metrics.npy").dtype == np.float32
+    idx = np.load(a / "traj_ics.npy").astype(np.int64)
+    assert 1 <= len(idx) < 100 and (np.diff(idx) > 0).all() and idx.min() >= 0 and idx.max() < 100
+    assert np.array_equal(np.load(a / "traj.npy"), arrays["traj"].numpy()[idx])
+
+
 BENCH_RANK_SCRIPT = r"""
 import json, os, sys, time
 sys.path.insert(0, {root!r}); sys.argv = ["bench.py"]

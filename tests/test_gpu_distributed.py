@@ -121,8 +121,8 @@ def test_rccl_one_rank_equals_no_group_bitwise(tmp_path):
 def test_bench_one_gpu_runs_rccl_exchange():
     """A plain `python bench.py` (N = 1, default backend nccl) creates a
     one-rank RCCL group and reports the all_gather it actually ran inside the
-    timed region, and the timed rollout's parity against the reference."""
-    p = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2",
+    timed region, and (--full) the timed rollout's parity against the reference."""
+    p = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--full",
               "--no-cpu-baseline", "--no-other-configs", "--also", ""], 300)
     # stdout is exactly the one JSON line (RCCL's version banner goes to stderr)
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -133,6 +133,45 @@ def test_bench_one_gpu_runs_rccl_exchange():
     assert c["calls"] == 1 and c["bytes_received_per_rank"] == 4096 * (5 * 4 + 8) * 4
     assert c["exchange_ms"] > 0
     assert d["parity"]["within_gate"] and d["parity"]["steps_checked"] == 4
+
+
+@pytest.mark.timeout(120)
+@pytest.mark.parametrize("steps,last", [(3, 3), (101, 33)])
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path, steps, last):
+    """A plain run (no --full) times the headline alone: every side line of the
+    result is null, --steps is the number of timed steps and ms_per_step the
+    wall time of one.  --dump-outputs writes what the timed rollout returned:
+    the float32 arrays equal HybridSolver.run_batch on the same seeds bit for
+    bit (the inputs are the same from run to run).  101 steps run as rollouts
+    of 34 + 34 + 33 steps from the ICs (a single rollout of these weights turns
+    non-finite from step 93 on): 101 timed steps, the last rollout's outputs."""
+    import torch
+    from hybridflux import HybridSolver
+    out = tmp_path / "dump"
+    p = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+              "--ics-per-gpu", "48", "--dist-backend", "gloo", "--dump-outputs", str(out)], 100)
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1 and lines[0].startswith("{"), p.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == steps and d["roofline"]["launches"] == -(-steps // 50) and d["warmup"] == 1
+    assert d["dtype"] == "f32" and d["higher_is_better"] is True and d["finite_fraction"] == 1.0
+    # value = ICs / (seconds per step); ms_per_step is rounded to 1e-4 ms, value to 0.1
+    assert d["ms_per_step"] > 0
+    assert abs(d["value"] - 48 / (d["ms_per_step"] * 1e-3)) <= d["value"] * 1e-4 / d["ms_per_step"] + 0.1
+    for key in ("cpu_baseline", "parity", "alt", "radii", "other_configs", "other_models", "train"):
+        assert d[key] is None, key
+    assert d["roofline"]["kernel_ms_next_rollout"] is None
+    got = {f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))}
+    assert sorted(got) == ["final", "metrics", "traj"]
+    assert all(a.dtype == np.float32 for a in got.values())
+    solver = HybridSolver(os.path.join(ROOT, "tests", "golden", "weights_W1_r3.npz"), radius=3, device="cuda:0")
+    ics = solver.baseline.initial_conditions(range(1000, 1048), as_tensor=True)
+    want = solver.run_batch(ics, last, traj=True, metrics=True)
+    torch.cuda.synchronize()
+    assert got["traj"].shape == (48, last + 1, 3, 64) and got["metrics"].shape == (48, last + 1, 4)
+    for key in ("final", "traj", "metrics"):
+        w = want[key].cpu().numpy()
+        assert np.isfinite(w).all() and np.array_equal(got[key].view(np.uint32), w.view(np.uint32)), key
 
 
 @pytest.mark.timeout(600)
