@@ -221,20 +221,14 @@ PinnW pinn_view(const float *p, int D, int H, int L) {
 // reaches HBM; the ICs never exchange anything, so no step needs a grid sync.
 constexpr int kPinnIcs = 16;
 
-#ifndef HF_PINN_WAVES
-#define HF_PINN_WAVES 8
-#endif
 // waves per workgroup: 8 (two per SIMD, two output tiles each, sharing each B
 // fragment read).  With the loads serialised (round 3) 16 waves of one tile
 // measured 3 % faster than 8 (profiles/r03_pinn_ab.txt); with the weight
 // stream pipelined 8 waves measure 1.5-2.5 % faster than 16
 // (profiles/r04_pinn_waves_ab.jsonl).
-constexpr int kPinnWaves = HF_PINN_WAVES;
-#ifndef HF_PINN_AHEAD
-#define HF_PINN_AHEAD 4
-#endif
+constexpr int kPinnWaves = 8;
 // weight k-blocks in flight per wave (pinn_layer's software pipeline)
-constexpr int kPinnAhead = HF_PINN_AHEAD;
+constexpr int kPinnAhead = 4;
 
 // This wave's packed weight rows of one layer: output tiles wave + kPinnWaves j
 // (j < NT; a spare tile past the layer's last is clamped to it and not stored)
@@ -274,35 +268,10 @@ struct PinnSplit {
   int *flag;   // [R] step tag of the partial in sp
   int tag;     // this step's tag (t + 1)
 };
-// Barrier-free layer hand-off (HF_PINN_FLAGS): each output tile carries a
-// flag word in LDS that its wave sets (release, workgroup scope) to the
-// layer's tag (step * L + layer + 1, increasing) once the tile is stored; a
-// wave reads input k-block c only after flag c holds the producing layer's tag
-// (acquire).  Tiles are owned by one wave each, the activations cycle through
-// three buffers (a writer of layer l has consumed every tile of layer l-1, so
-// every wave is past layer l-2, the last reader of the buffer layer l
-// overwrites), so no workgroup barrier orders a step: a wave starts a layer on
-// the k-blocks that are ready while the slower waves finish theirs.  The last
-// layer's owner waves also store their new state rows to the trajectory.
-struct PinnSync {
-  const int *in_flag = nullptr;  // flags of the input tiles (nullptr: a barrier ordered them)
-  int in_tag = 0;
-  int *out_flag = nullptr;
-  int out_tag = 0;
-  float *traj = nullptr;  // ACT 1: row step + 1 of IC b0 (ICs ldt apart), or nullptr
-  int64_t ldt = 0;
-  int nic = 0;  // ICs of the workgroup that exist
-};
-__device__ __forceinline__ void pinn_wait(const int *f, int tag) {
-  // bounded: never reached in a correct run, but a lost producer ends in wrong values, not a hang
-  for (int it = 0; __hip_atomic_load(f, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < tag && it < (1 << 20); ++it)
-    __builtin_amdgcn_s_sleep(1);
-}
 template <int K, int NTILES, int ACT, int KBN, int NT, bool SPLIT = false>
 __device__ __forceinline__ void pinn_layer(const PinnRows<NT> &wrow, const float *bias, const float *in, float *out,
                                            int wave, int lane, f4v (&wq)[kPinnAhead][NT],
-                                           const PinnRows<NT> &nrow, const PinnSplit &spl = PinnSplit{},
-                                           const PinnSync &sy = PinnSync{}) {
+                                           const PinnRows<NT> &nrow, const PinnSplit &spl = PinnSplit{}) {
   constexpr int KB = K / 16, P = kPinnAhead;
   static_assert(KB % P == 0 && KBN >= P - 1, "a layer's k-blocks fill whole rounds of the ring");
   static_assert(!SPLIT || (ACT == 1 && NT == 2 && 2 * (NTILES - kPinnWaves) == kPinnWaves && KB % 2 == 0),
@@ -314,15 +283,6 @@ __device__ __forceinline__ void pinn_layer(const PinnRows<NT> &wrow, const float
   f4v acc[NT];
 #pragma unroll
   for (int j = 0; j < NT; ++j) acc[j] = f4v{0.f, 0.f, 0.f, 0.f};
-  // flags: one read of all the input tiles' flags; only if some are not yet
-  // set does the wave wait per k-block
-  bool ready = true;
-  if (sy.in_flag) {
-    const int f = lane < KB ? __hip_atomic_load(sy.in_flag + lane, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)
-                            : sy.in_tag;
-    ready = __all(f >= sy.in_tag);
-    if (!ready) pinn_wait(sy.in_flag, sy.in_tag);
-  }
   f4v bv = *reinterpret_cast<const f4v *>(in + lane * 4);
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -338,10 +298,7 @@ __device__ __forceinline__ void pinn_layer(const PinnRows<NT> &wrow, const float
       }
     }
     f4v bn = bv;
-    if (c + 1 < KB) {
-      if (!ready) pinn_wait(sy.in_flag + c + 1, sy.in_tag);
-      bn = *reinterpret_cast<const f4v *>(in + (c + 1) * 256 + lane * 4);
-    }
+    if (c + 1 < KB) bn = *reinterpret_cast<const f4v *>(in + (c + 1) * 256 + lane * 4);
     const bool use1 = on1(c);
 #pragma unroll
     for (int e = 0; e < 4; ++e)
@@ -386,12 +343,8 @@ __device__ __forceinline__ void pinn_layer(const PinnRows<NT> &wrow, const float
       const f4v st = *reinterpret_cast<const f4v *>(o);
 #pragma unroll
       for (int i = 0; i < 4; ++i) v[i] = __fadd_rn(st[i], v[i]);
-      // the new state's features 16t + 4 (lane >> 4) .. +3 of IC lane & 15
-      if (sy.traj && (lane & 15) < sy.nic)
-        *reinterpret_cast<f4v *>(sy.traj + (lane & 15) * sy.ldt + 16 * t + 4 * (lane >> 4)) = v;
     }
     *reinterpret_cast<f4v *>(o) = v;
-    if (sy.out_flag) __hip_atomic_store(sy.out_flag + t, sy.out_tag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
   }
 }
 
@@ -407,24 +360,12 @@ __global__ __launch_bounds__(64 * kPinnWaves, 1) void pinn_run_kernel(PinnW w, c
   static_assert(H >= D, "the widest layer sets the tiles per wave");
   constexpr int NTH = 64 * kPinnWaves;
   __shared__ f4v s_state4[D * kPinnIcs / 4];
-// HF_PINN_FLAGS=1: the barrier-free hand-off (PinnSync).  Measured and not
-// kept: correct (tests/test_gpu_baselines.py) but 12 % slower than the
-// barriers (profiles/r06_models_ab.txt, run 3): without a barrier the older
-// wave of each SIMD pair runs ahead and then waits on the younger one's tiles.
-#ifndef HF_PINN_FLAGS
-#define HF_PINN_FLAGS 0
-#endif
-  constexpr bool kFlags = HF_PINN_FLAGS;
-  __shared__ f4v s_act4[kFlags ? 3 : 2][H * kPinnIcs / 4];
-  __shared__ int s_fh[3][H / 16];  // PinnSync flags of the three activation buffers' tiles
-  __shared__ int s_fs[D / 16];     // ... and of the state's
+  // (workgroup barriers order the layers: a barrier-free flag hand-off measured
+  // 12 % slower, profiles/r06_models_ab.txt, run 3)
+  __shared__ f4v s_act4[2][H * kPinnIcs / 4];
   __shared__ f4v s_bias4[kMaxChainLayers * H / 4];  // layer l's bias at l * H
   // the split last layer's partial sums and flags (PinnSplit)
-#ifdef HF_EXP_PINN_NOSPLIT  // A/B: the clamped spare tile of round 5
-  constexpr bool kSplit = false;
-#else
   constexpr bool kSplit = 2 * (D / 16 - kPinnWaves) == kPinnWaves && NT == 2 && (H / 16) % 2 == 0;
-#endif
   __shared__ f4v s_part[kSplit ? (D / 16 - kPinnWaves) * 64 : 1];
   __shared__ int s_flag[kSplit ? D / 16 - kPinnWaves : 1];
   float *s_state = reinterpret_cast<float *>(s_state4);
@@ -441,12 +382,7 @@ __global__ __launch_bounds__(64 * kPinnWaves, 1) void pinn_run_kernel(PinnW w, c
     if (traj && b0 + n < B) traj[b * ldt + d] = v;
   }
   const int L = w.L;
-#ifdef HF_EXP_PINN_PRIO  // experiment: static issue priority 1 for the second-dispatched half (waves 4-7)
-  if (wave >= kPinnWaves / 2) __builtin_amdgcn_s_setprio(1);
-#endif
   if (kSplit && tid < D / 16 - kPinnWaves) s_flag[tid] = 0;
-  if (tid < 3 * (H / 16)) s_fh[tid / (H / 16)][tid % (H / 16)] = 0;
-  if (tid < D / 16) s_fs[tid] = 0;
   float *const s_bias = reinterpret_cast<float *>(s_bias4);
   for (int l = 0; l < L; ++l)
     for (int i = tid; i < (l == L - 1 ? D : H); i += NTH) s_bias[l * H + i] = w.b[l][i];
@@ -471,30 +407,7 @@ __global__ __launch_bounds__(64 * kPinnWaves, 1) void pinn_run_kernel(PinnW w, c
 #pragma unroll
       for (int j = 0; j < NT; ++j) wq[kb][j] = *reinterpret_cast<const f4v *>(r0.p[j] + 256 * kb);
   }
-  if constexpr (kFlags) {
-    float *const act2 = reinterpret_cast<float *>(s_act4[kFlags ? 2 : 0]);
-    auto hb = [&](int i) { return i == 0 ? act0 : (i == 1 ? act1 : act2); };
-    const int nic = B - b0 < kPinnIcs ? (int)(B - b0) : kPinnIcs;
-    for (int t = 0; t < T; ++t) {
-      const int G = t * L;  // tags: layer l of step t publishes G + l + 1
-      pinn_layer<D, H / 16, 0, H / 16, NT>(row(0), s_bias, s_state, hb(0), wave, lane, wq, row(1), PinnSplit{},
-                                           PinnSync{s_fs, G, s_fh[0], G + 1});
-      for (int l = 1; l < L - 1; ++l)
-        pinn_layer<H, H / 16, 0, H / 16, NT>(row(l), s_bias + l * H, hb((l - 1) % 3), hb(l % 3), wave, lane, wq,
-                                             row(l + 1), PinnSplit{},
-                                             PinnSync{s_fh[(l - 1) % 3], G + l, s_fh[l % 3], G + l + 1});
-      PinnSync sl{s_fh[(L - 2) % 3], G + L - 1, s_fs, G + L,
-                  traj ? traj + b0 * ldt + (int64_t)(t + 1) * D : nullptr, ldt, nic};
-      if constexpr (kSplit)
-        pinn_layer<H, D / 16, 1, D / 16, NT, true>(row(L - 1), s_bias + (L - 1) * H, hb((L - 2) % 3), s_state, wave,
-                                                   lane, wq, row(0), PinnSplit{s_part, s_flag, t + 1}, sl);
-      else
-        pinn_layer<H, D / 16, 1, D / 16, NT>(row(L - 1), s_bias + (L - 1) * H, hb((L - 2) % 3), s_state, wave, lane,
-                                             wq, row(0), PinnSplit{}, sl);
-    }
-    __syncthreads();  // every wave's last state tiles stored
-  }
-  for (int t = 0; t < (kFlags ? 0 : T); ++t) {
+  for (int t = 0; t < T; ++t) {
     pinn_layer<D, H / 16, 0, H / 16, NT>(row(0), s_bias, s_state, act0, wave, lane, wq, row(1));
     __syncthreads();
     for (int l = 1; l < L - 1; ++l) {
@@ -640,11 +553,9 @@ __global__ void pure_pack_kernel(const float *__restrict__ W, int64_t ld, int ro
   P[i] = W[(int64_t)(16 * u + (lane & 15)) * ld + j * jcol + 16 * kb + 4 * (lane >> 4) + e];
 }
 
-#ifndef HF_PURE_WG
-#define HF_PURE_WG 2
-#endif
+constexpr int kPureWG = 2;  // workgroups per CU (launch bounds)
 template <int H, int NC, bool PACKED>
-__global__ __launch_bounds__(64 * (H / 16), HF_PURE_WG) void pure_run_kernel(PureW w, const float *__restrict__ state0,
+__global__ __launch_bounds__(64 * (H / 16), kPureWG) void pure_run_kernel(PureW w, const float *__restrict__ state0,
                                                                     float *__restrict__ final_state,
                                                                     const float *__restrict__ x,
                                                                     float *__restrict__ traj, int B, int T) {
@@ -665,16 +576,10 @@ __global__ __launch_bounds__(64 * (H / 16), HF_PURE_WG) void pure_run_kernel(Pur
     if (traj) traj[b * ldt + i] = v;
   }
   for (int i = tid; i < NX; i += NTH) s_x[i] = x[i];
-#ifdef HF_EXP_PURE_PRIO  // experiment: static issue priority 1 for the second-dispatched half
-  if (u >= H / 32) __builtin_amdgcn_s_setprio(1);
-#endif
   __syncthreads();
-#ifndef HF_PURE_MFMA_IO
-#define HF_PURE_MFMA_IO 1
-#endif
   for (int t = 0; t < T; ++t) {
     // input_mlp: h = tanh(W_in [n, u, E, x] + b_in)
-    if (HF_PURE_MFMA_IO) {
+    {
       // on the matrix core: one v_mfma_f32_16x16x4f32 per cell group, A = rows
       // 16u .. 16u+15 of W_in (lane: row lane & 15, input lane >> 4), B = the
       // group's [n, u, E, x] (lane: input lane >> 4 of cell NC (lane & 15) + g);
@@ -698,16 +603,6 @@ __global__ __launch_bounds__(64 * (H / 16), HF_PURE_WG) void pure_run_kernel(Pur
         }
         *reinterpret_cast<f4v *>(act + ((u * NC + g) * 64 + lane) * 4) = h;
       }
-    } else {
-      for (int idx = tid; idx < H * NX; idx += NTH) {
-        const int f = idx / NX, c = idx - f * NX;
-        const float *wi = w.w_in + f * 4;
-        float v = __fmul_rn(wi[0], s_st[c]);
-        v = __fmaf_rn(wi[1], s_st[NX + c], v);
-        v = __fmaf_rn(wi[2], s_st[2 * NX + c], v);
-        v = __fmaf_rn(wi[3], s_x[c], v);
-        act[pure_act_idx<NC>(f, c)] = tanh_fast(__fadd_rn(v, w.b_in[f]));
-      }
     }
     __syncthreads();
     for (int l = 0; l < w.L; ++l) {
@@ -730,17 +625,9 @@ __global__ __launch_bounds__(64 * (H / 16), HF_PURE_WG) void pure_run_kernel(Pur
           const float pl = g > 0 ? acc[0][g - 1][i] : dpp_ror(acc[0][NC - 1][i], 0);
           const float pr = g < NC - 1 ? acc[0][g + 1][i] : dpp_ror(acc[0][0][i], 1);
           const float qv = acc[1][g][i];
-#ifndef HF_PURE_TANH2
-#define HF_PURE_TANH2 1
-#endif
-          if (HF_PURE_TANH2) {  // the two messages' tanh as packed f32 (bit-identical)
-            const hf_f2 t = tanh_fast2((hf_f2{pl, pr} + qv) + bq[i]);
-            h[i] = __fadd_rn(h[i], __fadd_rn(t.x, t.y));
-          } else {
-            float m = tanh_fast(__fadd_rn(__fadd_rn(pl, qv), bq[i]));
-            m = __fadd_rn(m, tanh_fast(__fadd_rn(__fadd_rn(pr, qv), bq[i])));
-            h[i] = __fadd_rn(h[i], m);
-          }
+          // the two messages' tanh as packed f32 (bit-identical to two tanh_fast)
+          const hf_f2 t = tanh_fast2((hf_f2{pl, pr} + qv) + bq[i]);
+          h[i] = __fadd_rn(h[i], __fadd_rn(t.x, t.y));
         }
         *reinterpret_cast<f4v *>(act2 + o) = h;
       }
@@ -777,35 +664,27 @@ __global__ __launch_bounds__(64 * (H / 16), HF_PURE_WG) void pure_run_kernel(Pur
       act2 = tmp;
     }
     // output_mlp.2 and the update: state += W_o2 o + b_o2
-    if (HF_PURE_MFMA_IO) {
-      // on the matrix core: wave g < NC takes cell group g, A = the 3 rows of
-      // W_o2 (rows 3..15 zero; the packed weights' k order), B = o as stored:
-      // H/16 k-blocks x 4 MFMA steps; channel ch of cell NC c + g lands in lane
-      // c, element ch
-      if (u < NC) {
-        const int g = u, row = lane & 15;
-        f4v acc = f4v{0.f, 0.f, 0.f, 0.f};
+    // on the matrix core: wave g < NC takes cell group g, A = the 3 rows of
+    // W_o2 (rows 3..15 zero; the packed weights' k order), B = o as stored:
+    // H/16 k-blocks x 4 MFMA steps; channel ch of cell NC c + g lands in lane
+    // c, element ch
+    if (u < NC) {
+      const int g = u, row = lane & 15;
+      f4v acc = f4v{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int kb = 0; kb < H / 16; ++kb) {
-          const f4v av = row < 3 ? *reinterpret_cast<const f4v *>(w.w_o2 + row * H + 16 * kb + q4)
-                                 : f4v{0.f, 0.f, 0.f, 0.f};
-          const f4v bv = *reinterpret_cast<const f4v *>(act + ((kb * NC + g) * 64 + lane) * 4);
+      for (int kb = 0; kb < H / 16; ++kb) {
+        const f4v av = row < 3 ? *reinterpret_cast<const f4v *>(w.w_o2 + row * H + 16 * kb + q4)
+                               : f4v{0.f, 0.f, 0.f, 0.f};
+        const f4v bv = *reinterpret_cast<const f4v *>(act + ((kb * NC + g) * 64 + lane) * 4);
 #pragma unroll
-          for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], bv[e], acc, 0, 0, 0);
-        }
-        if (lane < 16) {
-          const int cell = NC * lane + g;
-#pragma unroll
-          for (int ch = 0; ch < 3; ++ch)
-            s_st[ch * NX + cell] = __fadd_rn(s_st[ch * NX + cell], __fadd_rn(acc[ch], w.b_o2[ch]));
-        }
+        for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], bv[e], acc, 0, 0, 0);
       }
-    } else if (tid < 3 * NX) {
-      const int ch = tid / NX, c = tid - ch * NX;
-      const float *wo = w.w_o2 + ch * H;
-      float v = 0.f;
-      for (int f = 0; f < H; ++f) v = __fmaf_rn(wo[f], act[pure_act_idx<NC>(f, c)], v);
-      s_st[tid] = __fadd_rn(s_st[tid], __fadd_rn(v, w.b_o2[ch]));
+      if (lane < 16) {
+        const int cell = NC * lane + g;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch)
+          s_st[ch * NX + cell] = __fadd_rn(s_st[ch * NX + cell], __fadd_rn(acc[ch], w.b_o2[ch]));
+      }
     }
     __syncthreads();
     if (traj)
@@ -814,9 +693,6 @@ __global__ __launch_bounds__(64 * (H / 16), HF_PURE_WG) void pure_run_kernel(Pur
   for (int i = tid; i < 3 * NX; i += NTH) final_state[b * 3 * NX + i] = s_st[i];
 }
 
-#ifndef HF_PURE_FUSED
-#define HF_PURE_FUSED 1
-#endif
 bool pure_fused_ok(int H, int nx) { return (H == 64 || H == 128) && nx % 16 == 0 && nx >= 16 && nx <= 64; }
 
 // floats of the one-launch PureGNN rollout's packed weights (L layers, width H)
@@ -937,7 +813,7 @@ hipError_t launch_pure_gnn_run(const float *params, int H, int L, const float *s
   const int64_t N = (int64_t)B * nx, S = 3LL * nx;
   const int64_t ldt = (T + 1) * S;
   hipError_t e;
-  if (HF_PURE_FUSED && T > 0 && pure_fused_ok(H, nx))  // one launch (it writes trajectory row 0 itself; ws: packed weights)
+  if (T > 0 && pure_fused_ok(H, nx))  // one launch (it writes trajectory row 0 itself; ws: packed weights)
     return H == 64 ? pure_fused_h<64>(w, state0, final_state, x, B, nx, T, traj, ws, s)
                    : pure_fused_h<128>(w, state0, final_state, x, B, nx, T, traj, ws, s);
   if (traj && (e = hipMemcpy2DAsync(traj, sizeof(float) * ldt, state0, sizeof(float) * S, sizeof(float) * S, B,
@@ -966,12 +842,12 @@ int64_t pinn_ws_bytes(int D, int H, int64_t B) {
 
 int64_t pure_gnn_run_ws_bytes(int H, int B, int nx, int T) {
   if (B == 0 || T == 0) return 0;
-  if (HF_PURE_FUSED && pure_fused_ok(H, nx))  // the packed weights, for up to kMaxChainLayers layers
+  if (pure_fused_ok(H, nx))  // the packed weights, for up to kMaxChainLayers layers
     return (int64_t)a256(sizeof(float) * pure_packed_floats(H, kMaxChainLayers));
   return pure_gnn_ws_bytes(H, (int64_t)B * nx, 2LL * B * nx);
 }
 
-bool pure_gnn_run_ws_optional(int H, int nx, int T) { return HF_PURE_FUSED && T > 0 && pure_fused_ok(H, nx); }
+bool pure_gnn_run_ws_optional(int H, int nx, int T) { return T > 0 && pure_fused_ok(H, nx); }
 
 int64_t pinn_run_ws_bytes(int D, int H, int64_t B) {
   // the one-launch shape: the packed weight copy, sized for the most layers the ABI admits

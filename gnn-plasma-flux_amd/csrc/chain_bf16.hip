@@ -49,19 +49,8 @@ typedef unsigned u4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ unsigned pk_bf16(float a, float b) {
   return __builtin_bit_cast(unsigned, __builtin_convertvector(f2{a, b}, b2));
 }
-// ReLU of two f32 values packed to bf16.  HF_EXP_IRELU (experiment): convert
-// first, then a signed 16-bit max with 0 on the bf16 bit patterns (one
-// v_pk_max_i16 for two values); equal to bf16(relu(z)) except that a
-// negative-signed NaN becomes +0.
-__device__ __forceinline__ unsigned pk_relu_bf16(float a, float b) {
-#ifdef HF_EXP_IRELU
-  typedef short s2 __attribute__((ext_vector_type(2)));
-  const s2 v = __builtin_bit_cast(s2, pk_bf16(a, b));
-  return __builtin_bit_cast(unsigned, __builtin_elementwise_max(v, s2{0, 0}));
-#else
-  return pk_bf16(relu(a), relu(b));
-#endif
-}
+// ReLU of two f32 values packed to bf16
+__device__ __forceinline__ unsigned pk_relu_bf16(float a, float b) { return pk_bf16(relu(a), relu(b)); }
 __device__ __forceinline__ f4 mma(const u4 &a, const u4 &b, f4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(b8, a), __builtin_bit_cast(b8, b), c, 0, 0, 0);
 }
@@ -70,14 +59,9 @@ __device__ __forceinline__ f4 mma(const u4 &a, const u4 &b, f4 c) {
 // fragments, or the seam reads after a ring barrier), then one MFMA and up to
 // NV VALU (epilogue work of the previous pair) at a time.  The sched_barrier
 // keeps the next unit's reads from being picked for this unit's DS group.
-#ifndef HF_EXP_VFIRST
-#define HF_EXP_VFIRST 0
-#endif
 template <int NM, int NV, int ND = 4>
 __device__ __forceinline__ void interleave() {
   __builtin_amdgcn_sched_group_barrier(0x100, ND, 0);
-  // experiment: VALU issued between the fragment reads and the first MFMA
-  if constexpr (HF_EXP_VFIRST > 0 && NV > 0) __builtin_amdgcn_sched_group_barrier(0x002, HF_EXP_VFIRST, 0);
 #pragma unroll
   for (int i = 0; i < NM; ++i) {
     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -192,14 +176,8 @@ struct CoreBF16 {
     return;
 #endif
     const int l = Seam::lane_id(), o = sm.par * (NW * 16) + ((l >> 4) << 1) + t;
-#ifdef HF_EXP_SEAM1
-    // experiment: one read per tile: lanes j = 15 read the right wave's value,
-    // every other lane the left wave's (only j = 0 uses L, only j = 15 uses R)
-    L = R = ((l & 15) == 15 ? sm.rdr : sm.rdl)[o];
-#else
     L = sm.rdl[o];
     R = sm.rdr[o];
-#endif
   }
 
   struct Feed {
@@ -773,9 +751,6 @@ __global__ __launch_bounds__(64 * Core::kNW, 1) void chain_flux_sw_kernel(ChainW
   Seam sm{lds4 + kBaseF4 + Seam::slot(R.wave, 0), lds4 + kBaseF4 + Seam::slot((R.wave + NW - 1) % NW, 1),
           lds4 + kBaseF4 + Seam::slot((R.wave + 1) % NW, 0), 0};
   __syncthreads();  // small weights staged (no DMA in flight yet)
-#ifdef HF_EXP_PRIO_HI  // experiment: static issue priority 1 for the second-dispatched half (waves 4-7)
-  if (R.wave >= NW / 2) __builtin_amdgcn_s_setprio(1);
-#endif
   R.prime(R.chunks - 1);  // the pass starts two units before chunk 0 (Core::pos)
   typename Core::Feed F;
   Core::begin(R, F);
@@ -819,19 +794,9 @@ __global__ __launch_bounds__(64 * Core::kNW, 1) void chain_flux_sw_kernel(ChainW
 #endif
     }
   };
-#ifdef HF_EXP_PREFETCH
-  float pre[MT];
-  if (blockIdx.x < nsw) load_feat(blockIdx.x, pre);
-#endif
   for (int k = blockIdx.x; k < nsw; k += gridDim.x) {
     float feat[MT];
-#ifdef HF_EXP_PREFETCH
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) feat[mt] = pre[mt];
-    if (k + (int)gridDim.x < nsw) load_feat(k + gridDim.x, pre);  // in flight under this forward
-#else
     load_feat(k, feat);
-#endif
     float f_fwd[MT], f_bwd[MT];
     Core::template gnn_seam<MT>(W, S, R, F, park_of<Core, false>(lds, R.wave), sm, feat, f_fwd, f_bwd);
     const int s0 = __builtin_amdgcn_readfirstlane(first(k));
@@ -991,19 +956,13 @@ struct CellBF16T {
     readout_finish<1>(pf1, pb1, W.b2, ffwd, fbwd);
   }
 };
-#ifndef HF_CELLS_LOADER
-#define HF_CELLS_LOADER 1
-#endif
-using CellBF16Ld = CellBF16T<HF_CELLS_LOADER != 0>;  // with a loader wave (the cell-split kernels)
+using CellBF16Ld = CellBF16T<true>;  // with a loader wave (the cell-split kernels)
 
 }  // namespace
 
 // ring position of the deferred DMA: 0 (pair unit 2) measured best; 1, 2, 3: +3-10 % (profiles/r02_cfg4_diag.jsonl, run D)
-#ifndef HF_SW_DMAU
-#define HF_SW_DMAU 0
-#endif
 // the super-window core (any nx other than 16..64; cfg4's 1024): 8 waves, two per SIMD
-using SwCoreBF16 = CoreBF16<8, 4, 4, false, 3, 1, HF_SW_DMAU, true>;
+using SwCoreBF16 = CoreBF16<8, 4, 4, false, 3, 1, 0, true>;
 
 hipError_t launch_chain_flux_bf16(const ChainW &w, const float *nf, const float *state, int64_t ld_state,
                                   const float *x, int B, int nx, float *fe, float *ff, hipStream_t s) {

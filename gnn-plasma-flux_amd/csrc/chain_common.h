@@ -656,7 +656,7 @@ __global__ __launch_bounds__(64 * Core::kNW, Core::kWGPerCU) void chain_flux_ker
 // Fused training forward (FluxGNN.forward under autograd on tagged chains of
 // nx = 16*MT cells, train_chain.hip launch_chain_forward_train): the flux
 // kernel's IC-per-wave pass plus the activation tape (TrainTape) the backward
-// GEMMs read.  W comes from pack_chain_f32_kernel (the parameters change every
+// GEMMs read.  W comes from pack_chain_train_f32_kernel (the parameters change every
 // optimizer step); b2 is read from the device (*b2p).
 template <class Core, int MT>
 __global__ __launch_bounds__(64 * Core::kNW, Core::kWGPerCU) void chain_train_fwd_kernel(
@@ -708,120 +708,18 @@ __global__ __launch_bounds__(64 * Core::kNW, Core::kWGPerCU) void chain_train_fw
   R.drain();
 }
 
-// The readout's backward in the backward pass (train_chain.hip
-// launch_chain_backward, fused path): from the forward's P/Q tape (P = W_a h +
-// b_e, Q = W_b h, [N][P | Q]) and the flux gradient g ([B][2nx]: g_f, g_b),
-// with z_f(i) = P_i + Q_{i+1}, z_b(i) = P_{i+1} + Q_i (src/flux_gnn.py:62-66),
-//   dP_i = g_f(i) w2 [z_f(i) > 0] + g_b(i-1) w2 [z_b(i-1) > 0]
-//   dQ_i = g_b(i) w2 [z_b(i) > 0] + g_f(i-1) w2 [z_f(i-1) > 0]
-// in the lane layout (neighbours one m-tile over, or a row rotation at the
-// seam), the sums and products of edge_backward_kernel bit for bit, stored to
-// dpq ([N][dP | dQ], the readout weight gradient's operand and this pass's B
-// operand), and this IC's dw2 = sum g_f ReLU(z_f) + g_b ReLU(z_b), db2 = sum
-// g_f + g_b to part[b][0..H] (a fixed-order row reduction).  Replaces the
-// separate edge_backward_h128_kernel pass over P/Q and dP/dQ.
-#ifndef HF_TRAIN_EDGE_FOLD  // (train_chain.hip: measured and not kept; default off)
-#define HF_TRAIN_EDGE_FOLD 0
-#endif
-struct EdgeFold {
-  const float *pq;     // nullptr: no fold (the pass reads dpq as written by the edge kernel)
-  const float *gflux;  // [B][2nx]
-  const float *w2;     // [kH]
-  float *dpq;          // [N][2 kH]
-  float *part;         // [B][kH + 1]
-};
-template <int MT>
-__device__ __forceinline__ void edge_fold_ic(const EdgeFold &E, int64_t b, bool live, int lane) {
-  constexpr int nx = 16 * MT;
-  const int j = lane & 15, g4 = 4 * (lane >> 4);
-  const float *src = E.pq + b * nx * 2 * kH + g4;
-  float *dst = E.dpq + b * nx * 2 * kH + g4;
-  float gf[MT], gb[MT], gfl[MT], gbl[MT];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-    gf[mt] = E.gflux[b * 2 * nx + cell_of<MT>(mt, j)];
-    gb[mt] = E.gflux[b * 2 * nx + nx + cell_of<MT>(mt, j)];
-  }
-  left_nb<MT>(gf, gfl);
-  left_nb<MT>(gb, gbl);
-  float dw[kNT][4];
-#pragma unroll
-  for (int nt = 0; nt < kNT; ++nt) {
-    f4 P4[MT], Q4[MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      P4[mt] = ldf4(src + (int64_t)cell_of<MT>(mt, j) * 2 * kH + 16 * nt);
-      Q4[mt] = ldf4(src + (int64_t)cell_of<MT>(mt, j) * 2 * kH + kH + 16 * nt);
-    }
-    const f4 w = ldf4(E.w2 + 16 * nt + g4);
-    f4 dP4[MT], dQ4[MT];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float P[MT], Q[MT], Pr[MT], Pl[MT], Qr[MT], Ql[MT];
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) P[mt] = P4[mt][r], Q[mt] = Q4[mt][r];
-      right_nb<MT>(P, Pr);
-      left_nb<MT>(P, Pl);
-      right_nb<MT>(Q, Qr);
-      left_nb<MT>(Q, Ql);
-      float acc = 0.f;
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) {
-        const float zf = __fadd_rn(P[mt], Qr[mt]), zbp = __fadd_rn(P[mt], Ql[mt]);
-        const float zb = __fadd_rn(Pr[mt], Q[mt]), zfp = __fadd_rn(Pl[mt], Q[mt]);
-        dP4[mt][r] = __fadd_rn(zf > 0.f ? __fmul_rn(gf[mt], w[r]) : 0.f, zbp > 0.f ? __fmul_rn(gbl[mt], w[r]) : 0.f);
-        dQ4[mt][r] = __fadd_rn(zb > 0.f ? __fmul_rn(gb[mt], w[r]) : 0.f, zfp > 0.f ? __fmul_rn(gfl[mt], w[r]) : 0.f);
-        acc = fmaf(gf[mt], zf > 0.f ? zf : 0.f, acc);
-        acc = fmaf(gb[mt], zb > 0.f ? zb : 0.f, acc);
-      }
-      dw[nt][r] = acc;
-    }
-    if (live) {
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) {
-        *reinterpret_cast<f4 *>(dst + (int64_t)cell_of<MT>(mt, j) * 2 * kH + 16 * nt) = dP4[mt];
-        *reinterpret_cast<f4 *>(dst + (int64_t)cell_of<MT>(mt, j) * 2 * kH + kH + 16 * nt) = dQ4[mt];
-      }
-    }
-  }
-  float db = 0.f;
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) db = __fadd_rn(db, __fadd_rn(gf[mt], gb[mt]));
-  // sums over the row's 16 lanes (its 16 MT cells), in the same order in every lane
-  auto row_sum = [](float v) {
-    v = __fadd_rn(v, dpp_zero<0x128>(v));  // row_ror:8
-    v = __fadd_rn(v, dpp_zero<0x124>(v));  // row_ror:4
-    v = __fadd_rn(v, dpp_zero<0x122>(v));  // row_ror:2
-    return __fadd_rn(v, dpp_zero<kRowRor1>(v));
-  };
-#pragma unroll
-  for (int nt = 0; nt < kNT; ++nt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) dw[nt][r] = row_sum(dw[nt][r]);
-  db = row_sum(db);
-  if (live && j == 0) {
-    float *o = E.part + b * (kH + 1);
-#pragma unroll
-    for (int nt = 0; nt < kNT; ++nt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) o[16 * nt + g4 + r] = dw[nt][r];
-    if (g4 == 0) o[kH] = db;
-  }
-  __threadfence_block();  // this wave's dP / dQ stores complete before it reads them back
-}
-
 // Fused data gradient of the update layers (train_chain.hip
 // launch_chain_backward): from g[L] = ReLU'(h[L]) * dh[L] (the readout's
 // gradient, global) to g[l] = ReLU'(h[l]) * (W_a^T g[l+1] + W_b^T agg g[l+1])
 // for l = L-1 .. 0 (the aggregation is self-adjoint on the periodic chain),
 // one IC per wave through the flux kernel's layer pass: the same [x ; agg x]
 // B operand from registers, the transposed weights streamed through the ring
-// (pack_chain_bwd_f32_kernel), the ReLU' bits the forward stored
+// (pack_chain_train_f32_kernel), the ReLU' bits the forward stored
 // (TrainTape::mbits).  g[l] = g0 + l * gstride, [N][H] each.
 template <class Core, int MT>
 __global__ __launch_bounds__(64 * Core::kNW, Core::kWGPerCU) void chain_train_bwd_kernel(
     ChainW W, int64_t items, float *g0, int64_t gstride, const unsigned *__restrict__ mbits,
-    const float *__restrict__ dPQ, EdgeFold EF) {
+    const float *__restrict__ dPQ) {
   constexpr int nx = 16 * MT;
   __shared__ f4 lds4[Core::kSlots * Core::kChunkFloats / 4];
   float *lds = reinterpret_cast<float *>(lds4);
@@ -845,9 +743,6 @@ __global__ __launch_bounds__(64 * Core::kNW, Core::kWGPerCU) void chain_train_bw
     f4 g[MT][kNT];
     if (dPQ) {
       // g[L] = ReLU'(h[L]) * (W_a^T dP + W_b^T dQ): a layer pass with B = [dP ; dQ]
-#if HF_TRAIN_EDGE_FOLD
-      if (EF.pq) edge_fold_ic<MT>(EF, b, live, lane);  // dP / dQ of this IC into dPQ (= EF.dpq) first
-#endif
       SecondHalf<MT> X;
       const float *src = dPQ + b * nx * 2 * kH + g4;
 #pragma unroll
@@ -1124,12 +1019,6 @@ __global__ __launch_bounds__(cells_threads<CC>(), 1) void chain_rollout_cells_ke
   auto R = make_ring<CC>(W, lds);
   const int wave = R.wave, lane = R.lane, j = lane & 15, g = lane >> 4;
   constexpr bool kLd = CC::R_t::kLoader;
-#ifndef HF_LDR_EMIT
-#define HF_LDR_EMIT 0
-#endif
-  // HF_LDR_EMIT=1: the loader wave writes the per-step outputs instead of the
-  // lead (measured equal on cfg2, profiles/r02_cfg2_loader_ab.json)
-  constexpr bool kLdEmit = kLd && HF_LDR_EMIT;
   const bool shadow = wave >= IPW * WPI;     // (the loader wave, wave kWaves, too)
   const int slot = shadow ? 0 : wave / WPI;  // IC of this wave within the workgroup
   const int pos = shadow ? 0 : wave % WPI;   // cells 16*pos .. 16*pos + 15 of it
@@ -1180,21 +1069,12 @@ __global__ __launch_bounds__(cells_threads<CC>(), 1) void chain_rollout_cells_ke
   };
   if constexpr (kLd) {
     if (wave == kWaves) {  // the loader: the compute waves' ring barriers and step barriers, in order
-#ifdef HF_LDR_PRIO  // A/B: the loader's wave priority
-      __builtin_amdgcn_s_setprio(HF_LDR_PRIO);
-#endif
       R.loader_prime();
       R.loader_next();  // CC::begin
       const int ro_chunks = R.chunks - W.layers * CC::kLayerChunks;
       for (int t = 0; t < T; ++t) {  // one forward pass: update layers, then the readout
         for (int l = 0; l < W.layers; ++l) {
-          for (int k = 0; k < CC::kLayerChunks; ++k) {
-            R.loader_next();
-            // state t is in LDS from the end of step t-1 to this step's FV
-            // (after the second step barrier below): its outputs, off the lead's path
-            if (kLdEmit && l == 0 && k == 0)
-              for (int sl = 0; sl < IPW; ++sl) emit(sl, t);
-          }
+          for (int k = 0; k < CC::kLayerChunks; ++k) R.loader_next();
           if constexpr (CC::kLayerBarrier) lds_barrier();  // the layer's halo trade (CellHalo::exchange)
         }
         for (int k = 0; k < ro_chunks; ++k) R.loader_next();
@@ -1202,15 +1082,13 @@ __global__ __launch_bounds__(cells_threads<CC>(), 1) void chain_rollout_cells_ke
         lds_barrier();  // face fluxes
         lds_barrier();  // new state
       }
-      if (kLdEmit)
-        for (int sl = 0; sl < IPW; ++sl) emit(sl, T);
       R.drain();
       return;
     }
   }
   const bool out = lead && live;
   float *ftj = (flux_traj && out) ? flux_traj + b * (int64_t)T * NX : nullptr;
-  if (!kLdEmit && lead) emit(slot, 0);
+  if (lead) emit(slot, 0);
   R.prime();
   typename CC::Feed F;
   CC::begin(R, F);
@@ -1249,9 +1127,9 @@ __global__ __launch_bounds__(cells_threads<CC>(), 1) void chain_rollout_cells_ke
     }
     lds_barrier();  // new state visible to every wave
     // the lead's outputs of the new state overlap the other waves' next
-    // forward (nothing writes the state again before this step's FV); with a
-    // loader wave, the loader writes them
-    if (!kLdEmit && lead) emit(slot, t + 1);
+    // forward (nothing writes the state again before this step's FV; the loader
+    // wave writing them instead measured equal on cfg2, profiles/r02_cfg2_loader_ab.json)
+    if (lead) emit(slot, t + 1);
   }
   R.drain();
   if (!out) return;

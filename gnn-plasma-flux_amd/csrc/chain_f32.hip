@@ -73,11 +73,8 @@ struct CoreF32T {
 #ifndef HF_DIAG_NODS  // timing diagnostic only: results are wrong
     load_unit(F, (U + 1) % kUPC, R.lane);
 #endif
-#ifndef HF_F32_DEFU
-#define HF_F32_DEFU 0
-#endif
-    // after unit DEFU+1's fragment reads of the new chunk (A/B: HF_F32_DEFU 0..2)
-    if constexpr (DEF && U == HF_F32_DEFU) R.issue_pending();
+    // after unit 1's fragment reads of the new chunk
+    if constexpr (DEF && U == 0) R.issue_pending();
   }
   // B operand of flat k-step KS (0..63) of an update layer: k-steps 0..31 read
   // h itself, 32..63 the neighbour mean (h[i+1] + h[i-1]) / 2.  H = CellHalo:
@@ -365,24 +362,15 @@ struct CoreF32T {
   }
 };
 
-#ifndef HF_F32_DEFER
-#define HF_F32_DEFER 1
-#endif
-using CoreF32 = CoreF32T<2, kRingSlots, false, HF_F32_DEFER != 0>;
+using CoreF32 = CoreF32T<2, kRingSlots, false, true>;  // IC-per-wave: deferred ring DMA (DEF)
 
 // ---------------------------------------------------------------------------
 // Cell-split small-batch kernels (chain_common.h) on the f32 core at MT = 1.
-#ifndef HF_CELLS_AHEAD
-#define HF_CELLS_AHEAD 4
-#endif
-constexpr int kCellsAhead = HF_CELLS_AHEAD;
+constexpr int kCellsAhead = 4;
 // The cell-split kernels' core: a fifth (loader) wave issues the weight
 // ring's DMA, so the four compute waves carry none (chain_common.h Ring
-// LOADER).  HF_CELLS_LOADER=0 builds the four-wave form (A/B).
-#ifndef HF_CELLS_LOADER
-#define HF_CELLS_LOADER 1
-#endif
-using CellCoreLd = CoreF32T<kCellsAhead, kCellsAhead + 1, HF_CELLS_LOADER != 0>;
+// LOADER).
+using CellCoreLd = CoreF32T<kCellsAhead, kCellsAhead + 1, true>;
 }  // namespace
 
 // Whether the cell-split kernel beats the IC-per-wave kernel for B ICs of nx
@@ -470,9 +458,6 @@ __device__ __forceinline__ void pack_chain_f32_at(const GraphW &w, float *__rest
   }
   small[i] = v;
 }
-__global__ void pack_chain_f32_kernel(GraphW w, float *__restrict__ stream, int64_t nstream, float *__restrict__ small) {
-  pack_chain_f32_at(w, stream, nstream, small, (int64_t)blockIdx.x * 256 + threadIdx.x);
-}
 
 // The update layers' transposed weights for chain_train_bwd_kernel, in the
 // f32 stream format, layers L-1 .. 0: A(n, k) = W_l[k][n] (k < H: W_a^T) or
@@ -488,9 +473,6 @@ __device__ __forceinline__ void pack_chain_bwd_f32_at(const GraphW &w, float *__
   const float *W = readout ? w.w_e : w.w_l + l * w.lsw;
   const float half = readout ? 1.f : 0.5f;
   stream[idx] = s < kKS ? W[(int64_t)k * 2 * kH + n] : half * W[(int64_t)k * 2 * kH + kH + n];
-}
-__global__ void pack_chain_bwd_f32_kernel(GraphW w, float *__restrict__ stream, int64_t nstream, int ro) {
-  pack_chain_bwd_f32_at(w, stream, nstream, ro, (int64_t)blockIdx.x * 256 + threadIdx.x);
 }
 // Both packs in one launch (the training forward packs the backward's
 // transposed stream too: the parameters do not change between the two passes
@@ -518,9 +500,9 @@ hipError_t train_fwd_launch(const ChainW &cw, const float *b2p, const float *nf,
 }
 template <int MT>
 hipError_t train_bwd_launch(const ChainW &cw, int64_t B, float *g0, int64_t gstride, const unsigned *mbits,
-                            const float *dPQ, const EdgeFold &ef, hipStream_t s) {
+                            const float *dPQ, hipStream_t s) {
   hipLaunchKernelGGL((chain_train_bwd_kernel<CoreF32, MT>), dim3((unsigned)train_blocks<MT>(B)),
-                     dim3(64 * CoreF32::kNW), 0, s, cw, B, g0, gstride, mbits, dPQ, ef);
+                     dim3(64 * CoreF32::kNW), 0, s, cw, B, g0, gstride, mbits, dPQ);
   return hipGetLastError();
 }
 }  // namespace
@@ -533,27 +515,18 @@ int64_t chain_train_mask_bytes(int layers, int64_t N) { return (int64_t)(layers 
 int64_t chain_train_bwd_pack_bytes(int layers) { return (int64_t)16 * (layers + 1) * chain_chunk_bytes(kPrecF32); }
 
 hipError_t launch_chain_train_bwd_fused(const GraphW &w, int64_t B, int nx, float *g0, int64_t gstride,
-                                        const unsigned *mbits, void *pack, const float *dPQ, hipStream_t s,
-                                        const float *pq, const float *gflux, const float *w2, float *epart,
-                                        bool prepacked) {
-  // pq != nullptr: the readout's backward from the P/Q tape in this pass (EdgeFold), writing dPQ
-  const EdgeFold ef{pq, gflux, w2, const_cast<float *>(dPQ), epart};
-  const int L = w.layers;
-  if (B <= 0 || (L == 0 && !dPQ)) return hipSuccess;
-  float *stream = static_cast<float *>(pack);
-  const int64_t nstream = (int64_t)16 * (L + (dPQ ? 1 : 0)) * 2048;
-  if (!prepacked)
-    hipLaunchKernelGGL(pack_chain_bwd_f32_kernel, dim3((unsigned)(nstream / 256)), dim3(256), 0, s, w, stream, nstream,
-                       dPQ ? 1 : 0);
+                                        const unsigned *mbits, const void *bpack, const float *dPQ,
+                                        hipStream_t s) {
+  if (B <= 0) return hipSuccess;
   ChainW cw{};
-  cw.stream = stream;
-  cw.layers = L;
+  cw.stream = static_cast<const float *>(bpack);
+  cw.layers = w.layers;
   cw.prec = kPrecF32;
   switch (nx) {
-    case 16: return train_bwd_launch<1>(cw, B, g0, gstride, mbits, dPQ, ef, s);
-    case 32: return train_bwd_launch<2>(cw, B, g0, gstride, mbits, dPQ, ef, s);
-    case 48: return train_bwd_launch<3>(cw, B, g0, gstride, mbits, dPQ, ef, s);
-    case 64: return train_bwd_launch<4>(cw, B, g0, gstride, mbits, dPQ, ef, s);
+    case 16: return train_bwd_launch<1>(cw, B, g0, gstride, mbits, dPQ, s);
+    case 32: return train_bwd_launch<2>(cw, B, g0, gstride, mbits, dPQ, s);
+    case 48: return train_bwd_launch<3>(cw, B, g0, gstride, mbits, dPQ, s);
+    case 64: return train_bwd_launch<4>(cw, B, g0, gstride, mbits, dPQ, s);
     default: return hipErrorInvalidValue;
   }
 }
@@ -564,22 +537,18 @@ bool chain_train_fused_ok(const GraphW &w, int nx) {
 }
 
 hipError_t launch_chain_train_fwd_fused(const GraphW &w, const float *nf, int64_t B, int nx, float *fe, float *h0,
-                                        int64_t hstride, float *pq, unsigned *mbits, void *pack, hipStream_t s,
-                                        void *bpack, int ro) {
+                                        int64_t hstride, float *pq, unsigned *mbits, void *pack, void *bpack,
+                                        hipStream_t s) {
   if (B <= 0) return hipSuccess;
   const int L = w.layers;
   float *stream = static_cast<float *>(pack);
   const int64_t nstream = (int64_t)chain_chunks(L, kPrecF32) * chain_chunk_bytes(kPrecF32) / 4;
   float *small = stream + nstream;
   const int64_t total = nstream + 512 + kH * (3 + L);
-  if (bpack) {  // + the backward's stream (launch_chain_train_bwd_fused with prepacked)
-    const int64_t nb = (int64_t)16 * (L + (ro ? 1 : 0)) * 2048;
-    hipLaunchKernelGGL(pack_chain_train_f32_kernel, dim3((unsigned)((total + nb + 255) / 256)), dim3(256), 0, s, w,
-                       stream, nstream, small, total, static_cast<float *>(bpack), nb, ro);
-  } else {
-    hipLaunchKernelGGL(pack_chain_f32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, stream,
-                       nstream, small);
-  }
+  // + the backward's stream (launch_chain_train_bwd_fused), the readout's [W_a^T | W_b^T] first
+  const int64_t nb = (int64_t)16 * (L + 1) * 2048;
+  hipLaunchKernelGGL(pack_chain_train_f32_kernel, dim3((unsigned)((total + nb + 255) / 256)), dim3(256), 0, s, w,
+                     stream, nstream, small, total, static_cast<float *>(bpack), nb, 1);
   ChainW cw{};
   cw.stream = stream;
   cw.win = small;

@@ -540,14 +540,8 @@ struct CellF16x3T {
     readout_finish<1>(pf1, pb1, W.b2, ffwd, fbwd);
   }
 };
-#ifndef HF_CELLS_LOADER
-#define HF_CELLS_LOADER 1
-#endif
-using CellF16x3Ld = CellF16x3T<HF_CELLS_LOADER != 0>;  // with a loader wave (the cell-split kernels)
-#ifndef HF_K32_DEFER
-#define HF_K32_DEFER 1
-#endif
-constexpr bool kK32Defer = HF_K32_DEFER != 0;  // IC-per-wave f16x3 cores: deferred ring DMA (CoreF16x3T DEF)
+using CellF16x3Ld = CellF16x3T<true>;  // with a loader wave (the cell-split kernels)
+constexpr bool kK32Defer = true;       // IC-per-wave f16x3 cores: deferred ring DMA (CoreF16x3T DEF)
 
 }  // namespace
 

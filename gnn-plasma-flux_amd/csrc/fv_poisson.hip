@@ -337,11 +337,9 @@ __global__ __launch_bounds__(64 * kFftWaves, N >= 2048 ? 1 : 2) void fv_step_fft
   double2 v[V];
   // IC b's inputs are loaded before IC a's stores: loads and stores share
   // vmcnt, so a load issued after them would wait until they had drained
-  // (HF_FV_NO_PREFETCH: the old order, A/B builds only)
+  // (measured against the old order in profiles/r02_fv_prefetch_ab.md)
   FvIn<N> xb;
-#ifndef HF_FV_NO_PREFETCH
   if (two) fv_load<HYBRID, N>(in + b * ld_in, HYBRID ? face_flux + b * N : nullptr, lane, xb);
-#endif
   {
     FvIn<N> xa;
     fv_load<HYBRID, N>(in + a * ld_in, HYBRID ? face_flux + a * N : nullptr, lane, xa);
@@ -353,9 +351,6 @@ __global__ __launch_bounds__(64 * kFftWaves, N >= 2048 ? 1 : 2) void fv_step_fft
   }
   {
     double r[V];
-#ifdef HF_FV_NO_PREFETCH
-    if (two) fv_load<HYBRID, N>(in + b * ld_in, HYBRID ? face_flux + b * N : nullptr, lane, xb);
-#endif
     if (two)
       fv_update_in<HYBRID, N>(xb, out + b * ld_out, c, dt, nu, dx2, flux_out ? flux_out + b * ld_flux : nullptr,
                               metrics != nullptr, mb, lane, r);

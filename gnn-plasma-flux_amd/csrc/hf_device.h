@@ -318,10 +318,7 @@ constexpr int fft_lds_elems() { return N + N / 16; }
 
 // Stockham passes NS.. of an N-point transform.  v[t + r*(V/R)] holds index
 // lane + 64t + r*N/R; the first pass (NS == 1) reads v, the last writes it.
-#ifndef HF_FFT_MAX_RADIX
-#define HF_FFT_MAX_RADIX 16
-#endif
-constexpr int kFftMaxRadix = HF_FFT_MAX_RADIX;
+constexpr int kFftMaxRadix = 16;
 template <int N, int NS, bool INV>
 __device__ __forceinline__ void fft_passes(double2 (&v)[N / 64], double2 *lds, const double2 *__restrict__ tw,
                                            int lane) {

@@ -19,12 +19,6 @@ namespace tg {
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef float f16 __attribute__((ext_vector_type(16)));
 
-#ifndef HF_TG_KC
-#define HF_TG_KC 32
-#endif
-#ifndef HF_TG_WG
-#define HF_TG_WG 2
-#endif
 // timing diagnostics (CXXFLAGS_EXTRA=-DHF_DIAG_TG_*; results wrong): no stage
 // loads (NOGL), LDS stores (NOLS), stage barriers (NOBAR), partial-tile stores (NOEPI)
 #ifdef HF_DIAG_TG_NOGL
@@ -47,17 +41,11 @@ constexpr bool kDiagNoEpi = true;
 #else
 constexpr bool kDiagNoEpi = false;
 #endif
-#ifndef HF_TG_FRAG_AHEAD
-#define HF_TG_FRAG_AHEAD 1
-#endif
-#ifndef HF_TG_PAIR_LOOP
-#define HF_TG_PAIR_LOOP 1
-#endif
-constexpr bool kFragAhead = HF_TG_FRAG_AHEAD, kPairLoop = HF_TG_PAIR_LOOP;
-constexpr int kBM = 128, kBN = 128, kKC = HF_TG_KC;  // reduction chunk per stage (32; 16: a build knob)
-constexpr int kNQ = kBM * kKC / 4 / 256;             // float4 per thread per operand per stage
-constexpr int kIMSh = kKC == 32 ? 3 : 2;             // log2(float4 per [i][r] row)
-static_assert(kKC == 32 || kKC == 16, "stage depth");
+constexpr int kBM = 128, kBN = 128, kKC = 32;  // reduction chunk per stage
+constexpr int kTgWG = 2;                        // workgroups per CU (launch bounds)
+constexpr int kNQ = kBM * kKC / 4 / 256;        // float4 per thread per operand per stage
+constexpr int kIMSh = 3;                        // log2(float4 per [i][r] row)
+static_assert(kKC == 4 << kIMSh, "stage depth");
 constexpr int kStrIM = kKC + 4;   // [i][r] tile rows: 36 floats (conflict-free b128 reads of 16 lanes)
 constexpr int kStrRM = kBM + 8;   // [r][i] tile rows: 136 floats (the two lane halves 4 rows apart land on disjoint banks)
 constexpr int kTileF = (kBM * kStrIM > kKC * kStrRM) ? kBM * kStrIM : kKC * kStrRM;
@@ -98,7 +86,6 @@ struct VPlain {
     return *reinterpret_cast<const f4 *>(p + (unsigned)(w.off + c));
   }
   // two-phase form (tgemm_kernel): load2 issues the loads, combine forms the value
-  static constexpr bool kTwo = false;
   __device__ void load2(const Row &w, int c, f4 &a, f4 &) const { a = load4(w, c); }
   __device__ f4 combine(int, const f4 &a, const f4 &) const { return a; }
   bool fits32() const { return rows * ld + cols + (rows >> hshift) * hoff < (int64_t(1) << 31); }
@@ -149,7 +136,6 @@ struct VStencil {
   // made the compiler wait for both loads right where they were issued, at the
   // start of the stage, before its MFMAs; a branch on c < C (uniform only when
   // C is a multiple of the stage depth) spilled the pair to scratch.
-  static constexpr bool kTwo = true;
   __device__ void load2(const Row &w, int c, f4 &a, f4 &b) const {
     c = c < 2 * C ? c : 2 * C - 4;
     const bool self = c < C;
@@ -235,7 +221,6 @@ struct VPQ {
     c = c < H ? c : H - 4;
     return *reinterpret_cast<const f4 *>(W + (unsigned)(w.off + c));
   }
-  static constexpr bool kTwo = false;
   __device__ void load2(const Row &w, int c, f4 &a, f4 &) const { a = load4(w, c); }
   __device__ f4 combine(int, const f4 &a, const f4 &) const { return a; }
   bool fits32() const { return 2LL * H * H < (int64_t(1) << 31); }
@@ -300,39 +285,18 @@ struct EpiMsg {
 // views, unsplit views): no clamps or zeroed rows, and each thread's row
 // handles are stepped by kKC per stage instead of recomputed (the stencil's
 // cell index without a division).
-#ifndef HF_TG_XCD
-#define HF_TG_XCD 1
-#endif
-// HF_TG_XCD (measured +0.8 % on the training step, profiles/r05_train_tgemm_xcd_prio_ab.txt):
-// pairs of consecutive tiles (x fastest) on one XCD.  Blocks b and
+// Pairs of consecutive tiles (x fastest) on one XCD (measured +0.8 % on the
+// training step, profiles/r05_train_tgemm_xcd_prio_ab.txt).  Blocks b and
 // b + 8 share an XCD (MI355X_MICROARCH.md, workgroup dispatch); consecutive
 // tiles of a weight-gradient split read the same rows (the two column tiles
 // of [h ; agg h], or the P and Q halves against h[L]).
 __device__ __forceinline__ void tg_block(unsigned &bx, unsigned &by, unsigned &bz) {
-  bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-  if (HF_TG_XCD) {
-    const unsigned gx = gridDim.x, gy = gridDim.y, T = gx * gy * gridDim.z;
-    unsigned L = bx + gx * (by + gy * bz);
-    if (L < T - T % 16) L = 2 * (8 * (L >> 4) + (L & 7)) + ((L >> 3) & 1);
-    bx = L % gx;
-    by = (L / gx) % gy;
-    bz = L / (gx * gy);
-  }
-}
-
-// HF_TG_STAGGER > 0 (a build knob): a workgroup whose waves hold an odd wave
-// slot on their SIMDs (the second workgroup of a CU, HW_REG_HW_ID.WAVE_ID)
-// starts s_sleep(HF_TG_STAGGER) x 64 cycles late, so that the two workgroups
-// sharing each SIMD reach their LDS stores and barriers at different times
-// (MI355X_MICROARCH.md, "two waves that run the same program")
-#ifndef HF_TG_STAGGER
-#define HF_TG_STAGGER 0
-#endif
-__device__ __forceinline__ void tg_stagger() {
-  if constexpr (HF_TG_STAGGER > 0) {
-    const unsigned slot = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 4);  // HW_ID[3:0]
-    if (slot & 1) __builtin_amdgcn_s_sleep(HF_TG_STAGGER);
-  }
+  const unsigned gx = gridDim.x, gy = gridDim.y, T = gx * gy * gridDim.z;
+  unsigned L = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
+  if (L < T - T % 16) L = 2 * (8 * (L >> 4) + (L & 7)) + ((L >> 3) & 1);
+  bx = L % gx;
+  by = (L / gx) % gy;
+  bz = L / (gx * gy);
 }
 
 // One output tile (bx, by) of split bz: the body of tgemm_kernel and of
@@ -357,17 +321,12 @@ __device__ __forceinline__ void tgemm_tile(LA ga, LB gb, Epi epi, int64_t I, int
     for (int b = 0; b < 2; ++b)
 #pragma unroll
       for (int v = 0; v < 16; ++v) acc[a][b][v] = 0.f;
-  // Two register sets of 4 float4 per operand: the loads of stage s+2 are
-  // issued while stage s computes and land in LDS at the end of stage s+1, so
-  // each load has two stages (~2 x 4096 MFMA cycles per wave) to arrive.
-#ifndef HF_TG_DEPTH
-#define HF_TG_DEPTH 1
-#endif
-  constexpr int kDepth = HF_TG_DEPTH;  // stages of loads in flight: 1 (double buffer) and 2 measured equal
-  // (profiles/r03_train_gemm_depth_ab.txt); 1 holds ~30 fewer registers
-  f4 ra[kDepth][kNQ], rbv[kDepth][kNQ], csum = f4{0.f, 0.f, 0.f, 0.f};
+  // One register set of 4 float4 per operand: the loads of stage s+1 are issued
+  // while stage s computes and land in LDS at its end (a second set in flight
+  // measured equal and holds ~30 more registers, profiles/r03_train_gemm_depth_ab.txt)
+  f4 ra[kNQ], rbv[kNQ], csum = f4{0.f, 0.f, 0.f, 0.f};
   // second loads of two-phase views (the stencil's neighbour rows)
-  f4 ra2[LA::kTwo ? kDepth : 1][kNQ], rb2[LB::kTwo ? kDepth : 1][kNQ];
+  f4 ra2[kNQ], rb2[kNQ];
   // thread -> (global row, col) of its 4 float4 per operand per stage.  The
   // rows of an [i][r] operand are the same every stage: their handles are made once.
   typename LA::Row rowa[kNQ];
@@ -401,27 +360,27 @@ __device__ __forceinline__ void tgemm_tile(LA ga, LB gb, Epi epi, int64_t I, int
   };
   // issues the stage's loads only; lstore forms the values (view combine, the
   // zeroed reduction rows past the split's end) when it writes them to LDS
-  auto gload = [&](int set, int64_t r0) {
+  auto gload = [&](int64_t r0) {
 #pragma unroll
     for (int q = 0; q < kNQ; ++q) {
       const int idx = t + 256 * q;
       if constexpr (EX) {
-        ga.load2x(rowa[q], col_a(q, r0), ra[set][q], ra2[LA::kTwo ? set : 0][q]);
-        gb.load2x(rowb[q], col_b(q, r0), rbv[set][q], rb2[LB::kTwo ? set : 0][q]);
+        ga.load2x(rowa[q], col_a(q, r0), ra[q], ra2[q]);
+        gb.load2x(rowb[q], col_b(q, r0), rbv[q], rb2[q]);
         ga.adv(rowa[q]);
         gb.adv(rowb[q]);
       } else {
-        ga.load2(ARM ? ga.row(r0 + (idx >> 5)) : rowa[q], col_a(q, r0), ra[set][q], ra2[LA::kTwo ? set : 0][q]);
-        gb.load2(BRM ? gb.row(r0 + (idx >> 5)) : rowb[q], col_b(q, r0), rbv[set][q], rb2[LB::kTwo ? set : 0][q]);
+        ga.load2(ARM ? ga.row(r0 + (idx >> 5)) : rowa[q], col_a(q, r0), ra[q], ra2[q]);
+        gb.load2(BRM ? gb.row(r0 + (idx >> 5)) : rowb[q], col_b(q, r0), rbv[q], rb2[q]);
       }
     }
   };
-  auto lstore = [&](int buf, int set, int64_t r0) {
+  auto lstore = [&](int buf, int64_t r0) {
 #pragma unroll
     for (int q = 0; q < kNQ; ++q) {
       const int idx = t + 256 * q, im = (1 << kIMSh) - 1;
-      f4 va = ga.combine(col_a(q, r0), ra[set][q], ra2[LA::kTwo ? set : 0][q]);
-      f4 vb = gb.combine(col_b(q, r0), rbv[set][q], rb2[LB::kTwo ? set : 0][q]);
+      f4 va = ga.combine(col_a(q, r0), ra[q], ra2[q]);
+      f4 vb = gb.combine(col_b(q, r0), rbv[q], rb2[q]);
       const bool in = EX || r0 + (idx >> 5) < re;
       if (ARM) va = f4{in ? va[0] : 0.f, in ? va[1] : 0.f, in ? va[2] : 0.f, in ? va[3] : 0.f};
       if (BRM) vb = f4{in ? vb[0] : 0.f, in ? vb[1] : 0.f, in ? vb[2] : 0.f, in ? vb[3] : 0.f};
@@ -433,21 +392,15 @@ __device__ __forceinline__ void tgemm_tile(LA ga, LB gb, Epi epi, int64_t I, int
     }
   };
   if (rb < re) {
-    gload(0, rb);
-    lstore(0, 0, rb);
-    if (kDepth == 2 && rb + kKC < re) gload(kDepth - 1, rb + kKC);
+    gload(rb);
+    lstore(0, rb);
   }
   __syncthreads();
   // one stage; register sets and LDS buffers indexed by the compile-time parity
   auto stage = [&](auto parity, int64_t r0) {
     constexpr int cur = decltype(parity)::value;
-    // LDS[cur] holds stage r0; depth 2: register set cur^1 holds (in flight) stage r0 + kKC
-    if (kDiagNoGl) {
-    } else if (kDepth == 2) {
-      if (r0 + 2 * kKC < re) gload(cur % kDepth, r0 + 2 * kKC);
-    } else if (r0 + kKC < re) {
-      gload(0, r0 + kKC);
-    }
+    // LDS[cur] holds stage r0
+    if (!kDiagNoGl && r0 + kKC < re) gload(r0 + kKC);
     const float *A = sA[cur], *B = sB[cur];
     // fragments of group g (8 reduction rows): av[x][s] / bv[x][s] for MFMA step s
     auto frag = [&](int g, float (&av)[2][4], float (&bv)[2][4]) {
@@ -480,50 +433,31 @@ __device__ __forceinline__ void tgemm_tile(LA ga, LB gb, Epi epi, int64_t I, int
 #pragma unroll
           for (int b = 0; b < 2; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[a][s], bv[b][s], acc[a][b], 0, 0, 0);
     };
-    if constexpr (kFragAhead) {
-      // group g + 1's fragments are read while group g's 16 MFMAs run: the
-      // wave keeps its own MFMA pipe fed instead of waiting one LDS latency
-      // per MFMA step for the other wave of its SIMD to cover it
-      float av[2][2][4], bv[2][2][4];
-      frag(0, av[0], bv[0]);
+    // group g + 1's fragments are read while group g's 16 MFMAs run: the
+    // wave keeps its own MFMA pipe fed instead of waiting one LDS latency
+    // per MFMA step for the other wave of its SIMD to cover it
+    float av[2][2][4], bv[2][2][4];
+    frag(0, av[0], bv[0]);
 #pragma unroll
-      for (int g = 0; g < kKC / 8; ++g) {
-        if (g + 1 < kKC / 8) frag(g + 1, av[(g + 1) & 1], bv[(g + 1) & 1]);
-        __builtin_amdgcn_sched_barrier(0);  // the next group's ds_reads stay ahead of this group's MFMAs
-        mfma16(av[g & 1], bv[g & 1]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    } else {
-#pragma unroll
-      for (int g = 0; g < kKC / 8; ++g) {
-        float av[2][4], bv[2][4];
-        frag(g, av, bv);
-        mfma16(av, bv);
-      }
+    for (int g = 0; g < kKC / 8; ++g) {
+      if (g + 1 < kKC / 8) frag(g + 1, av[(g + 1) & 1], bv[(g + 1) & 1]);
+      __builtin_amdgcn_sched_barrier(0);  // the next group's ds_reads stay ahead of this group's MFMAs
+      mfma16(av[g & 1], bv[g & 1]);
+      __builtin_amdgcn_sched_barrier(0);
     }
-    if (!kDiagNoLs && r0 + kKC < re) lstore(cur ^ 1, (cur ^ 1) % kDepth, r0 + kKC);
+    if (!kDiagNoLs && r0 + kKC < re) lstore(cur ^ 1, r0 + kKC);
     if (!kDiagNoBar) __syncthreads();
   };
-  if (kPairLoop) {
-    // stage pairs, then an odd last stage: no exit from between the two
-    // parities, whose accumulators the compiler otherwise copied to the exit's
-    // registers every pair (64 VGPRs and 32 moves behind an MFMA drain)
-    const int nst = rb < re ? (int)((re - rb + kKC - 1) / kKC) : 0;
-    int k = 0;
-    for (; k + 2 <= nst; k += 2) {
-      stage(std::integral_constant<int, 0>{}, rb + (int64_t)k * kKC);
-      stage(std::integral_constant<int, 1>{}, rb + (int64_t)(k + 1) * kKC);
-    }
-    if (k < nst) stage(std::integral_constant<int, 0>{}, rb + (int64_t)k * kKC);
-  } else {
-    for (int64_t r0 = rb; r0 < re;) {
-      stage(std::integral_constant<int, 0>{}, r0);
-      r0 += kKC;
-      if (r0 >= re) break;
-      stage(std::integral_constant<int, 1>{}, r0);
-      r0 += kKC;
-    }
+  // stage pairs, then an odd last stage: no exit from between the two
+  // parities, whose accumulators the compiler otherwise copied to the exit's
+  // registers every pair (64 VGPRs and 32 moves behind an MFMA drain)
+  const int nst = rb < re ? (int)((re - rb + kKC - 1) / kKC) : 0;
+  int k = 0;
+  for (; k + 2 <= nst; k += 2) {
+    stage(std::integral_constant<int, 0>{}, rb + (int64_t)k * kKC);
+    stage(std::integral_constant<int, 1>{}, rb + (int64_t)(k + 1) * kKC);
   }
+  if (k < nst) stage(std::integral_constant<int, 0>{}, rb + (int64_t)k * kKC);
   if constexpr (Epi::kBlock) {
     static_assert(kBM * EpiMsg::kS <= 2 * kBufF, "a parked P or Q tile fits one operand's two buffers");
     epi.block(acc, sA[0], sB[0], i0, j0, I, wi, wj, lane, t);
@@ -583,11 +517,10 @@ __device__ __forceinline__ void tgemm_tile(LA ga, LB gb, Epi epi, int64_t I, int
 }
 
 template <class LA, bool ARM, class LB, bool BRM, class Epi, bool COLSUM, bool EX = false>
-__global__ __launch_bounds__(256, HF_TG_WG) void tgemm_kernel(LA ga, LB gb, Epi epi, int64_t I, int64_t J, int64_t R,
+__global__ __launch_bounds__(256, kTgWG) void tgemm_kernel(LA ga, LB gb, Epi epi, int64_t I, int64_t J, int64_t R,
                                                        int64_t rsplit, float *bias_part) {
   unsigned bx, by, bz;
   tg_block(bx, by, bz);
-  tg_stagger();
   tgemm_tile<LA, ARM, LB, BRM, Epi, COLSUM, EX>(ga, gb, epi, I, J, R, rsplit, bias_part, bx, by, bz);
 }
 
@@ -607,19 +540,15 @@ struct TgBatch {
   int64_t S;  // splits per problem
 };
 template <class LA, bool ARM, class LB, bool BRM, class Epi, bool COLSUM, bool EX = false>
-__global__ __launch_bounds__(256, HF_TG_WG) void tgemm_batch_kernel(TgBatch<LA, LB, Epi> bt, int64_t I, int64_t J,
+__global__ __launch_bounds__(256, kTgWG) void tgemm_batch_kernel(TgBatch<LA, LB, Epi> bt, int64_t I, int64_t J,
                                                              int64_t R, int64_t rsplit) {
   unsigned bx, by, bz;
   tg_block(bx, by, bz);
-  tg_stagger();
   const unsigned pb = bz / (unsigned)bt.S, sz = bz - pb * (unsigned)bt.S;
   tgemm_tile<LA, ARM, LB, BRM, Epi, COLSUM, EX>(bt.a[pb], bt.b[pb], bt.e[pb], I, J, R, rsplit, bt.bias_part[pb], bx, by,
                                                 sz);
 }
 
-#ifndef HF_TG_EXACT
-#define HF_TG_EXACT 1
-#endif
 // EXOK (both operands RM): the exact kernel where the shapes allow it
 template <class LA, bool ARM, class LB, bool BRM, class Epi, bool COLSUM = false, bool EXOK = false>
 hipError_t tgemm(const LA &ga, const LB &gb, const Epi &epi, int64_t I, int64_t J, int64_t R, int splits,
@@ -632,7 +561,7 @@ hipError_t tgemm(const LA &ga, const LB &gb, const Epi &epi, int64_t I, int64_t 
   const int64_t S = R > 0 ? (R + rsplit - 1) / rsplit : 1;
   dim3 grid((unsigned)((I + kBM - 1) / kBM), (unsigned)((J + kBN - 1) / kBN), (unsigned)S);
   if constexpr (EXOK && ARM && BRM) {
-    if (HF_TG_EXACT && R > 0 && I % kBM == 0 && J % kBN == 0 && R % kKC == 0 && ga.exact_ok(R) && gb.exact_ok(R)) {
+    if (R > 0 && I % kBM == 0 && J % kBN == 0 && R % kKC == 0 && ga.exact_ok(R) && gb.exact_ok(R)) {
       hipLaunchKernelGGL((tgemm_kernel<LA, ARM, LB, BRM, Epi, COLSUM, true>), grid, dim3(256), 0, s, ga, gb, epi, I, J,
                          R, rsplit, bias_part);
       return hipGetLastError();
@@ -649,7 +578,7 @@ template <class LA, class LB, class Epi, bool COLSUM>
 hipError_t tgemm_batch(TgBatch<LA, LB, Epi> bt, int64_t I, int64_t J, int64_t R, int splits, hipStream_t s) {
   if (I <= 0 || J <= 0 || bt.n <= 0) return hipSuccess;
   if (bt.n > kTgMaxBatch) return hipErrorInvalidValue;
-  bool exact = HF_TG_EXACT && R > 0 && I % kBM == 0 && J % kBN == 0 && R % kKC == 0;
+  bool exact = R > 0 && I % kBM == 0 && J % kBN == 0 && R % kKC == 0;
   for (int p = 0; p < bt.n; ++p) {
     if (!bt.a[p].fits32() || !bt.b[p].fits32()) return hipErrorInvalidValue;
     exact = exact && bt.a[p].exact_ok(R) && bt.b[p].exact_ok(R);

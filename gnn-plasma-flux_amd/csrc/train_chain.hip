@@ -81,13 +81,7 @@ inline unsigned part_reduce_blocks(int64_t I, int64_t J, int64_t nbias) {
 // slice q sums splits [qS/SL, (q+1)S/SL) in order, then the slice sums are
 // added in a fixed pairwise tree (deterministic).  1 KiB per wave load
 // instead of 256 B.
-#ifndef HF_PR_SLICES
-#define HF_PR_SLICES 16
-#endif
-#ifndef HF_PR_UNROLL
-#define HF_PR_UNROLL 4
-#endif
-constexpr int kPrSlices = HF_PR_SLICES;
+constexpr int kPrSlices = 16, kPrUnroll = 4;
 static_assert(kPrSlices == 8 || kPrSlices == 16, "slices: a power of two, 32 x slices threads");
 __device__ __forceinline__ void part_reduce4_block(f4 (*s_q)[32], unsigned bx, unsigned by,
                                                    const float *__restrict__ part, int S, int64_t I, int64_t J,
@@ -110,7 +104,7 @@ __device__ __forceinline__ void part_reduce4_block(f4 (*s_q)[32], unsigned bx, u
   const int s0 = (int)((int64_t)S * q / kPrSlices), s1 = (int)((int64_t)S * (q + 1) / kPrSlices);
   f4 v = f4{0.f, 0.f, 0.f, 0.f};
   if (ok) {
-#pragma unroll HF_PR_UNROLL
+#pragma unroll kPrUnroll
     for (int sp = s0; sp < s1; ++sp) {
       const f4 x = src[(int64_t)sp * per + t];
 #pragma unroll
@@ -153,15 +147,14 @@ __global__ __launch_bounds__(32 * kPrSlices) void part_reduce4_kernel(const floa
 inline unsigned part_reduce4_blocks(int64_t I, int64_t J, int64_t nbias) {
   return (unsigned)((I * J / 4 + 31) / 32 + (nbias / 4 + 31) / 32);
 }
-// NP problems of one shape at per-problem strides (float4 form only): one launch
-inline bool launch_part_reduce_batch(int NP, const float *part, int64_t part_ps, int S, int64_t I, int64_t J,
+constexpr bool pr_job_ok(int64_t I, int64_t J, int64_t nbias) { return J % 4 == 0 && I % 4 == 0 && nbias % 4 == 0; }
+// NP problems of one shape at per-problem strides (float4 form only: pr_job_ok shapes): one launch
+inline void launch_part_reduce_batch(int NP, const float *part, int64_t part_ps, int S, int64_t I, int64_t J,
                                      float *out, int64_t out_ps, int ish, int64_t ld, int64_t hoff,
                                      const float *bias_part, int64_t bpart_ps, int64_t nbias, float *bias,
                                      int64_t bias_ps, hipStream_t s) {
-  if (!(J % 4 == 0 && I % 4 == 0 && nbias % 4 == 0)) return false;
   hipLaunchKernelGGL(part_reduce4_kernel, dim3(part_reduce4_blocks(I, J, nbias), (unsigned)NP), dim3(32 * kPrSlices), 0,
                      s, part, S, I, J, out, ish, ld, hoff, bias_part, nbias, bias, part_ps, out_ps, bpart_ps, bias_ps);
-  return true;
 }
 // Every split reduction of the fused backward in ONE launch, after the last
 // weight-gradient pass: the readout's dw2 / db2 (edge_partial_reduce_block,
@@ -213,15 +206,11 @@ inline PrJob pr_job(const float *part, int S, int64_t I, int64_t J, float *out, 
   return PrJob{part,    bpart,   out, bias, I, J, ld, hoff, nbias, part_ps, out_ps, bpart_ps, bias_ps,
                S,       ish,     part_reduce4_blocks(I, J, nbias), np};
 }
-inline bool pr_job_ok(int64_t I, int64_t J, int64_t nbias) { return J % 4 == 0 && I % 4 == 0 && nbias % 4 == 0; }
 
 // the float4 form where the shapes allow it
-#ifndef HF_PART_REDUCE4
-#define HF_PART_REDUCE4 1
-#endif
 inline void launch_part_reduce(const float *part, int S, int64_t I, int64_t J, float *out, int ish, int64_t ld,
                                int64_t hoff, const float *bias_part, int64_t nbias, float *bias, hipStream_t s) {
-  if (HF_PART_REDUCE4 && J % 4 == 0 && I % 4 == 0 && nbias % 4 == 0)
+  if (pr_job_ok(I, J, nbias))
     hipLaunchKernelGGL(part_reduce4_kernel, dim3(part_reduce4_blocks(I, J, nbias)), dim3(32 * kPrSlices), 0, s, part, S, I, J,
                        out, ish, ld, hoff, bias_part, nbias, bias, 0, 0, 0, 0);
   else
@@ -344,10 +333,7 @@ __global__ __launch_bounds__(256) void edge_backward_kernel(const float *__restr
 // products as edge_backward_kernel, bit for bit.  dw2 is accumulated per lane
 // half (P lanes the g_f terms, Q lanes the g_b terms) and joined at the end,
 // in a fixed order.
-#ifndef HF_EB_CELLS
-#define HF_EB_CELLS 8
-#endif
-constexpr int kEbCells = HF_EB_CELLS;  // cells per wave: 8 (47.5 us at B = 2000; 16: 51.0, 32: 51.3; r05_train_small_kernels_ab.txt)
+constexpr int kEbCells = 8;  // cells per wave: 8 (47.5 us at B = 2000; 16: 51.0, 32: 51.3; r05_train_small_kernels_ab.txt)
 __device__ __forceinline__ float other_half(float v) {  // v of lane l ^ 32
   const unsigned u = __float_as_uint(v);
   const auto s = __builtin_amdgcn_permlane32_swap(u, u, false, false);
@@ -802,25 +788,12 @@ __global__ __launch_bounds__(256) void loss_final_kernel(const float *__restrict
   }
 }
 
-#ifndef HF_WGRAD_SPLITS
-#define HF_WGRAD_SPLITS 256
-#endif
-constexpr int kWgradSplits = HF_WGRAD_SPLITS;
-// the update layers' weight-gradient GEMMs in one launch (HF_TRAIN_WG_BATCH):
+constexpr int kWgradSplits = 256;
+// the update layers' weight-gradient GEMMs in one launch (tgemm_batch):
 // L x 2 column tiles x these splits fill the CUs on their own, and fewer
 // splits write and re-read fewer partial tiles
-#ifndef HF_WGRAD_BATCH_SPLITS
-#define HF_WGRAD_BATCH_SPLITS 64
-#endif
-constexpr int kWgradBatchSplits = HF_WGRAD_BATCH_SPLITS;
-// 1: the layers' split reductions in one launch
-#ifndef HF_PR_BATCH
-#define HF_PR_BATCH 1
-#endif
-#ifndef HF_INPUT_SPLITS
-#define HF_INPUT_SPLITS 512
-#endif
-constexpr int kInputSplits = HF_INPUT_SPLITS;  // the input layer's weight-gradient splits
+constexpr int kWgradBatchSplits = 64;
+constexpr int kInputSplits = 512;  // the input layer's weight-gradient splits
 
 // The update layers' weight gradients on the chain (fused path: H = 128, chains
 // of nx % 32 == 0 cells), every layer in one launch, split-K over the cells m:
@@ -852,14 +825,7 @@ struct WgStencilBatch {
   int64_t in_rows;
   int in_blocks;
 };
-#ifndef HF_WGS_SPLITS
-#define HF_WGS_SPLITS 128
-#endif
-constexpr int kWgsSplits = HF_WGS_SPLITS;
-#ifndef HF_WGS_FRAG_AHEAD
-#define HF_WGS_FRAG_AHEAD 0
-#endif
-constexpr bool kWsFragAhead = HF_WGS_FRAG_AHEAD;
+constexpr int kWgsSplits = 128;
 __global__ __launch_bounds__(256, 2) void wgrad_stencil_kernel(WgStencilBatch bt, int64_t N, int nx, int64_t rsplit) {
   __shared__ float sA[2][kWsKC * kWsStr];
   __shared__ float sB[2][(kWsKC + 2) * kWsStr];
@@ -870,7 +836,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_stencil_kernel(WgStencilBatch bt
                              bt.in_nf, N, bt.in_rows, bt.in_part, bt.in_bpart);
     return;
   }
-  tg_stagger();
   const unsigned pb = blockIdx.x / (unsigned)bt.S, z = blockIdx.x - pb * (unsigned)bt.S;
   const float *__restrict__ G = bt.g[pb];
   const float *__restrict__ X = bt.x[pb];
@@ -951,25 +916,11 @@ __global__ __launch_bounds__(256, 2) void wgrad_stencil_kernel(WgStencilBatch bt
             for (int b = 0; b < 4; ++b)
               acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[a][s], bv[b][s], acc[a][b], 0, 0, 0);
       };
-      if constexpr (kWsFragAhead) {
-        // group g + 1's fragments are read (and formed) before group g's 32
-        // MFMAs issue: one LDS wait per group instead of one per MFMA step
-        float av[2][2][4], bv[2][4][4];
-        frag(0, av[0], bv[0]);
 #pragma unroll
-        for (int g = 0; g < kWsKC / 8; ++g) {
-          if (g + 1 < kWsKC / 8) frag(g + 1, av[(g + 1) & 1], bv[(g + 1) & 1]);
-          __builtin_amdgcn_sched_barrier(0);
-          mfma32(av[g & 1], bv[g & 1]);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      } else {
-#pragma unroll
-        for (int g = 0; g < kWsKC / 8; ++g) {
-          float av[2][4], bv[4][4];
-          frag(g, av, bv);
-          mfma32(av, bv);
-        }
+      for (int g = 0; g < kWsKC / 8; ++g) {
+        float av[2][4], bv[4][4];
+        frag(g, av, bv);
+        mfma32(av, bv);
       }
       if (k + 1 < nst) lstore(cur ^ 1);
       __syncthreads();
@@ -1003,126 +954,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_stencil_kernel(WgStencilBatch bt
     *reinterpret_cast<f4 *>(bt.bpart[pb] + (int64_t)z * kWsH + 4 * t) = v;
   }
 }
-// The readout's weight gradient (fused path, H = 128):
-//   part[z][c][k] = sum_{m in split z} dPQ[m][c] h[L][m][k]  (c < 2H, k < H)
-//   bias_part[z][c] = sum_{m in split z} dPQ[m][c]
-// tgemm's EpiPart / COLSUM layout and arithmetic bit for bit (the same MFMA
-// operands and order per output; the column sums in tgemm's thread order:
-// rows of one residue mod 8 in increasing order, then the 8 residues in
-// order), but ONE workgroup owns the whole 256 x 128 tile of a split, so that
-// h[L]'s rows are staged once instead of once per 128-row tile.  Stages of
-// 16 cells (the 256-wide dPQ rows would not leave room for two workgroups per
-// CU at 32): wave w = outputs c in [64w, 64w + 64) x all 128 k.
-constexpr int kWrKC = 16, kWrStrA = 2 * kWsH + 8;
-#ifndef HF_WGR_SPLITS
-#define HF_WGR_SPLITS 512
-#endif
-constexpr int kWgrSplits = HF_WGR_SPLITS;
-__global__ __launch_bounds__(256, 2) void wgrad_readout_kernel(const float *__restrict__ dPQ,
-                                                               const float *__restrict__ X, int64_t N, int64_t rsplit,
-                                                               float *__restrict__ part, float *__restrict__ bpart) {
-  __shared__ float sA[2][kWrKC * kWrStrA];
-  __shared__ float sB[2][kWrKC * kWsStr];
-  __shared__ f4 s_cs[8][64];
-  const unsigned z = blockIdx.x;
-  const int t = threadIdx.x, lane = t & 63, h = lane >> 5, wave = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int rb = (int)((int64_t)z * rsplit), re = (int)(rb + rsplit < N ? rb + rsplit : N);
-  const int nst = rb < re ? (re - rb) / kWrKC : 0;  // whole stages (host-checked)
-  // loads of a stage at r0: A (dPQ) rows r0 + (t >> 5) + 8u, float4 columns (t & 31) + 32p (u, p < 2);
-  // B (h) rows r0 + (t >> 5) + 8u, float4 column t & 31 (the column sums' thread order: residue t >> 5)
-  f4 ra[2][2], rx[2], cs[2] = {f4{0.f, 0.f, 0.f, 0.f}, f4{0.f, 0.f, 0.f, 0.f}};
-  const int g8 = t >> 5, c4 = 4 * (t & 31);
-  auto gload = [&](int r0) {
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int r = r0 + g8 + 8 * u;
-#pragma unroll
-      for (int p = 0; p < 2; ++p) ra[u][p] = *reinterpret_cast<const f4 *>(dPQ + (unsigned)(r * 2 * kWsH + 128 * p + c4));
-      rx[u] = *reinterpret_cast<const f4 *>(X + (unsigned)(r * kWsH + c4));
-    }
-  };
-  auto lstore = [&](int buf) {
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int row = g8 + 8 * u;
-#pragma unroll
-      for (int p = 0; p < 2; ++p) {
-        *reinterpret_cast<f4 *>(&sA[buf][row * kWrStrA + 128 * p + c4]) = ra[u][p];
-        cs[p] += ra[u][p];
-      }
-      *reinterpret_cast<f4 *>(&sB[buf][row * kWsStr + c4]) = rx[u];
-    }
-  };
-  f16 acc[2][4];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-#pragma unroll
-      for (int v = 0; v < 16; ++v) acc[a][b][v] = 0.f;
-  if (nst > 0) {
-    gload(rb);
-    lstore(0);
-  }
-  __syncthreads();
-  auto stage = [&](auto parity, int k) {
-    constexpr int cur = decltype(parity)::value;
-    if (k + 1 < nst) gload(rb + (k + 1) * kWrKC);
-    const float *A = sA[cur], *B = sB[cur];
-#pragma unroll
-    for (int g = 0; g < kWrKC / 8; ++g) {
-      float av[2][4], bv[4][4];
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const int r = 8 * g + 4 * h + s;
-#pragma unroll
-        for (int x = 0; x < 2; ++x) av[x][s] = A[r * kWrStrA + 64 * wave + 32 * x + (lane & 31)];
-#pragma unroll
-        for (int b = 0; b < 4; ++b) bv[b][s] = B[r * kWsStr + 32 * b + (lane & 31)];
-      }
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-          for (int b = 0; b < 4; ++b)
-            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[a][s], bv[b][s], acc[a][b], 0, 0, 0);
-    }
-    if (k + 1 < nst) lstore(cur ^ 1);
-    __syncthreads();
-  };
-  int k = 0;
-  for (; k + 2 <= nst; k += 2) {
-    stage(std::integral_constant<int, 0>{}, k);
-    stage(std::integral_constant<int, 1>{}, k + 1);
-  }
-  if (k < nst) stage(std::integral_constant<int, 0>{}, k);
-  float *pz = part + (int64_t)z * 2 * kWsH * kWsH;
-#pragma unroll
-  for (int b = 0; b < 4; ++b) {
-    const int j = 32 * b + (lane & 31);
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int v = 0; v < 16; ++v)
-        pz[(64 * wave + 32 * a + 8 * (v >> 2) + 4 * h + (v & 3)) * kWsH + j] = acc[a][b][v];
-  }
-  // column sums: thread (g8, column quad) holds rows of residue g8; fold the 8 residues in order
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    s_cs[g8][(t & 31) + 32 * p] = cs[p];
-  }
-  __syncthreads();
-  if (t < 64) {
-    f4 v = s_cs[0][t];
-#pragma unroll
-    for (int q = 1; q < 8; ++q) v += s_cs[q][t];
-    *reinterpret_cast<f4 *>(bpart + (int64_t)z * 2 * kWsH + 4 * (t & 31) + 128 * (t >> 5)) = v;
-  }
-}
-inline int64_t wgr_rsplit(int64_t N) { return ((N + kWgrSplits - 1) / kWgrSplits + kWsKC - 1) / kWsKC * kWsKC; }
-inline int64_t wgr_splits(int64_t N) { return (N + wgr_rsplit(N) - 1) / wgr_rsplit(N); }
-
 // splits of N cells (whole stages)
 inline int64_t wgs_rsplit(int64_t N) { return ((N + kWgsSplits - 1) / kWgsSplits + kWsKC - 1) / kWsKC * kWsKC; }
 inline int64_t wgs_splits(int64_t N) { return (N + wgs_rsplit(N) - 1) / wgs_rsplit(N); }
@@ -1158,14 +989,10 @@ bool chain_train_ok(const GraphW &w, int chain_nx, int64_t N) {
          w.in_dim <= 8 && N > 0 && N * 2 * H + 2 * H < (int64_t(1) << 31);
 }
 
-#ifndef HF_TRAIN_FUSED
-#define HF_TRAIN_FUSED 1  // 0: the GEMM forward at every nx (A/B builds)
-#endif
-
 // h[0..L] | pq | (FluxGNN(4, 128, L <= 8): the fused forward's packed weights
 // and ReLU' bits; the chain length is unknown here, so the space is kept for
 // every chain)
-bool fused_width(const GraphW &w) { return HF_TRAIN_FUSED && chain_train_fused_ok(w, 64); }
+bool fused_width(const GraphW &w) { return chain_train_fused_ok(w, 64); }
 int64_t chain_tape_bytes(const GraphW &w, int64_t N) {
   return (int64_t)((w.layers + 1) * al256(sizeof(float) * N * w.hidden) + al256(sizeof(float) * N * 2 * w.hidden) +
                    (fused_width(w) ? al256((size_t)chain_train_pack_bytes(w.layers)) +
@@ -1185,65 +1012,22 @@ FusedTape fused_tape(const GraphW &w, int64_t N, const ChainTape &t) {
   char *m = p + al256((size_t)chain_train_pack_bytes(w.layers));
   return FusedTape{p, reinterpret_cast<unsigned *>(m), m + al256((size_t)chain_train_mask_bytes(w.layers, N))};
 }
-bool fused_chain(const GraphW &w, int nx, int64_t N) { return HF_TRAIN_FUSED && chain_train_fused_ok(w, nx) && N % nx == 0; }
+bool fused_chain(const GraphW &w, int nx, int64_t N) { return chain_train_fused_ok(w, nx) && N % nx == 0; }
 
-// 1: the fused path forms the readout's backward (dP, dQ, dw2, db2) from the
-// P/Q tape inside the backward pass (EdgeFold) instead of edge_backward_h128_kernel.
-// Measured and not kept (round 6, profiles/r06_train_edgefold_ab.txt): the
-// backward pass grew 349 -> 414 us against the 48 + 5 us it saved (the pass
-// runs one wave per SIMD, so the P/Q loads' latency is exposed).  Default 0
-// (chain_common.h holds the same switch for the kernel side).
-#ifndef HF_TRAIN_EDGE_FOLD
-#define HF_TRAIN_EDGE_FOLD 0
-#endif
-// 1: the readout's data gradient is the fused backward pass's first pass
-#ifndef HF_TRAIN_RO_FOLD
-#define HF_TRAIN_RO_FOLD 1
-#endif
-// 1: the fused path's update-layer weight-gradient GEMMs (independent once the
-// fused backward pass has every layer's g) run as ONE launch (tgemm_batch)
-#ifndef HF_TRAIN_WG_BATCH
-#define HF_TRAIN_WG_BATCH 1
-#endif
-// 1: those GEMMs on wgrad_stencil_kernel (H = 128, nx % 32 == 0)
-#ifndef HF_TRAIN_WGS
-#define HF_TRAIN_WGS 1
-#endif
-// 1: the readout's weight gradient on wgrad_readout_kernel (fused path, H = 128).
-// Measured and not kept (profiles/r06_train_wgs_ab.txt): 80.6 us at 500 splits
-// against tgemm's 76.4 us at 250, and the final reduction 21 -> 28 us (bitwise
-// equal gradients at 250 splits, where it fills only half the CUs)
-#ifndef HF_TRAIN_WGR
-#define HF_TRAIN_WGR 0
-#endif
-// 1: on that path, every split reduction in one launch (final_reduce_kernel)
-#ifndef HF_FINAL_REDUCE
-#define HF_FINAL_REDUCE 1
-#endif
-// 1: the float4 input-layer weight gradient (H = 128, F = 4)
-#ifndef HF_INPUT_WGRAD4
-#define HF_INPUT_WGRAD4 1
-#endif
-// 1: on the stencil path, that gradient's blocks on the stencil kernel's launch
-#ifndef HF_INPUT_IN_WGS
-#define HF_INPUT_IN_WGS 1
-#endif
 int64_t chain_backward_ws_bytes(const GraphW &w, int64_t N) {
   const int64_t H = w.hidden;
   size_t b = al256(sizeof(float) * N * 2 * H);  // dPQ
   b += 2 * al256(sizeof(float) * N * H);        // deltas
-  const int64_t S = std::max(tgemm_splits(N, kWgradSplits), wgr_splits(N));
+  const int64_t S = tgemm_splits(N, kWgradSplits);
   b += al256(sizeof(float) * S * 2 * H * H);    // weight-gradient partials (largest: 2H x H or H x 2H)
   b += al256(sizeof(float) * S * 2 * H);        // bias partials
   b += al256(sizeof(float) * kEdgeBlocks * (H + 1));
   b += al256(sizeof(float) * kInputSplits * H * (w.in_dim + 1));
-  if (fused_width(w)) {  // fused backward: g[0..L] side by side + the transposed weights
+  if (fused_width(w)) {  // fused backward: g[0..L] side by side
     b += (w.layers + 1) * al256(sizeof(float) * N * H);
     // + every update layer's weight-gradient partials (the layers' GEMMs in one launch)
     const int64_t SB = std::max(tgemm_splits(N, kWgradBatchSplits), wgs_splits(N));
-    if (HF_TRAIN_WG_BATCH) b += w.layers * (al256(sizeof(float) * SB * 2 * H * H) + al256(sizeof(float) * SB * 2 * H));
-    // + the readout's per-IC dw2 / db2 partials of the folded edge backward (B <= N / 16)
-    if (HF_TRAIN_EDGE_FOLD) b += al256(sizeof(float) * (N / 16 + 1) * (H + 1));
+    b += w.layers * (al256(sizeof(float) * SB * 2 * H * H) + al256(sizeof(float) * SB * 2 * H));
   }
   return (int64_t)b;
 }
@@ -1255,7 +1039,7 @@ hipError_t launch_chain_forward_train(const GraphW &w, const float *nf, int64_t 
   if (fused_chain(w, nx, N)) {  // (N = B * nx on a tagged chain)
     const FusedTape f = fused_tape(w, N, t);
     return launch_chain_train_fwd_fused(w, nf, N / nx, nx, flux, t.h[0], (int64_t)(al256(sizeof(float) * N * H) / 4),
-                                        t.pq, f.mbits, f.pack, s, f.bpack, HF_TRAIN_RO_FOLD);
+                                        t.pq, f.mbits, f.pack, f.bpack, s);
   }
 #define HF_IN_FWD(FF)                                                                                      \
   hipLaunchKernelGGL(input_forward_kernel<FF>, dim3((unsigned)((N * (H / 4) + 255) / 256)), dim3(256), 0, s, nf, \
@@ -1281,11 +1065,28 @@ hipError_t launch_chain_forward_train(const GraphW &w, const float *nf, int64_t 
   return hipGetLastError();
 }
 
+// The fused path's shapes (chain_train_fused_ok: in_dim kIn, hidden kH, L <= kMaxChainLayers)
+// always fit the batched launches and the float4 reductions below.
+static_assert(kMaxChainLayers <= kTgMaxBatch && kH == kWsH && kIn == 4, "fused path: one launch for every layer");
+static_assert(pr_job_ok(2 * kH, kH, kH) && pr_job_ok(kH, 2 * kH, kH) && pr_job_ok(kH, kIn, kH),
+              "fused path: float4 reductions");
+
 hipError_t launch_chain_backward(const GraphW &w, const float *nf, int64_t N, int nx, const void *tape,
                                  const float *grad_flux, float *grad_params, float *grad_nf, void *ws, hipStream_t s) {
   const int H = w.hidden, L = w.layers, F = w.in_dim, hsh = __builtin_ctz(H);
   const ChainTape t = carve_chain_tape(w, N, const_cast<void *>(tape));
   const GraphW g = graph_view_state_dict(grad_params, F, H, L);
+  // The two paths and the fused path's launch shapes:
+  // fused: FluxGNN(4, 128) on nx in {16, 32, 48, 64}: every layer's data gradient in one
+  //   IC-per-wave pass (chain_train_bwd_kernel); else a GEMM per layer
+  // wg_batch: the fused path's update-layer weight gradients in ONE launch
+  // wgs: that launch on wgrad_stencil_kernel (nx % 32 == 0), else tgemm_batch
+  // one_reduce: on the stencil path, every split reduction in one launch at the end (final_reduce_kernel)
+  // in_fold: on the stencil path, the input layer's weight-gradient blocks on the stencil kernel's launch
+  const bool fused = fused_chain(w, nx, N);
+  const bool wg_batch = fused && L >= 1;
+  const bool wgs = wg_batch && nx % kWsKC == 0 && N % kWsKC == 0 && N * kWsH < (int64_t(1) << 31);
+  const bool one_reduce = wgs, in_fold = wgs;
   char *p = static_cast<char *>(ws);
   auto take = [&](size_t bytes) {
     float *r = reinterpret_cast<float *>(p);
@@ -1293,38 +1094,22 @@ hipError_t launch_chain_backward(const GraphW &w, const float *nf, int64_t N, in
     return r;
   };
   const int64_t S = tgemm_splits(N, kWgradSplits);
-  const int64_t Sp = std::max(S, wgr_splits(N));  // (the partial buffers' splits, as chain_backward_ws_bytes)
-  float *dPQ = take(sizeof(float) * N * 2 * H);
-  float *dl[2] = {take(sizeof(float) * N * H), take(sizeof(float) * N * H)};
-  float *part = take(sizeof(float) * Sp * 2 * H * H);
-  float *bpart = take(sizeof(float) * Sp * 2 * H);
-  float *epart = take(sizeof(float) * kEdgeBlocks * (H + 1));
-  float *ipart = take(sizeof(float) * kInputSplits * H * (F + 1));
-  // fused (FluxGNN(4, 128) on nx <= 64): g[l] = G + l * gstride for every layer
-  const bool fused = fused_chain(w, nx, N);
-  const int64_t gstride = (int64_t)(al256(sizeof(float) * N * H) / 4);
-  float *G = fused ? take((L + 1) * al256(sizeof(float) * N * H)) : nullptr;
-  void *bpack = fused ? fused_tape(w, N, t).bpack : nullptr;  // (packed by the forward)
-  const bool wg_batch = fused && HF_TRAIN_WG_BATCH && L >= 1 && L <= kTgMaxBatch;
-  // the layers' weight gradients: wgrad_stencil_kernel where its shapes hold, else tgemm_batch
-  const bool wgs = wg_batch && HF_TRAIN_WGS && H == kWsH && nx % kWsKC == 0 && N % kWsKC == 0 &&
-                   N * kWsH < (int64_t(1) << 31);
   const int64_t SB = wgs ? wgs_splits(N) : tgemm_splits(N, kWgradBatchSplits);
-  // the readout's weight gradient: wgrad_readout_kernel on the fused path at H = 128
-  const bool wgr = fused && HF_TRAIN_WGR && H == kWsH && N % kWsKC == 0 && N * 2 * kWsH < (int64_t(1) << 31);
-  const int64_t SR = wgr ? wgr_splits(N) : S;
+  const int64_t gstride = (int64_t)(al256(sizeof(float) * N * H) / 4);
   const int64_t lpstride = (int64_t)(al256(sizeof(float) * SB * 2 * H * H) / 4),
                 lbstride = (int64_t)(al256(sizeof(float) * SB * 2 * H) / 4);
+  float *dPQ = take(sizeof(float) * N * 2 * H);
+  float *dl[2] = {take(sizeof(float) * N * H), take(sizeof(float) * N * H)};
+  float *part = take(sizeof(float) * S * 2 * H * H);
+  float *bpart = take(sizeof(float) * S * 2 * H);
+  float *epart = take(sizeof(float) * kEdgeBlocks * (H + 1));
+  float *ipart = take(sizeof(float) * kInputSplits * H * (F + 1)), *ipb = ipart + (int64_t)kInputSplits * H * F;
+  float *G = fused ? take((L + 1) * al256(sizeof(float) * N * H)) : nullptr;  // g[l] = G + l * gstride
   float *lpart = wg_batch ? take(L * al256(sizeof(float) * SB * 2 * H * H)) : nullptr;
   float *lbpart = wg_batch ? take(L * al256(sizeof(float) * SB * 2 * H)) : nullptr;
-  // the readout's backward folded into the backward pass (needs its readout pass: HF_TRAIN_RO_FOLD)
-  const bool efold = fused && HF_TRAIN_EDGE_FOLD && HF_TRAIN_RO_FOLD && H == 128;
-  float *efpart = efold ? take(sizeof(float) * (N / 16 + 1) * (H + 1)) : nullptr;
   hipError_t e;
-  // the fast path's split reductions all in one launch at the end (final_reduce_kernel)
-  const bool one_reduce = HF_FINAL_REDUCE && wgs && !efold && pr_job_ok(2 * H, H, H) && pr_job_ok(H, 2 * H, H) &&
-                          pr_job_ok(H, F, H);
   PrJobs jobs{};
+  // the reduction of part / bpart's splits: a job of the final launch, or a launch of its own
   auto reduce = [&](int64_t I, int64_t J, float *out, int ish, int64_t ld, int64_t hoff, int64_t nbias, float *bias,
                     int splits) {
     if (one_reduce) {
@@ -1335,9 +1120,7 @@ hipError_t launch_chain_backward(const GraphW &w, const float *nf, int64_t N, in
     return hipGetLastError();
   };
   // readout: dPQ, dw2, db2                                                          (:62-66)
-  if (efold) {
-    // (formed inside the backward pass below, then the readout weight gradient)
-  } else if (H == 128)
+  if (H == 128)
     hipLaunchKernelGGL(edge_backward_h128_kernel, dim3(kEdgeBlocks), dim3(256), 0, s, t.pq, N / nx, nx, w.w_2,
                        grad_flux, dPQ, epart);
   else
@@ -1350,131 +1133,100 @@ hipError_t launch_chain_backward(const GraphW &w, const float *nf, int64_t N, in
     jobs.gw2 = const_cast<float *>(g.w_2);
     jobs.gb2 = const_cast<float *>(g.b_2);
     jobs.eblocks = (unsigned)(H + 1);
-  } else if (!efold) {
+  } else {
     hipLaunchKernelGGL(edge_partial_reduce_kernel, dim3((unsigned)(H + 1)), dim3(256), 0, s, epart,
                        kEdgeBlocks, H, const_cast<float *>(g.w_2), const_cast<float *>(g.b_2));
   }
   // dW_e[c % H][(c / H) H + k] = sum_m dPQ[m][c] h[L][m][k]; db_e = column sums of dP
-  auto readout_wgrad = [&]() -> hipError_t {
-    if (wgr) {
-      hipLaunchKernelGGL(wgrad_readout_kernel, dim3((unsigned)SR), dim3(256), 0, s, dPQ, t.h[L], N, wgr_rsplit(N), part,
-                         bpart);
-    } else {
-      const VPlain A{dPQ, 2LL * H, N, kNoSplit, 0, 2 * H};
-      const VPlain B{t.h[L], H, N, kNoSplit, 0, H};
-      if ((e = tgemm<VPlain, true, VPlain, true, EpiPart, true, true>(A, B, EpiPart{part, 2LL * H, H}, 2 * H, H, N,
-                                                                 kWgradSplits, s, bpart)))
-        return e;
-    }
-    if ((e = reduce(2 * H, H, const_cast<float *>(g.w_e), hsh, 2LL * H, H, H, const_cast<float *>(g.b_e), (int)SR)))
-      return e;
-    return hipSuccess;
-  };
-  if (!efold && (e = readout_wgrad())) return e;
-  // dh[L] = [W_a ; W_b]^T dPQ, masked by ReLU'(h[L]) (fused: the first pass of chain_train_bwd_kernel)
-  int cur = 0;
-  const bool fold = fused && HF_TRAIN_RO_FOLD;
-  if (!fold) {
+  {
     const VPlain A{dPQ, 2LL * H, N, kNoSplit, 0, 2 * H};
-    const VPlain B{w.w_e, 2LL * H, 2LL * H, hsh, H, H};  // B(r = c, j = k) = [W_a ; W_b][c][k]
-    float *gL = fused ? G + L * gstride : dl[cur];
-    if ((e = tgemm<VPlain, false, VPlain, true>(A, B, EpiMask{gL, H, t.h[L], H}, N, H, 2 * H, 1, s))) return e;
+    const VPlain B{t.h[L], H, N, kNoSplit, 0, H};
+    if ((e = tgemm<VPlain, true, VPlain, true, EpiPart, true, true>(A, B, EpiPart{part, 2LL * H, H}, 2 * H, H, N,
+                                                               kWgradSplits, s, bpart)))
+      return e;
+    if ((e = reduce(2 * H, H, const_cast<float *>(g.w_e), hsh, 2LL * H, H, H, const_cast<float *>(g.b_e), (int)S)))
+      return e;
   }
-  // fused: every layer's data gradient in one IC-per-wave pass (chain_train_bwd_kernel)
-  if (fused && (e = launch_chain_train_bwd_fused(w, N / nx, nx, G, gstride, fused_tape(w, N, t).mbits, bpack,
-                                                 fold ? dPQ : nullptr, s, efold ? t.pq : nullptr, grad_flux,
-                                                 w.w_2, efpart, true)))
-    return e;
-  if (efold) {  // dw2, db2 from the per-IC partials; then dW_e, db_e from the dPQ the pass wrote
-    hipLaunchKernelGGL(edge_partial_reduce_kernel, dim3((unsigned)(H + 1)), dim3(256), 0, s, efpart,
-                       (int)(N / nx), H, const_cast<float *>(g.w_2), const_cast<float *>(g.b_2));
-    if ((e = readout_wgrad())) return e;
-  }
-  // the input layer's weight-gradient splits
-  const int64_t in_rows = (N + kInputSplits - 1) / kInputSplits;
-  const int in_nsp = (int)((N + in_rows - 1) / in_rows);
-  // on the stencil kernel's launch (its blocks after the layers')
-  const bool in_fold = wgs && HF_INPUT_IN_WGS && HF_INPUT_WGRAD4 && H == 128 && F == 4;
-  if (wgs) {  // dW_l, db_l of every update layer: one launch, then the layers' reductions
-    WgStencilBatch bt{};
-    bt.n = L;
-    bt.S = (int)SB;
-    for (int l = 0; l < L; ++l) {
-      bt.g[l] = G + (l + 1) * gstride;
-      bt.x[l] = t.h[l];
-      bt.part[l] = lpart + l * lpstride;
-      bt.bpart[l] = lbpart + l * lbstride;
-    }
-    if (in_fold) {  // + the input layer's weight-gradient partials (d = g[0])
-      bt.in_d = G;
+  const float *d0;  // g[0], the input layer's delta
+  if (fused) {
+    // g[L] = ReLU'(h[L]) * [W_a ; W_b]^T dPQ and every layer's data gradient below it, in one pass
+    const FusedTape f = fused_tape(w, N, t);  // (bpack: packed by the forward)
+    if ((e = launch_chain_train_bwd_fused(w, N / nx, nx, G, gstride, f.mbits, f.bpack, dPQ, s))) return e;
+    d0 = G;
+    if (wgs) {  // dW_l, db_l of every update layer: one launch
+      WgStencilBatch bt{};
+      bt.n = L;
+      bt.S = (int)SB;
+      for (int l = 0; l < L; ++l) {
+        bt.g[l] = G + (l + 1) * gstride;
+        bt.x[l] = t.h[l];
+        bt.part[l] = lpart + l * lpstride;
+        bt.bpart[l] = lbpart + l * lbstride;
+      }
+      // + the input layer's weight-gradient partials (in_fold)
+      const int64_t in_rows = (N + kInputSplits - 1) / kInputSplits;
+      bt.in_d = d0;
       bt.in_nf = nf;
       bt.in_part = ipart;
-      bt.in_bpart = ipart + (int64_t)kInputSplits * H * F;
+      bt.in_bpart = ipb;
       bt.in_rows = in_rows;
-      bt.in_blocks = in_nsp;
-    }
-    hipLaunchKernelGGL(wgrad_stencil_kernel, dim3((unsigned)(SB * L + bt.in_blocks)), dim3(256), 0, s, bt, N, nx,
-                       wgs_rsplit(N));
-    if (one_reduce)
+      bt.in_blocks = (int)((N + in_rows - 1) / in_rows);
+      hipLaunchKernelGGL(wgrad_stencil_kernel, dim3((unsigned)(SB * L + bt.in_blocks)), dim3(256), 0, s, bt, N, nx,
+                         wgs_rsplit(N));
       jobs.j[jobs.n++] = pr_job(lpart, (int)SB, H, 2 * H, const_cast<float *>(g.w_l), kNoSplit, 2LL * H, 0, lbpart, H,
                                 const_cast<float *>(g.b_l), (unsigned)L, lpstride, g.lsw, lbstride, g.lsb);
-    else if (!(HF_PR_BATCH && launch_part_reduce_batch(L, lpart, lpstride, (int)SB, H, 2 * H, const_cast<float *>(g.w_l),
-                                                  g.lsw, kNoSplit, 2LL * H, 0, lbpart, lbstride, H,
-                                                  const_cast<float *>(g.b_l), g.lsb, s)))
-      for (int l = L - 1; l >= 0; --l)
-        launch_part_reduce(lpart + l * lpstride, (int)SB, H, 2 * H, const_cast<float *>(g.w_l + l * g.lsw), kNoSplit,
-                           2LL * H, 0, lbpart + l * lbstride, H, const_cast<float *>(g.b_l + l * g.lsb), s);
-    if ((e = hipGetLastError())) return e;
-  } else if (wg_batch) {  // the same with tgemm_batch over the stencil view
-    TgBatch<VPlain, VStencil, EpiPart> bt{};
-    bt.n = L;
-    for (int l = 0; l < L; ++l) {
-      bt.a[l] = VPlain{G + (l + 1) * gstride, H, N, kNoSplit, 0, H};
-      bt.b[l] = VStencil{t.h[l], N, H, nx};
-      bt.e[l] = EpiPart{lpart + l * lpstride, H, 2LL * H};
-      bt.bias_part[l] = lbpart + l * lbstride;
+    } else if (wg_batch) {  // the same with tgemm_batch over the stencil view, then the layers' reductions in one launch
+      TgBatch<VPlain, VStencil, EpiPart> bt{};
+      bt.n = L;
+      for (int l = 0; l < L; ++l) {
+        bt.a[l] = VPlain{G + (l + 1) * gstride, H, N, kNoSplit, 0, H};
+        bt.b[l] = VStencil{t.h[l], N, H, nx};
+        bt.e[l] = EpiPart{lpart + l * lpstride, H, 2LL * H};
+        bt.bias_part[l] = lbpart + l * lbstride;
+      }
+      if ((e = tgemm_batch<VPlain, VStencil, EpiPart, true>(bt, H, 2 * H, N, kWgradBatchSplits, s))) return e;
+      launch_part_reduce_batch(L, lpart, lpstride, (int)SB, H, 2 * H, const_cast<float *>(g.w_l), g.lsw, kNoSplit,
+                               2LL * H, 0, lbpart, lbstride, H, const_cast<float *>(g.b_l), g.lsb, s);
     }
-    if ((e = tgemm_batch<VPlain, VStencil, EpiPart, true>(bt, H, 2 * H, N, kWgradBatchSplits, s))) return e;
-    if (!(HF_PR_BATCH && launch_part_reduce_batch(L, lpart, lpstride, (int)SB, H, 2 * H, const_cast<float *>(g.w_l),
-                                                  g.lsw, kNoSplit, 2LL * H, 0, lbpart, lbstride, H,
-                                                  const_cast<float *>(g.b_l), g.lsb, s)))
-      for (int l = L - 1; l >= 0; --l)
-        launch_part_reduce(lpart + l * lpstride, (int)SB, H, 2 * H, const_cast<float *>(g.w_l + l * g.lsw), kNoSplit,
-                           2LL * H, 0, lbpart + l * lbstride, H, const_cast<float *>(g.b_l + l * g.lsb), s);
     if ((e = hipGetLastError())) return e;
-  }
-  for (int l = L - 1; l >= 0 && !wg_batch; --l) {  // update layers, last to first                      (:53-60)
-    // dW_l[o][k] = sum_m delta[m][o] [h[l] ; agg h[l]][m][k], db_l = column sums of delta
+  } else {
+    // dh[L] = [W_a ; W_b]^T dPQ, masked by ReLU'(h[L])
+    int cur = 0;
     {
-      const VPlain A{fused ? G + (l + 1) * gstride : dl[cur], H, N, kNoSplit, 0, H};
-      const VStencil B{t.h[l], N, H, nx};
-      if ((e = tgemm<VPlain, true, VStencil, true, EpiPart, true, true>(A, B, EpiPart{part, H, 2LL * H}, H, 2 * H, N,
-                                                                  kWgradSplits, s, bpart)))
-        return e;
-      if ((e = reduce(H, 2 * H, const_cast<float *>(g.w_l + l * g.lsw), kNoSplit, 2LL * H, 0, H,
-                      const_cast<float *>(g.b_l + l * g.lsb), (int)S)))
-        return e;
+      const VPlain A{dPQ, 2LL * H, N, kNoSplit, 0, 2 * H};
+      const VPlain B{w.w_e, 2LL * H, 2LL * H, hsh, H, H};  // B(r = c, j = k) = [W_a ; W_b][c][k]
+      if ((e = tgemm<VPlain, false, VPlain, true>(A, B, EpiMask{dl[cur], H, t.h[L], H}, N, H, 2 * H, 1, s))) return e;
     }
-    // dh[l] = W_a^T delta + W_b^T agg(delta) (the aggregation's adjoint is itself on the
-    // chain), masked by ReLU'(h[l]): B(r, j) = W_l[r % H][(r / H) H + j]
-    if (!fused) {
+    for (int l = L - 1; l >= 0; --l) {  // update layers, last to first                      (:53-60)
+      // dW_l[o][k] = sum_m delta[m][o] [h[l] ; agg h[l]][m][k], db_l = column sums of delta
+      {
+        const VPlain A{dl[cur], H, N, kNoSplit, 0, H};
+        const VStencil B{t.h[l], N, H, nx};
+        if ((e = tgemm<VPlain, true, VStencil, true, EpiPart, true, true>(A, B, EpiPart{part, H, 2LL * H}, H, 2 * H, N,
+                                                                    kWgradSplits, s, bpart)))
+          return e;
+        if ((e = reduce(H, 2 * H, const_cast<float *>(g.w_l + l * g.lsw), kNoSplit, 2LL * H, 0, H,
+                        const_cast<float *>(g.b_l + l * g.lsb), (int)S)))
+          return e;
+      }
+      // dh[l] = W_a^T delta + W_b^T agg(delta) (the aggregation's adjoint is itself on the
+      // chain), masked by ReLU'(h[l]): B(r, j) = W_l[r % H][(r / H) H + j]
       const VStencil A{dl[cur], N, H, nx};
       const VPlain B{w.w_l + l * w.lsw, 2LL * H, 2LL * H, hsh, H, H};
       if ((e = tgemm<VStencil, false, VPlain, true>(A, B, EpiMask{dl[cur ^ 1], H, t.h[l], H}, N, H, 2 * H, 1, s)))
         return e;
       cur ^= 1;
     }
+    d0 = dl[cur];
   }
   // input MLP                                                                        (:49)
-  const float *d0 = fused ? G : dl[cur];
-  const int64_t rows = in_rows;
-  const int nsp = in_nsp;
-  float *ipb = ipart + (int64_t)kInputSplits * H * F;
+  const int64_t rows = (N + kInputSplits - 1) / kInputSplits;  // the input layer's weight-gradient splits
+  const int nsp = (int)((N + rows - 1) / rows);
 #define HF_IN_WG(FF) \
   hipLaunchKernelGGL(input_wgrad_kernel<FF>, dim3((unsigned)nsp), dim3(256), 0, s, d0, nf, H, N, rows, ipart, ipb)
   if (in_fold) {
     // (on the stencil kernel's launch above)
-  } else if (HF_INPUT_WGRAD4 && H == 128 && F == 4) {
+  } else if (H == 128 && F == 4) {
     hipLaunchKernelGGL(input_wgrad_h128f4_kernel, dim3((unsigned)nsp), dim3(256), 0, s, d0, nf, N, rows, ipart, ipb);
   } else {
     HF_INPUT_DISPATCH(F, HF_IN_WG)
@@ -1508,10 +1260,7 @@ hipError_t launch_ablation_loss(const float *fe, const float *st, const float *f
   float *nn = reinterpret_cast<float *>(p);
   float *En = reinterpret_cast<float *>(p + al256(sizeof(float) * (size_t)B * nx));
   float *part = reinterpret_cast<float *>(p + 2 * al256(sizeof(float) * (size_t)B * nx));
-#ifndef HF_LOSS_FUSED
-#define HF_LOSS_FUSED 1
-#endif
-  if (HF_LOSS_FUSED && !poisson_uses_fft(nx) && nx <= kLossFusedMaxNx) {
+  if (!poisson_uses_fft(nx) && nx <= kLossFusedMaxNx) {
     hipLaunchKernelGGL(loss_step_kernel, dim3((unsigned)B), dim3(256), (size_t)nx * (sizeof(double) + 2 * sizeof(float)),
                        s, fe, st, ft, sn, pc, B, nx, c, lam[0], dt, r, part, dfe);
   } else {

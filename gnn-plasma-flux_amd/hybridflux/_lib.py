@@ -149,9 +149,9 @@ def build_flags(v=None):
 
 
 def diagnostic_build(v=None):
-    """True when the library was built with an HF_DIAG_* timing diagnostic or an
-    HF_EXP_* experiment switch (or any other extra flag): its results are not
-    the shipped kernels' and no headline may be printed from it."""
+    """True when the library was built with an HF_DIAG_* timing diagnostic (or
+    any other extra flag): its results are not the shipped kernels' and no
+    headline may be printed from it."""
     return build_flags(v) != ""
 
 

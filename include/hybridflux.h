@@ -140,6 +140,9 @@ int hf_graph_flux(hf_model_t model, const float *dev_node_features, int64_t N,
  * hf_graph_backward writes dL/dparams (overwriting, same layout as
  * dev_params, hf_model_param_count floats) and, when dev_grad_node_features
  * is not NULL, dL/dnode_features [N][in_dim].  dev_grad_flux is dL/dflux [E].
+ * dev_params must be unchanged since the hf_graph_forward_train that wrote
+ * the tape: the tape holds weights packed by that forward, so the optimizer
+ * step comes after hf_graph_backward.
  * Weight gradients are split-K sums reduced in a fixed order: bitwise
  * deterministic for a given N, E.  chain_nx > 0 declares that edge_index is
  * N/chain_nx disjoint periodic chains of chain_nx cells in build_chain_graph

@@ -53,7 +53,7 @@ def test_build_hash_covers_extra_flags(tmp_path):
     the Makefile would run, with the hash and the flags it would embed)."""
     import subprocess
     csrc = _lib.CSRC
-    for extra in ("", "-DHF_DIAG_NOFV", "-DHF_EXP_PREFETCH -DHF_DIAG_NOSYNC"):
+    for extra in ("", "-DHF_DIAG_NOFV", "-DHF_DIAG_NOFEAT -DHF_DIAG_NOSYNC"):
         p = subprocess.run(["make", "-n", "-B", "-C", csrc, f"BUILD={tmp_path}", f"OUT={tmp_path}/x.so",
                             f"CXXFLAGS_EXTRA={extra}", f"{tmp_path}/capi.cpp.o"],
                            capture_output=True, text=True, check=True)
@@ -68,17 +68,16 @@ def test_build_hash_covers_extra_flags(tmp_path):
 
 
 def test_no_switch_defined_in_source():
-    """The HF_DIAG_* / HF_EXP_* switches are set only from the command line
+    """The HF_DIAG_* timing switches are set only from the command line
     (CXXFLAGS_EXTRA, covered by the hash and the version string); a source that
-    #defines one would ship a diagnostic kernel under a clean version.  The one
-    exception is HF_EXP_VFIRST's default of 0 (off)."""
+    #defines one (or an HF_EXP_* experiment switch, none of which remain) would
+    ship a diagnostic kernel under a clean version."""
     for f in os.listdir(_lib.CSRC):
         if not f.endswith((".hip", ".h", ".cpp")):
             continue
         for ln in open(os.path.join(_lib.CSRC, f)):
             m = re.match(r"\s*#\s*define\s+(HF_(?:DIAG|EXP)_\w+)(.*)", ln)
-            if m:
-                assert m.group(1) == "HF_EXP_VFIRST" and m.group(2).strip() == "0", f"{f}: {ln.strip()}"
+            assert not m, f"{f}: {ln.strip()}"
 
 
 def test_param_count_matches_reference_model():
