@@ -74,15 +74,7 @@ __global__ void add_delta_kernel(const float *__restrict__ state, const float *_
   if (out2) out2[b * ld2 + r] = v;
 }
 
-struct PureW {
-  const float *w_in, *b_in;  // [H][in], [H]
-  const float *w_l, *b_l;    // layer l at + l*(2H*H + H): [H][2H], [H]
-  const float *w_o1, *b_o1;  // [H][H], [H]
-  const float *w_o2, *b_o2;  // [3][H], [3]
-  int in_dim, H, L;
-  int64_t ls;
-  const float *w_lp, *w_o1p;  // the one-launch rollout's packed copies: [l][u][P|Q][kb][lane][4], [u][kb][lane][4]
-};
+}  // namespace
 
 PureW pure_view(const float *p, int in_dim, int H, int L) {
   PureW w{};
@@ -102,6 +94,8 @@ PureW pure_view(const float *p, int in_dim, int H, int L) {
   w.b_o2 = p + o;
   return w;
 }
+
+namespace {
 
 struct PureWs {
   float *h0, *h1, *P, *Q, *nf, *delta;
@@ -131,9 +125,13 @@ PureWs carve_pure(void *ws, int H, int64_t N) {
 // layer is ONE f32 MFMA GEMM h [N][H] x [W_a ; W_b]^T whose block epilogue
 // forms the messages and the residual (EpiMsg), and output_mlp.0 is a GEMM
 // with a tanh epilogue.  Otherwise: the generic linear + gather kernels.
+}  // namespace
+
 bool pure_chain_ok(int H, int chain_nx, int64_t N) {
   return chain_nx > 0 && 128 % chain_nx == 0 && H % 64 == 0 && H <= 1024 && N * H < (int64_t(1) << 31);
 }
+
+namespace {
 
 // PureGNN.forward (train_pure_gnn.py:57-76) over buckets already built.
 hipError_t pure_forward(const PureW &w, const float *nf, int64_t N, const int64_t *src, const int *off,

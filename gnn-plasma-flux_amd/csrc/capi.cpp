@@ -551,6 +551,64 @@ int hf_pure_gnn_run(const float *params, int hidden, int layers, const float *st
   return HF_OK;
 }
 
+// PureGNN training: the argument checks shared by the two passes
+static int pure_train_args(const char *fn, int in_dim, int hidden, int layers, int64_t N, int64_t E, int chain_nx) {
+  if (!train_dims_ok(in_dim, hidden, layers))
+    return fail(HF_EINVAL, std::string(fn) + ": bad model dimensions (layers <= 8)");
+  if (N < 1 || E < 0) return fail(HF_EINVAL, std::string(fn) + ": need N >= 1 and E >= 0");
+  if (N > 0x7fffffffLL || E > 0x7fffffffLL) return fail(HF_EUNSUPPORTED, std::string(fn) + ": > 2^31 nodes/edges");
+  return chain_args(fn, chain_nx, N, E);
+}
+
+int64_t hf_pure_gnn_tape_bytes(int in_dim, int hidden, int layers, int64_t N, int64_t E) {
+  if (!train_dims_ok(in_dim, hidden, layers) || N < 1 || E < 0) return -1;
+  return hf::pure_tape_bytes(hidden, layers, N, E);
+}
+
+int64_t hf_pure_gnn_backward_workspace_bytes(int in_dim, int hidden, int layers, int64_t N, int64_t E) {
+  if (!train_dims_ok(in_dim, hidden, layers) || N < 1 || E < 0) return -1;
+  return hf::pure_backward_ws_bytes(in_dim, hidden, layers, N, E);
+}
+
+int hf_pure_gnn_forward_train(const float *params, int in_dim, int hidden, int layers, const float *nf, int64_t N,
+                              const int64_t *ei, int64_t E, int chain_nx, float *delta, void *tape, void *stream) {
+  if (int rc = pure_train_args("hf_pure_gnn_forward_train", in_dim, hidden, layers, N, E, chain_nx)) return rc;
+  if (!params || !nf || !delta || !tape || (E > 0 && !ei))
+    return fail(HF_EINVAL, "hf_pure_gnn_forward_train: NULL pointer");
+  HF_CHECK_HIP(hf::launch_pure_forward_train(params, in_dim, hidden, layers, nf, N, ei, E, chain_nx, delta, tape,
+                                             as_stream(stream)),
+               "hf_pure_gnn_forward_train");
+  return HF_OK;
+}
+
+int hf_pure_gnn_backward(const float *params, int in_dim, int hidden, int layers, const float *nf, int64_t N,
+                         const int64_t *ei, int64_t E, int chain_nx, const void *tape, const float *grad_delta,
+                         float *grad_params, float *grad_nf, void *ws, void *stream) {
+  if (int rc = pure_train_args("hf_pure_gnn_backward", in_dim, hidden, layers, N, E, chain_nx)) return rc;
+  if (!params || !nf || !tape || !grad_delta || !grad_params || !ws || (E > 0 && !ei))
+    return fail(HF_EINVAL, "hf_pure_gnn_backward: NULL pointer");
+  HF_CHECK_HIP(hf::launch_pure_backward(params, in_dim, hidden, layers, nf, N, ei, E, chain_nx, tape, grad_delta,
+                                        grad_params, grad_nf, ws, as_stream(stream)),
+               "hf_pure_gnn_backward");
+  return HF_OK;
+}
+
+int64_t hf_state_mse_workspace_bytes(int B, int nx) {
+  if (B < 1 || nx < 1 || 3LL * B * nx > 0x7fffffffLL) return -1;
+  return hf::state_mse_ws_bytes(B, nx);
+}
+
+int hf_state_mse(const float *delta, const float *st, const float *sn, int B, int nx, float *loss, float *grad_delta,
+                 void *ws, int64_t ws_bytes, void *stream) {
+  if (B < 1 || nx < 1 || 3LL * B * nx > 0x7fffffffLL)
+    return fail(HF_EINVAL, "hf_state_mse: need B >= 1, nx >= 1 and 3 B nx < 2^31");
+  if (!delta || !st || !sn || !loss || !grad_delta || !ws) return fail(HF_EINVAL, "hf_state_mse: NULL pointer");
+  if (ws_bytes < hf::state_mse_ws_bytes(B, nx))
+    return fail(HF_EINVAL, "hf_state_mse: workspace smaller than hf_state_mse_workspace_bytes");
+  HF_CHECK_HIP(hf::launch_state_mse(delta, st, sn, B, nx, loss, grad_delta, ws, as_stream(stream)), "hf_state_mse");
+  return HF_OK;
+}
+
 int64_t hf_pinn_param_count(int dim, int hidden, int layers) {
   if (dim < 1 || hidden < 1 || layers < 2 || layers > hf::kMaxChainLayers) return -1;
   const int64_t D = dim, H = hidden;

@@ -203,8 +203,9 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const float *__restrict__ D,
     }
 }
 
-// gw[o][k] = sum_s part[s][o][k] (k < K), gb[o] = sum_s part[s][o][K], in a fixed order.
-__global__ void wgrad_reduce_kernel(const float *__restrict__ part, int S, int O, int K, float *gw, float *gb) {
+// gw[o][k] = sum_s part[s][o][k] (k < K; rows of gw ldw floats apart), gb[o] = sum_s part[s][o][K], in a fixed order.
+__global__ void wgrad_reduce_kernel(const float *__restrict__ part, int S, int O, int K, float *gw, int64_t ldw,
+                                    float *gb) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int KB = K + 1;
   if (t >= (int64_t)O * KB) return;
@@ -220,7 +221,7 @@ __global__ void wgrad_reduce_kernel(const float *__restrict__ part, int S, int O
   }
   for (; s < S; ++s) v0 = __fadd_rn(v0, part[(int64_t)s * st + t]);
   const float v = __fadd_rn(__fadd_rn(v0, v1), __fadd_rn(v2, v3));
-  if (k < K) gw[(int64_t)o * K + k] = v;
+  if (k < K) gw[(int64_t)o * ldw + k] = v;
   else if (gb) gb[o] = v;
 }
 
@@ -374,9 +375,10 @@ inline int64_t split_rows(int64_t M) {  // >= 256 rows per split, <= 128 splits,
   return (R + kKC - 1) / kKC * kKC;
 }
 
-// gw[O][K1+K2] = D^T X, gb[O] = column sums of D (gb may be NULL).
+// gw[O][K1+K2] = D^T X, gb[O] = column sums of D (gb may be NULL).  ldw > 0:
+// gw is a column block of a wider matrix, its rows ldw floats apart (M > 0).
 hipError_t wgrad(const float *D, int O, const float *A1, int K1, const int64_t *i1, const float *A2, int K2,
-                 const int64_t *i2, int64_t M, float *gw, float *gb, float *part, hipStream_t s) {
+                 const int64_t *i2, int64_t M, float *gw, float *gb, float *part, hipStream_t s, int64_t ldw = 0) {
   const int K = K1 + K2;
   if (M <= 0) {
     hipError_t e = hipMemsetAsync(gw, 0, sizeof(float) * O * K, s);
@@ -389,7 +391,7 @@ hipError_t wgrad(const float *D, int O, const float *A1, int K1, const int64_t *
   hipLaunchKernelGGL(wgrad_kernel, grid, dim3(256), 0, s, D, O, OpIn{A1, A2, i1, i2, K1, K2, M}, R, part);
   const int64_t n = (int64_t)O * (K + 1);
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, S, O, K, gw,
-                     gb);
+                     ldw > 0 ? ldw : K, gb);
   return hipGetLastError();
 }
 
@@ -500,6 +502,17 @@ hipError_t gemm_linear(const float *A1, int K1, const int64_t *i1, const float *
   return linear(A1, K1, i1, A2, K2, i2, W, b, out, M, O, act, s, nullptr, resid);
 }
 
+hipError_t gemm_wgrad(const float *D, int O, const float *X, int K, int64_t M, float *gw, int64_t ldw, float *gb,
+                      float *part, hipStream_t s) {
+  if (M <= 0) return hipErrorInvalidValue;
+  return wgrad(D, O, X, K, nullptr, nullptr, 0, nullptr, M, gw, gb, part, s, ldw);
+}
+
+int64_t gemm_wgrad_part_floats(int64_t M, int O, int K) {
+  const int64_t R = split_rows(M > 0 ? M : 1);
+  return ((M + R - 1) / R) * O * (K + 1);
+}
+
 hipError_t edge_buckets(const int64_t *key, int64_t E, int64_t N, int chain_nx, bool by_col, void *ws,
                         int **off, int **perm, hipStream_t s) {
   Carve c{static_cast<char *>(ws)};
@@ -507,6 +520,14 @@ hipError_t edge_buckets(const int64_t *key, int64_t E, int64_t N, int chain_nx, 
   *off = o;
   *perm = p;
   return build_csr(key, E, N, deg, o, cur, p, s, chain_nx, by_col);
+}
+
+void edge_buckets_view(void *ws, int64_t N, int64_t E, int **off, int **perm) {
+  Carve c{static_cast<char *>(ws)};
+  c.take<int>(N);
+  *off = c.take<int>(N + 1);
+  c.take<int>(N);
+  *perm = c.take<int>(E);
 }
 
 int64_t edge_buckets_bytes(int64_t N, int64_t E) {

@@ -93,12 +93,33 @@ enum { kActNone = 0, kActRelu = 1, kActTanh = 2 };
 hipError_t gemm_linear(const float *A1, int K1, const int64_t *i1, const float *A2, int K2, const int64_t *i2,
                        WView W, const float *b, float *out, int64_t M, int O, int act, const float *resid,
                        hipStream_t s);
+// gw[o][k] = sum_m D[m][o] X[m][k] ([O][K], rows ldw floats apart: ldw > K writes a column
+// block of a wider matrix), gb[o] = column sums of D (or NULL); M > 0.  Split-K over the
+// rows with the splits summed in a fixed order; part: gemm_wgrad_part_floats(M, O, K) floats.
+hipError_t gemm_wgrad(const float *D, int O, const float *X, int K, int64_t M, float *gw, int64_t ldw, float *gb,
+                      float *part, hipStream_t s);
+int64_t gemm_wgrad_part_floats(int64_t M, int O, int K);
 // Edges bucketed by key (row or col), ascending edge id per bucket; chain_nx > 0: arithmetic buckets.
 int64_t edge_buckets_bytes(int64_t N, int64_t E);
 hipError_t edge_buckets(const int64_t *key, int64_t E, int64_t N, int chain_nx, bool by_col, void *ws, int **off,
                         int **perm, hipStream_t s);
+// off / perm of buckets that edge_buckets built in ws earlier
+void edge_buckets_view(void *ws, int64_t N, int64_t E, int **off, int **perm);
 
 // PureGNN / PINN inference (baselines.hip).
+// View of PureGNN's flat float32 parameters in state-dict order.
+struct PureW {
+  const float *w_in, *b_in;  // [H][in], [H]
+  const float *w_l, *b_l;    // layer l at + l*(2H*H + H): [H][2H], [H]
+  const float *w_o1, *b_o1;  // [H][H], [H]
+  const float *w_o2, *b_o2;  // [3][H], [3]
+  int in_dim, H, L;
+  int64_t ls;
+  const float *w_lp, *w_o1p;  // the one-launch rollout's packed copies: [l][u][P|Q][kb][lane][4], [u][kb][lane][4]
+};
+PureW pure_view(const float *p, int in_dim, int H, int L);
+// shapes of the chain form of PureGNN's layers (tgemm.h EpiMsg): nx | 128, H % 64 == 0
+bool pure_chain_ok(int H, int chain_nx, int64_t N);
 int64_t pure_gnn_ws_bytes(int H, int64_t N, int64_t E);
 hipError_t launch_pure_gnn_forward(const float *params, int in_dim, int H, int L, const float *nf, int64_t N,
                                    const int64_t *ei, int64_t E, int chain_nx, float *delta, void *ws, hipStream_t s);
@@ -114,6 +135,20 @@ hipError_t launch_pinn_forward(const float *params, int D, int H, int L, const f
                                void *ws, hipStream_t s);
 hipError_t launch_pinn_run(const float *params, int D, int H, int L, const float *state0, float *final_state,
                            int64_t B, int T, float *traj, void *ws, hipStream_t s);
+
+// PureGNN training (pure_train.hip): the forward that keeps a tape, the
+// backward, and the fused state-MSE loss with its gradient.  layers <= kMaxChainLayers.
+int64_t pure_tape_bytes(int H, int L, int64_t N, int64_t E);
+int64_t pure_backward_ws_bytes(int in_dim, int H, int L, int64_t N, int64_t E);
+hipError_t launch_pure_forward_train(const float *params, int in_dim, int H, int L, const float *nf, int64_t N,
+                                     const int64_t *ei, int64_t E, int chain_nx, float *delta, void *tape,
+                                     hipStream_t s);
+hipError_t launch_pure_backward(const float *params, int in_dim, int H, int L, const float *nf, int64_t N,
+                                const int64_t *ei, int64_t E, int chain_nx, const void *tape, const float *grad_delta,
+                                float *grad_params, float *grad_nf, void *ws, hipStream_t s);
+int64_t state_mse_ws_bytes(int B, int nx);
+hipError_t launch_state_mse(const float *delta, const float *st, const float *sn, int B, int nx, float *loss,
+                            float *grad_delta, void *ws, hipStream_t s);
 
 // View of a flat float32 parameter buffer in state-dict order (the host_params
 // order of hf_model_create): update layers interleave weight and bias.

@@ -55,6 +55,15 @@ SIGNATURES = {
                                     c_void_p, c_void_p, c_void_p]),
     "hf_pure_gnn_run": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                 c_void_p, c_void_p]),
+    "hf_pure_gnn_tape_bytes": (c_int64, [c_int, c_int, c_int, c_int64, c_int64]),
+    "hf_pure_gnn_backward_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int64, c_int64]),
+    "hf_pure_gnn_forward_train": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int,
+                                          c_void_p, c_void_p, c_void_p]),
+    "hf_pure_gnn_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "hf_state_mse_workspace_bytes": (c_int64, [c_int, c_int]),
+    "hf_state_mse": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64,
+                             c_void_p]),
     "hf_pinn_param_count": (c_int64, [c_int, c_int, c_int]),
     "hf_pinn_workspace_bytes": (c_int64, [c_int, c_int, c_int64]),
     "hf_pinn_forward": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),

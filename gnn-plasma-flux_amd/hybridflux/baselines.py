@@ -9,15 +9,25 @@ scripts/evaluation/evaluate_multi_ic.py:45-83 and benchmark_timing.py:100-203
 over B initial conditions in one call.  forward() takes the reference's host
 (CPU) tensors too (evaluate_multi_ic.py:53-83 calls them with
 torch.FloatTensor states): they are staged to the current HIP device and the
-result is copied back.  Inference only: these modules have no backward
-kernels (the reference trains them with its own torch loops), so a forward
-under autograd raises.
+result is copied back.
+
+PureGNN is trainable on the engine: under autograd (grad enabled and a
+parameter or the node features requiring grad) forward() runs the training
+kernels of pure_train.hip instead (hf_pure_gnn_forward_train keeps a tape on
+the device, backward() runs hf_pure_gnn_backward), so the reference's
+`batch_loss.backward()` (train_pure_gnn.py:144) and its smoke test's call with
+grad enabled (examples/smoke_test.py:98-104) work unchanged; gradients land on
+each tensor's own device, and after flatten_parameters_() the kernels read the
+parameters in place (hybridflux.training.train_pure_gnn, FlatAdam).  Under
+torch.no_grad() the inference kernels run as before.  PINN stays inference
+only: it has no backward kernels, so its forward under autograd raises.
 """
 import torch
 import torch.nn as nn
 
 from . import engine
 from ._lib import check, lib, ptr
+from .flux_gnn import _flat_view
 
 
 def _flat(module):
@@ -44,6 +54,41 @@ class _Flat:
         return self.buf
 
 
+class _PureTrainForward(torch.autograd.Function):
+    """PureGNN.forward with HIP backward kernels (parameter order = state dict);
+    the counterpart of flux_gnn._TrainForward."""
+
+    @staticmethod
+    def forward(ctx, node_features, edge_index, dims, *params):
+        dev = engine.compute_device(node_features, "node_features")
+        flat = _flat_view(params, dev)
+        if flat is None:
+            flat = torch.cat([q.detach().reshape(-1).to(device=dev, dtype=torch.float32) for q in params])
+        delta, tape, nf, ei, chain_nx = engine.pure_gnn_forward_train(flat, dims, node_features.detach().to(dev),
+                                                                      edge_index)
+        ctx.save_for_backward(flat, tape, nf, ei)
+        ctx.dims = dims
+        ctx.chain_nx = chain_nx
+        ctx.shapes = [q.shape for q in params]
+        ctx.param_devices = [q.device for q in params]
+        ctx.nf_dtype, ctx.nf_device = node_features.dtype, node_features.device
+        return delta.to(node_features.device)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_delta):
+        flat, tape, nf, ei = ctx.saved_tensors
+        gp, gnf = engine.pure_gnn_backward(flat, ctx.dims, nf, ei, ctx.chain_nx, tape, grad_delta,
+                                           ctx.needs_input_grad[0])
+        grads, o = [], 0
+        for shp in ctx.shapes:
+            n = shp.numel()
+            grads.append(gp[o:o + n].view(shp).to(ctx.param_devices[len(grads)]))
+            o += n
+        gnf = gnf.to(device=ctx.nf_device, dtype=ctx.nf_dtype) if gnf is not None else None
+        return (gnf, None, None, *grads)
+
+
 class PureGNN(nn.Module):
     """End-to-end GNN predicting the state change per node (train_pure_gnn.py:35-76)."""
 
@@ -58,7 +103,10 @@ class PureGNN(nn.Module):
 
     def forward(self, node_features, edge_index):
         """node_features [N, input_dim], edge_index [2, E] -> delta_state [N, 3]."""
-        _no_grad_guard(self, node_features)
+        params = list(self.parameters())
+        if torch.is_grad_enabled() and (node_features.requires_grad or any(q.requires_grad for q in params)):
+            dims = (self.input_dim, self.hidden_dim, self.num_layers)
+            return _PureTrainForward.apply(node_features, edge_index, dims, *params)
         home = node_features.device
         dev = engine.compute_device(node_features, "node_features")
         nf, ei, N, E, chain_nx = engine._graph_inputs(node_features.to(dev), edge_index, self.input_dim)
@@ -70,6 +118,21 @@ class PureGNN(nn.Module):
                                             self.num_layers, ptr(nf), N, ptr(ei), E, chain_nx, ptr(delta), ptr(ws),
                                             engine.stream_of(nf.device)))
         return delta.to(home)
+
+    def flatten_parameters_(self):
+        """Re-home every parameter into one contiguous float32 buffer in
+        state-dict order (FluxGNN.flatten_parameters_'s contract: the parameters
+        keep their identity, FlatAdam can drive them, and the training forward
+        hands the kernels that buffer instead of concatenating the parameters
+        each step).  .to() / .cuda() afterwards undo it."""
+        params = list(self.parameters())
+        flat = torch.cat([q.detach().reshape(-1).to(torch.float32) for q in params])
+        o = 0
+        with torch.no_grad():
+            for q in params:
+                q.data = flat[o:o + q.numel()].view(q.shape)
+                o += q.numel()
+        return self
 
     def rollout(self, states0, n_steps, x, traj=True):
         """B ICs [B,3,nx] (device) -> dict(final [B,3,nx], traj [B,T+1,3,nx] or None);

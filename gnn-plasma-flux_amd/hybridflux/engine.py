@@ -362,6 +362,64 @@ def graph_backward(params, dims, nf, ei, chain_nx, tape, grad_flux, want_nf_grad
     return gp, gnf
 
 
+def pure_gnn_forward_train(params, dims, node_features, edge_index):
+    """PureGNN's training forward (hf_pure_gnn_forward_train): params is the flat
+    float32 device buffer in state-dict order.  Returns (delta [N,3], tape, nf,
+    ei, chain_nx); edge_index is range-checked (_graph_inputs)."""
+    in_dim, hidden, layers = dims
+    nf, ei, N, E, chain_nx = _graph_inputs(node_features, edge_index, in_dim)
+    if params.device != nf.device:
+        raise RuntimeError(f"PureGNN parameters on {params.device} but node_features on {nf.device}")
+    delta = torch.empty(N, 3, device=nf.device)
+    nb = int(lib().hf_pure_gnn_tape_bytes(in_dim, hidden, layers, N, E))
+    if nb < 0:
+        raise ValueError(f"PureGNN training needs N >= 1 and at most 8 layers (N = {N}, layers = {layers})")
+    tape = torch.empty(nb, dtype=torch.uint8, device=nf.device)
+    with torch.cuda.device(nf.device):
+        check(lib().hf_pure_gnn_forward_train(ptr(params), in_dim, hidden, layers, ptr(nf), N, ptr(ei), E, chain_nx,
+                                              ptr(delta), ptr(tape), stream_of(nf.device)))
+    return delta, tape, nf, ei, chain_nx
+
+
+def pure_gnn_backward(params, dims, nf, ei, chain_nx, tape, grad_delta, want_nf_grad):
+    """hf_pure_gnn_backward: (d params flat [P], d node_features [N,in] or None)."""
+    in_dim, hidden, layers = dims
+    N, E = nf.shape[0], ei.shape[1]
+    g = grad_delta.detach().to(device=nf.device, dtype=torch.float32).contiguous()
+    gp = torch.empty_like(params)
+    gnf = torch.empty_like(nf) if want_nf_grad else None
+    ws = torch.empty(int(lib().hf_pure_gnn_backward_workspace_bytes(in_dim, hidden, layers, N, E)),
+                     dtype=torch.uint8, device=nf.device)
+    with torch.cuda.device(nf.device):
+        check(lib().hf_pure_gnn_backward(ptr(params), in_dim, hidden, layers, ptr(nf), N, ptr(ei), E, chain_nx,
+                                         ptr(tape), ptr(g), ptr(gp), ptr(gnf) if gnf is not None else None, ptr(ws),
+                                         stream_of(nf.device)))
+    return gp, gnf
+
+
+def state_mse(delta, state_t, state_next):
+    """hf_state_mse: (loss [1], d loss / d delta [B*nx,3]) of the PureGNN
+    trainer's loss for delta [B*nx,3] and states [B,3,nx] on the device."""
+    require_device(delta, "delta")
+    d = delta.detach().to(torch.float32).contiguous()
+    st = state_t.detach().to(device=d.device, dtype=torch.float32).contiguous()
+    sn = state_next.detach().to(device=d.device, dtype=torch.float32).contiguous()
+    if st.dim() != 3 or st.shape[1] != 3 or sn.shape != st.shape or tuple(d.shape) != (st.shape[0] * st.shape[2], 3):
+        raise ValueError(f"state_mse: delta [B*nx,3] with states [B,3,nx], got {tuple(d.shape)}, "
+                         f"{tuple(st.shape)}, {tuple(sn.shape)}")
+    B, _, nx = st.shape
+    nb = int(lib().hf_state_mse_workspace_bytes(B, nx))
+    if nb < 0:
+        raise ValueError(f"state_mse: need B >= 1, nx >= 1 (B = {B}, nx = {nx})")
+    loss = torch.empty(1, device=d.device)
+    gd = torch.empty_like(d)
+    ws = torch.empty(nb, dtype=torch.uint8, device=d.device)
+    with torch.cuda.device(d.device):
+        check(lib().hf_state_mse(ptr(d), ptr(st), ptr(sn), B, nx, ptr(loss), ptr(gd), ptr(ws), nb,
+                                 stream_of(d.device)))
+    return loss, gd
+
+
 def poisson(grid, n):
     """Poisson E for densities n [B,nx]: the grid's mode (spectral: src/baseline_solver.py:59-68)."""
     require_device(n, "n")

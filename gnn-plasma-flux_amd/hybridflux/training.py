@@ -18,6 +18,11 @@ As in the reference, the Poisson / energy terms go through a detached
 Poisson solve (there numpy, :138-145; here hf_poisson), so they contribute to
 the loss value but not to the gradient; the multi-step rollout energies depend
 only on u, which the model does not touch (:174-196).
+
+PureGNN (scripts/training/train_pure_gnn.py:79-151) trains here too, at the
+end of this module: state_mse_loss (hf_state_mse), pure_gnn_step and
+train_pure_gnn, over PureGNN's own autograd Function (baselines.py,
+pure_train.hip).
 """
 import json
 import os
@@ -466,4 +471,104 @@ def train_model(state_t, flux_t, state_next, x, dt, dx, nu, config_name, stencil
         torch.save({k: v.clone() for k, v in model.state_dict().items()}, os.path.join(save_dir, f"hybrid_{config_name}_r{stencil_radius}.pt"))
         with open(os.path.join(save_dir, f"history_{config_name}_r{stencil_radius}.json"), "w") as f:
             json.dump(history, f, indent=2)
+    return model, history
+
+
+# ----------------------------------------------------------------- PureGNN
+class _StateMSE(torch.autograd.Function):
+    """The PureGNN trainer's loss and its gradient as one HIP pass (hf_state_mse)."""
+
+    @staticmethod
+    def forward(ctx, delta, state_t, state_next):
+        loss, gd = engine.state_mse(delta, state_t, state_next)
+        ctx.save_for_backward(gd)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        (gd,) = ctx.saved_tensors
+        return gd * g, None, None
+
+
+def state_mse_loss(delta, state_t, state_next):
+    """mean((state_t^T + delta - state_next^T)^2) for delta [B*nx,3] and states
+    [B,3,nx]: the reference's batch loss (train_pure_gnn.py:134-141, the mean
+    over samples of per-sample means, every sample having 3 nx values),
+    differentiable in delta."""
+    return _StateMSE.apply(delta, state_t, state_next)
+
+
+def pure_gnn_features(state_t, x):
+    """[B,3,nx] states and x [nx] -> node features [B*nx,4] = [n, u, E, x]
+    (train_pure_gnn.py:125-128, batched)."""
+    B, _, nx = state_t.shape
+    return torch.cat([state_t.permute(0, 2, 1).reshape(B * nx, 3), x.repeat(B).unsqueeze(1)], dim=1)
+
+
+def pure_gnn_step(model, opt, state_t, state_next, x):
+    """One optimizer step of the reference's loop (train_pure_gnn.py:112-145) on
+    a batch [B,3,nx]: ONE forward and backward over the batch's B disjoint
+    chains (a tagged chain_edge_index) instead of B per-sample graph calls, the
+    fused loss, opt.step().  Returns the detached loss (no host sync)."""
+    from .graph_constructor import chain_edge_index
+    B, _, nx = state_t.shape
+    delta = model(pure_gnn_features(state_t, x), chain_edge_index(nx, B, state_t.device))
+    loss = state_mse_loss(delta, state_t, state_next)
+    opt.zero_grad()
+    loss.backward()
+    opt.step()
+    return loss.detach()
+
+
+def pure_gnn_train_flop_per_sample(nx=64, H=128, L=4, F=4):
+    """Algorithmic FLOPs of one sample of the PureGNN training step (P/Q-split
+    messages, as train_flop_per_sample counts FluxGNN's): forward GEMMs once
+    (input 2FH, layers L*2*H*2H, output_mlp 2HH + 2*3H per cell), backward data
+    gradients once (the same layer and output_mlp sizes; none into the node
+    features) and weight gradients once (the same, plus the input layer's
+    2FH).  tanh, the message sums and the loss are not counted."""
+    gemm = L * 2 * H * 2 * H + 2 * H * H + 2 * 3 * H
+    return (2 * F * H + gemm + gemm + gemm + 2 * F * H) * nx
+
+
+def train_pure_gnn(state_t, state_next, x, epochs=50, lr=1e-3, batch_size=32, hidden_dim=None, num_layers=None,
+                   device="cuda", order=None, seed=None, log=None):
+    """scripts/training/train_pure_gnn.py:79-151 on the MI355X: PureGNN(4,
+    hidden_dim, num_layers) (default MODEL_CONFIG's, :94-98), Adam(lr), batches
+    of batch_size samples in a shuffled order (the last one may be partial),
+    the epoch's history entry the mean of its batch losses (:147-150).  Each
+    batch is one batched step (pure_gnn_step).  order: per epoch an explicit
+    sample order (a sequence of `epochs` index sequences) instead of the
+    shuffle.  Returns (model, {'loss': [...]})."""
+    from .baselines import PureGNN
+    engine.require_device(torch.empty(0, device=device), "device")
+    if seed is not None:
+        torch.manual_seed(seed)
+    st_all = torch.as_tensor(np.asarray(state_t, dtype=np.float32), device=device)
+    sn_all = torch.as_tensor(np.asarray(state_next, dtype=np.float32), device=device)
+    if st_all.dim() != 3 or st_all.shape[1] != 3 or sn_all.shape != st_all.shape or st_all.shape[0] < 1:
+        raise ValueError(f"state_t / state_next must be [N,3,nx] with N >= 1, got {tuple(st_all.shape)}, "
+                         f"{tuple(sn_all.shape)}")
+    n = st_all.shape[0]
+    x_dev = torch.as_tensor(np.asarray(x, dtype=np.float32), device=device)
+    model = PureGNN(MODEL_CONFIG["input_dim"], hidden_dim or MODEL_CONFIG["hidden_dim"],
+                    MODEL_CONFIG["num_layers"] if num_layers is None else num_layers).to(device)
+    model.flatten_parameters_()
+    opt = FlatAdam(model.parameters(), lr=lr)
+    gen = torch.Generator().manual_seed(0 if seed is None else seed)
+    history = {"loss": []}
+    model.train()
+    for epoch in range(epochs):
+        perm = torch.randperm(n, generator=gen) if order is None else torch.as_tensor(order[epoch], dtype=torch.int64)
+        if perm.numel() and (int(perm.min()) < -n or int(perm.max()) >= n):
+            raise IndexError(f"sample index out of range for a dataset of {n} samples")
+        perm = perm.to(device)
+        total, nb = torch.zeros((), device=device), 0
+        for k in range(0, perm.numel(), batch_size):
+            idx = perm[k:k + batch_size]
+            total += pure_gnn_step(model, opt, st_all[idx], sn_all[idx], x_dev)
+            nb += 1
+        history["loss"].append(float(total) / max(nb, 1))
+        if log:
+            log(f"Epoch {epoch + 1}/{epochs}, Loss: {history['loss'][-1]:.6f}")
     return model, history

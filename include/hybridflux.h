@@ -141,8 +141,10 @@ int hf_graph_flux(hf_model_t model, const float *dev_node_features, int64_t N,
  * dev_params, hf_model_param_count floats) and, when dev_grad_node_features
  * is not NULL, dL/dnode_features [N][in_dim].  dev_grad_flux is dL/dflux [E].
  * dev_params must be unchanged since the hf_graph_forward_train that wrote
- * the tape: the tape holds weights packed by that forward, so the optimizer
- * step comes after hf_graph_backward.
+ * the tape: the tape holds weights packed by that forward (and the backward
+ * multiplies by dev_params as the forward read them), so the optimizer step
+ * comes after hf_graph_backward; with parameters changed in between, the
+ * gradients are silently wrong.
  * Weight gradients are split-K sums reduced in a fixed order: bitwise
  * deterministic for a given N, E.  chain_nx > 0 declares that edge_index is
  * N/chain_nx disjoint periodic chains of chain_nx cells in build_chain_graph
@@ -280,6 +282,56 @@ int hf_pure_gnn_forward(const float *dev_params, int in_dim, int hidden, int lay
 int hf_pure_gnn_run(const float *dev_params, int hidden, int layers, const float *dev_state0,
                     float *dev_final, const float *dev_x, int B, int nx, int T, float *dev_traj,
                     void *dev_workspace, void *stream);
+
+/*
+ * PureGNN training (scripts/training/train_pure_gnn.py:59-76 under
+ * batch_loss.backward(), :100-151), mirroring hf_graph_forward_train /
+ * hf_graph_backward.  dev_params and dev_grad_params are flat float32 device
+ * buffers of hf_pure_gnn_param_count values in state-dict order (above);
+ * layers <= 8, N >= 1.  chain_nx as for hf_graph_forward_train: tagged chains
+ * with chain_nx dividing 128 and hidden a multiple of 64 run on the f32 MFMA
+ * GEMMs of csrc/tgemm.h, every other graph, width or chain length on the
+ * generic kernels (dev_edge_index must lie in [0, N): it is not checked here).
+ *
+ * hf_pure_gnn_forward_train writes dev_delta [N][3], bit-identical to
+ * hf_pure_gnn_forward, and a tape (hf_pure_gnn_tape_bytes: h_0..h_L, the
+ * output_mlp's hidden layer and every message) that hf_pure_gnn_backward
+ * consumes.  hf_pure_gnn_backward reads dev_grad_delta = dL/ddelta [N][3] and
+ * writes dL/dparams (overwriting) and, when dev_grad_node_features is not
+ * NULL, dL/dnode_features [N][in_dim]; workspace
+ * hf_pure_gnn_backward_workspace_bytes.  dev_params must be unchanged between
+ * the forward that wrote the tape and the backward (the backward multiplies
+ * by the weights the forward used), so the optimizer step comes after it.
+ * Every sum runs in a fixed order (the messages of a node in ascending edge
+ * order, split-K weight gradients reduced in split order, no atomics): two
+ * calls on the same inputs give the same bits.
+ *
+ * hf_state_mse: the trainer's loss (:134-141) for a batch in one pass.
+ * dev_delta [B*nx][3], dev_state_t / dev_state_next [B][3][nx]; writes
+ * dev_loss[0] = mean((state_t^T + delta - state_next^T)^2) over all 3 B nx
+ * values (= the mean over samples of the per-sample means) and dev_grad_delta
+ * [B*nx][3] = 2 (pred - target) / (3 B nx), by a two-stage reduction in a
+ * fixed order.  dev_workspace: hf_state_mse_workspace_bytes(B, nx).
+ *
+ * Bad arguments (NULL buffers, chain_nx not dividing N or E != 2N with
+ * chain_nx > 0, layers > 8, non-positive sizes, a workspace_bytes too small)
+ * return HF_EINVAL before any device call; the size queries return -1.
+ */
+int64_t hf_pure_gnn_tape_bytes(int in_dim, int hidden, int layers, int64_t N, int64_t E);
+int64_t hf_pure_gnn_backward_workspace_bytes(int in_dim, int hidden, int layers, int64_t N, int64_t E);
+int hf_pure_gnn_forward_train(const float *dev_params, int in_dim, int hidden, int layers,
+                              const float *dev_node_features, int64_t N, const int64_t *dev_edge_index,
+                              int64_t E, int chain_nx, float *dev_delta, void *dev_tape, void *stream);
+int hf_pure_gnn_backward(const float *dev_params, int in_dim, int hidden, int layers,
+                         const float *dev_node_features, int64_t N, const int64_t *dev_edge_index,
+                         int64_t E, int chain_nx, const void *dev_tape, const float *dev_grad_delta,
+                         float *dev_grad_params, float *dev_grad_node_features /* or NULL */,
+                         void *dev_workspace, void *stream);
+int64_t hf_state_mse_workspace_bytes(int B, int nx);
+int hf_state_mse(const float *dev_delta, const float *dev_state_t, const float *dev_state_next,
+                 int B, int nx, float *dev_loss, float *dev_grad_delta, void *dev_workspace,
+                 int64_t workspace_bytes, void *stream);
+
 int64_t hf_pinn_param_count(int dim, int hidden, int layers);
 int64_t hf_pinn_workspace_bytes(int dim, int hidden, int64_t B);
 int hf_pinn_forward(const float *dev_params, int dim, int hidden, int layers, const float *dev_state,
