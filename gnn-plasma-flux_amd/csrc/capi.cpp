@@ -505,6 +505,52 @@ int hf_adam_flat(float *params, const float *grads, float *exp_avg, float *exp_a
   return HF_OK;
 }
 
+// ------------------------------------------------------- unrolled training
+int64_t hf_unroll_workspace_bytes(int B, int nx) {
+  if (B < 1 || nx < 1) return -1;
+  return hf::unroll_ws_bytes(B, nx);
+}
+
+// the shape and Poisson-mode checks shared by hf_unroll_update / hf_unroll_adjoint (after the pointer checks)
+static int unroll_mode_args(const char *fn, int pm, int nx) {
+  if (pm != HF_POISSON_SPECTRAL && pm != HF_POISSON_TRIDIAG)
+    return fail(HF_EINVAL, std::string(fn) + ": unknown Poisson mode");
+  if (pm == HF_POISSON_TRIDIAG)
+    return fail(HF_EUNSUPPORTED, std::string(fn) + ": the tridiagonal Poisson mode has no adjoint here (spectral only)");
+  if (!hf::unroll_nx_ok(nx))
+    return fail(HF_EUNSUPPORTED, std::string(fn) + ": nx > 6144 (the tiled global-memory regime) is not supported");
+  return HF_OK;
+}
+
+int hf_unroll_update(const float *fe, const float *st, const float *x, const double *pc, int pm, int B, int nx, float c,
+                     float dt, float *st_next, float *nf_next, const float *target, const float *weights, float scale,
+                     float *loss, void *ws, int64_t ws_bytes, void *stream) {
+  if (B < 1 || nx < 1) return fail(HF_EINVAL, "hf_unroll_update: need B >= 1, nx >= 1");
+  if (!fe || !st || !x || !pc || !st_next || !ws) return fail(HF_EINVAL, "hf_unroll_update: NULL pointer");
+  if (target && (!weights || !loss))
+    return fail(HF_EINVAL, "hf_unroll_update: NULL weights or loss with a target");
+  if (st == st_next) return fail(HF_EINVAL, "hf_unroll_update: state and state_next must not alias");
+  if (ws_bytes < hf::unroll_ws_bytes(B, nx))
+    return fail(HF_EINVAL, "hf_unroll_update: workspace smaller than hf_unroll_workspace_bytes");
+  if (int rc = unroll_mode_args("hf_unroll_update", pm, nx)) return rc;
+  HF_CHECK_HIP(hf::launch_unroll_update(fe, st, x, pc, B, nx, c, dt, st_next, nf_next, target, weights, scale, loss, ws,
+                                        as_stream(stream)),
+               "hf_unroll_update");
+  return HF_OK;
+}
+
+int hf_unroll_adjoint(const float *st, const float *st_next, const float *target, const float *weights, float scale,
+                      const float *direct_next, const float *gnf_next, const double *pc, int pm, int B, int nx, float c,
+                      float dt, float *g_fe, float *direct, void *stream) {
+  if (B < 1 || nx < 1) return fail(HF_EINVAL, "hf_unroll_adjoint: need B >= 1, nx >= 1");
+  if (!st || !st_next || !target || !weights || !pc || !g_fe) return fail(HF_EINVAL, "hf_unroll_adjoint: NULL pointer");
+  if (int rc = unroll_mode_args("hf_unroll_adjoint", pm, nx)) return rc;
+  HF_CHECK_HIP(hf::launch_unroll_adjoint(st, st_next, target, weights, scale, direct_next, gnf_next, pc, B, nx, c, dt,
+                                         g_fe, direct, as_stream(stream)),
+               "hf_unroll_adjoint");
+  return HF_OK;
+}
+
 // ------------------------------------------------------- PureGNN / PINN
 int64_t hf_pure_gnn_param_count(int in_dim, int hidden, int layers) {
   if (in_dim < 1 || hidden < 1 || layers < 0) return -1;

@@ -115,7 +115,7 @@ __global__ __launch_bounds__(kFvThreads) void fv_step_kernel(
 // ones into a1, with rho and the window of c a tile needs staged in LDS, so
 // E is the LDS kernels' value bit for bit; the metrics come from
 // state_metrics_kernel, which sums in fv_step_kernel's order.
-constexpr int kFvLdsMaxNx = 6144;  // fv_lds_bytes(6144) = 144 KiB of dynamic LDS
+// (kFvLdsMaxNx = 6144, hf_internal.h: fv_lds_bytes(6144) = 144 KiB of dynamic LDS)
 constexpr int kPoissonTileJ = 1024;
 
 template <bool HYBRID>
@@ -202,31 +202,7 @@ __global__ __launch_bounds__(kFvThreads) void poisson_tri_kernel(const float *__
 // poisson_wave<N> turns into N (E_a + i E_b) in the same registers.
 // HBM: 12 B read + 12 B write per cell (+4 B F).  The transforms use a
 // wave-private padded LDS buffer.
-constexpr int kDppWaveShl1 = 0x130;  // lane l <- lane l+1 (lane 63: no source)
-constexpr int kDppWaveRol1 = 0x134;  // lane l <- lane l+1 (lane 63 <- lane 0)
-constexpr int kDppWaveShr1 = 0x138;  // lane l <- lane l-1 (lane 0: no source)
-constexpr int kDppWaveRor1 = 0x13C;  // lane l <- lane l-1 (lane 0 <- lane 63)
-// src moved by CTRL; lanes without a source keep `old`
-template <int CTRL>
-__device__ __forceinline__ float wave_dpp(float old, float src) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(src), CTRL, 0xF, 0xF, false));
-}
-// value at cell i-1 (left) or i+1 (right) for every register of a lane's
-// cells: a wave shift, and for the lane that shifts out of the wave (lane 0
-// left, lane 63 right) the rotated neighbour register (periodic wrap included)
-template <int V>
-__device__ __forceinline__ void left_of(const float (&x)[V], float (&l)[V]) {
-#pragma unroll
-  for (int i = 0; i < V; ++i)
-    l[i] = wave_dpp<kDppWaveShr1>(wave_dpp<kDppWaveRor1>(0.f, x[(i + V - 1) % V]), x[i]);
-}
-template <int V>
-__device__ __forceinline__ void right_of(const float (&x)[V], float (&rt)[V]) {
-#pragma unroll
-  for (int i = 0; i < V; ++i) rt[i] = wave_dpp<kDppWaveShl1>(wave_dpp<kDppWaveRol1>(0.f, x[(i + 1) % V]), x[i]);
-}
-
-constexpr int kFftWaves = 4;
+// (the wave rotations wave_dpp / left_of / right_of and kFftWaves: hf_device.h)
 
 // One IC's step inputs, cells lane + 64v: n, u, E and the face flux F
 // (hybrid: the GNN's; classical: n*u, src/baseline_solver.py:70-71).

@@ -385,6 +385,36 @@ __device__ __forceinline__ void poisson_wave(double2 (&v)[N / 64], double2 *lds,
   poisson_wave_tw<N>(v, lds, reinterpret_cast<const double2 *>(plan + N), plan + 2 * N, lane);
 }
 
+// ------------------------------------------------- wave-per-IC-pair kernels
+// The FFT-size kernels (fv_poisson.hip, unroll.hip) give a wave the cells
+// lane + 64v of a chain; a cell's chain neighbours come from the adjacent lane
+// by a wave rotation (DPP).
+constexpr int kDppWaveShl1 = 0x130;  // lane l <- lane l+1 (lane 63: no source)
+constexpr int kDppWaveRol1 = 0x134;  // lane l <- lane l+1 (lane 63 <- lane 0)
+constexpr int kDppWaveShr1 = 0x138;  // lane l <- lane l-1 (lane 0: no source)
+constexpr int kDppWaveRor1 = 0x13C;  // lane l <- lane l-1 (lane 0 <- lane 63)
+// src moved by CTRL; lanes without a source keep `old`
+template <int CTRL>
+__device__ __forceinline__ float wave_dpp(float old, float src) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(src), CTRL, 0xF, 0xF, false));
+}
+// value at cell i-1 (left) or i+1 (right) for every register of a lane's
+// cells: a wave shift, and for the lane that shifts out of the wave (lane 0
+// left, lane 63 right) the rotated neighbour register (periodic wrap included)
+template <int V>
+__device__ __forceinline__ void left_of(const float (&x)[V], float (&l)[V]) {
+#pragma unroll
+  for (int i = 0; i < V; ++i)
+    l[i] = wave_dpp<kDppWaveShr1>(wave_dpp<kDppWaveRor1>(0.f, x[(i + V - 1) % V]), x[i]);
+}
+template <int V>
+__device__ __forceinline__ void right_of(const float (&x)[V], float (&rt)[V]) {
+#pragma unroll
+  for (int i = 0; i < V; ++i) rt[i] = wave_dpp<kDppWaveShl1>(wave_dpp<kDppWaveRol1>(0.f, x[(i + 1) % V]), x[i]);
+}
+
+constexpr int kFftWaves = 4;  // waves (IC pairs) per workgroup of those kernels
+
 // Per-state rollout metrics, partial sums for one cell.
 // The finite flag is not tested per value: every value a lane adds is finite
 // exactly when its double sums are (a finite float term is bounded, |n| <

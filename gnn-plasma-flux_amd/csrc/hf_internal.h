@@ -226,6 +226,31 @@ hipError_t launch_fv_step(const float *in, int64_t ld_in, float *out, int64_t ld
                           float dt, float nu, float dx2, float *flux_out, int64_t ld_flux,
                           float *metrics, int64_t ld_metrics, int pm, hipStream_t s);
 
+// Largest nx whose chain and circulant column fit the one-workgroup-per-IC LDS
+// plan of fv_poisson.hip (144 KiB of dynamic LDS); beyond it the update and the
+// Poisson sum run tiled over global memory.
+constexpr int kFvLdsMaxNx = 6144;
+
+// Unrolled training (unroll.hip): one hybrid step from the FluxGNN's edge flux
+// fe [B][2nx] with the step's extras, and its adjoint; spectral Poisson,
+// nx <= kFvLdsMaxNx (unroll_nx_ok).  Contiguous [B][3][nx] states.
+//  update:  st_next = launch_fv_step(face_flux = 0.5 (fe[i] + fe[nx + i])) bit
+//           for bit; nf_next [B*nx][4] = [n', u', E', x] (or NULL); with target
+//           [B][3][nx]: loss[0] = scale * sum w_ch (st_next - target)^2, summed
+//           in a fixed order through ws (unroll_ws_bytes; w: 3 host floats).
+//  adjoint: g = direct_next + gnf_next[:, 0:3]^T (each or NULL) + 2 w scale
+//           (st_next - target) is dL/d st_next; writes g_fe [B][2nx] = dL/d fe
+//           and direct [B][3][nx] (or NULL) = the part of dL/d st that does not
+//           pass through the FluxGNN.
+bool unroll_nx_ok(int nx);
+int64_t unroll_ws_bytes(int B, int nx);
+hipError_t launch_unroll_update(const float *fe, const float *st, const float *x, const double *pc, int B, int nx,
+                                float c, float dt, float *st_next, float *nf_next, const float *target, const float *w,
+                                float scale, float *loss, void *ws, hipStream_t s);
+hipError_t launch_unroll_adjoint(const float *st, const float *st_next, const float *target, const float *w, float scale,
+                                 const float *direct_next, const float *gnf_next, const double *pc, int B, int nx,
+                                 float c, float dt, float *g_fe, float *direct, hipStream_t s);
+
 // The whole classical rollout (T steps of launch_fv_step's classical update)
 // in one launch, states held in registers: FFT nx up to 1024 (fv_run_fused).
 // state0 [B] x IC stride ld_s0 floats, state_final [B][3][nx] (may alias

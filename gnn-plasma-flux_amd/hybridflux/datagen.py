@@ -41,3 +41,15 @@ def generate_dataset(nx=64, num_initial_conditions=20, steps_per_ic=30, dt=5e-3,
             os.makedirs(d, exist_ok=True)
         np.savez(out_path, state_t=state_t, flux_t=flux_t, state_next=state_next, x=x, dt=dt, dx=solver.dx, nu=nu)
     return state_t, flux_t, state_next, x, dt, solver.dx, nu
+
+
+def generate_trajectories(nx=64, num_initial_conditions=20, steps_per_ic=30, dt=5e-3, t_end=1.0, nu=1e-3,
+                          device="cuda", seeds=None):
+    """The classical trajectories themselves, [N, steps+1, 3, nx] float32 (numpy):
+    the array generate_dataset computes and flattens into (state_t, state_next)
+    pairs, kept whole for multi-step windows (training.WindowDataset).  Same
+    ICs, same batched rollout; x, dx are BaselineSolver(nx=nx).x / .dx."""
+    solver = BaselineSolver(nx=nx, dt=dt, t_end=t_end, nu=nu, device=device)
+    seeds = list(range(num_initial_conditions)) if seeds is None else list(seeds)
+    ics = solver.initial_conditions(seeds, as_tensor=True)
+    return solver.run_batch(ics, steps_per_ic, traj=True)["traj"].cpu().numpy()

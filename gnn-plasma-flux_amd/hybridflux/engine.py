@@ -538,6 +538,100 @@ def adam_flat(params, grads, exp_avg, exp_avg_sq, step, done, lr, beta1, beta2, 
                                  float(lr), float(beta1), float(beta2), float(eps), stream_of(dev)))
 
 
+def unroll_workspace(B, nx, dev):
+    """hf_unroll_workspace_bytes of scratch for unroll_update on `dev` (a uint8 tensor)."""
+    nb = int(lib().hf_unroll_workspace_bytes(B, nx))
+    if nb < 0:
+        raise ValueError(f"unroll workspace: need B >= 1, nx >= 1 (B = {B}, nx = {nx})")
+    return torch.empty(nb, dtype=torch.uint8, device=dev)
+
+
+def _unroll_state(t, B, nx, dev, what):
+    require_device(t, what)
+    if t.dtype != torch.float32 or tuple(t.shape) != (B, 3, nx) or t.device != dev or not t.is_contiguous():
+        raise ValueError(f"{what} must be contiguous float32 [{B},3,{nx}] on {dev}, got {tuple(t.shape)} {t.dtype}")
+    return t
+
+
+def _weights3(weights):
+    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1))
+    if w.size != 3:
+        raise ValueError("channel weights must be (w_n, w_u, w_E)")
+    return w
+
+
+def unroll_update(grid, flux_edge, state, x=None, target=None, weights=(1.0, 1.0, 1.0), scale=0.0, want_nf=True,
+                  out=None, loss=None, ws=None):
+    """hf_unroll_update: one hybrid step of `state` [B,3,nx] from FluxGNN's edge
+    fluxes flux_edge [B*2nx] (src/hybrid_solver.py:45-63).  Returns (state_next
+    [B,3,nx], node_features_next [B*nx,4] or None, loss [1] or None): the next
+    step's FluxGNN input, and with `target` [B,3,nx] the term scale * sum w_ch
+    (state_next - target)^2.  x: the positions [nx] of the node features
+    (default the grid's).  out / loss / ws: preallocated state_next, loss
+    element and workspace (unroll_workspace)."""
+    require_device(state, "state")
+    B, _, nx = state.shape
+    dev = state.device
+    st = _unroll_state(state, B, nx, dev, "state")
+    fe = flux_edge.detach()
+    if fe.dtype != torch.float32 or fe.numel() != B * 2 * nx or fe.device != dev or not fe.is_contiguous() \
+            or nx != grid.nx:
+        raise ValueError(f"unroll update: flux_edge must be contiguous float32 [{B}*2*{nx}] on {dev}, nx the grid's")
+    xg, _ = grid.on(dev)
+    x = xg if x is None else x
+    if x.dtype != torch.float32 or x.numel() != nx or x.device != dev or not x.is_contiguous():
+        raise ValueError(f"unroll update: x must be contiguous float32 [{nx}] on {dev}")
+    pc = grid.spectral_plan(dev)
+    out = torch.empty_like(st) if out is None else _unroll_state(out, B, nx, dev, "out")
+    nf = torch.empty(B * nx, 4, device=dev) if want_nf else None
+    w = None
+    if target is not None:
+        target = _unroll_state(target, B, nx, dev, "target")
+        w = _weights3(weights)
+        loss = torch.empty(1, device=dev) if loss is None else loss
+        if loss.dtype != torch.float32 or loss.numel() != 1 or loss.device != dev:
+            raise ValueError("unroll update: loss must be one float32 element on the state's device")
+    else:
+        loss = None
+    ws = unroll_workspace(B, nx, dev) if ws is None else ws
+    with torch.cuda.device(dev):
+        check(lib().hf_unroll_update(ptr(fe), ptr(st), ptr(x), ptr(pc), grid.pmode, B, nx, grid.c32, grid.dt32, ptr(out),
+                                     ptr(nf), ptr(target), ptr(w), float(scale), ptr(loss), ptr(ws),
+                                     ws.numel() * ws.element_size(), stream_of(dev)))
+    return out, nf, loss
+
+
+def unroll_adjoint(grid, state, state_next, target, weights, scale, direct_next=None, gnf_next=None, want_direct=True):
+    """hf_unroll_adjoint: the adjoint of unroll_update's step.  state (s_k),
+    state_next (the predicted s_{k+1}) and target (s*_{k+1}) [B,3,nx];
+    direct_next [B,3,nx] / gnf_next [B*nx,4]: the direct part this call returned
+    for step k+1 and FluxGNN's d node_features of step k+1 (None at the last
+    step, or to cut the state gradient).  Returns (d loss / d flux_edge [B,2nx],
+    direct part [B,3,nx] or None)."""
+    require_device(state, "state")
+    B, _, nx = state.shape
+    dev = state.device
+    st = _unroll_state(state, B, nx, dev, "state")
+    sn = _unroll_state(state_next, B, nx, dev, "state_next")
+    tg = _unroll_state(target, B, nx, dev, "target")
+    if nx != grid.nx:
+        raise ValueError("unroll adjoint: nx must be the grid's")
+    if direct_next is not None:
+        direct_next = _unroll_state(direct_next, B, nx, dev, "direct_next")
+    if gnf_next is not None and (gnf_next.dtype != torch.float32 or tuple(gnf_next.shape) != (B * nx, 4)
+                                 or gnf_next.device != dev or not gnf_next.is_contiguous()):
+        raise ValueError(f"unroll adjoint: gnf_next must be contiguous float32 [{B * nx},4] on {dev}")
+    w = _weights3(weights)
+    pc = grid.spectral_plan(dev)
+    g_fe = torch.empty(B, 2 * nx, device=dev)
+    direct = torch.empty(B, 3, nx, device=dev) if want_direct else None
+    with torch.cuda.device(dev):
+        check(lib().hf_unroll_adjoint(ptr(st), ptr(sn), ptr(tg), ptr(w), float(scale), ptr(direct_next), ptr(gnf_next),
+                                      ptr(pc), grid.pmode, B, nx, grid.c32, grid.dt32, ptr(g_fe), ptr(direct),
+                                      stream_of(dev)))
+    return g_fe, direct
+
+
 def ablation_loss_terms(grid, flux_edge, st, ft, sn, lam, rollout_steps=0, dt=None):
     """hf_ablation_loss_ex: the reference trainer's loss (scripts/training/
     train_ablation.py:120-206) for B samples.  flux_edge [B, 2nx], st / sn

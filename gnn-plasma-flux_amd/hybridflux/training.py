@@ -34,7 +34,7 @@ import torch
 from . import engine
 from .baseline_solver import BaselineSolver
 from .config import ABLATION_CONFIGS, MODEL_CONFIG
-from .flux_gnn import FluxGNN
+from .flux_gnn import FluxGNN, _flat_view
 from .graph_constructor import build_chain_graph_batch, shared_chain_edge_index
 
 
@@ -571,4 +571,244 @@ def train_pure_gnn(state_t, state_next, x, epochs=50, lr=1e-3, batch_size=32, hi
         history["loss"].append(float(total) / max(nb, 1))
         if log:
             log(f"Epoch {epoch + 1}/{epochs}, Loss: {history['loss'][-1]:.6f}")
+    return model, history
+
+
+# -------------------------------------------------------- unrolled training
+# FluxGNN differentiated through K hybrid solver steps (include/hybridflux.h,
+# hf_unroll_update / hf_unroll_adjoint): the loss sees the solver's feedback
+# loop n -> E -> u -> node features that the evaluation rollouts run, which
+# the one-step ablation loss above never does.
+def _unrolled_forward(flat, dims, traj, x, grid, weights):
+    """The K taped forwards and updates.  Returns (loss [] , rec): rec holds
+    what the backward needs and the predicted states `pred` [K,B,3,nx]."""
+    B, K1, _, nx = traj.shape
+    K = K1 - 1
+    dev = traj.device
+    tr = traj.detach().to(torch.float32).transpose(0, 1).contiguous()  # [K+1,B,3,nx]: a step's rows contiguous
+    ei = shared_chain_edge_index(nx, B, dev)
+    scale = 1.0 / (K * 3 * B * nx)
+    pred = torch.empty(K, B, 3, nx, device=dev)
+    terms = torch.empty(K, device=dev)
+    ws = engine.unroll_workspace(B, nx, dev)
+    st = tr[0]
+    nf, _ = build_chain_graph_batch(st, x)
+    tapes, nfs, chain_nx = [], [], 0
+    for k in range(K):
+        flux, tape, nf_d, ei_d, chain_nx = engine.graph_forward_train(flat, dims, nf, ei)
+        _, nf, _ = engine.unroll_update(grid, flux, st, x, tr[k + 1], weights, scale, want_nf=k + 1 < K, out=pred[k],
+                                        loss=terms[k:k + 1], ws=ws)
+        tapes.append(tape)
+        nfs.append(nf_d)
+        st = pred[k]
+    rec = dict(tr=tr, pred=pred, tapes=tapes, nfs=nfs, ei=ei_d, chain_nx=chain_nx, scale=scale, K=K)
+    return terms.sum(), rec
+
+
+def _unrolled_backward(flat, dims, rec, grid, weights, through_state):
+    """The K adjoint / FluxGNN-backward pairs, last step first; the parameter
+    gradients of the steps are added in that order (K-1, K-2, ..., 0).
+    Returns d loss / d params as one flat buffer."""
+    tr, pred, K = rec["tr"], rec["pred"], rec["K"]
+    total, direct, gnf = None, None, None
+    for k in range(K - 1, -1, -1):
+        keep = through_state and k > 0  # step k's state gradient feeds step k-1
+        g_fe, direct = engine.unroll_adjoint(grid, tr[0] if k == 0 else pred[k - 1], pred[k], tr[k + 1], weights,
+                                             rec["scale"], direct, gnf, want_direct=keep)
+        gp, gnf = engine.graph_backward(flat, dims, rec["nfs"][k], rec["ei"], rec["chain_nx"], rec["tapes"][k],
+                                        g_fe.reshape(-1), keep)
+        total = gp if total is None else total.add_(gp)
+    return total
+
+
+def _unrolled_check(traj, x, grid):
+    engine.require_device(traj, "traj")
+    if traj.dim() != 4 or traj.shape[1] < 2 or traj.shape[2] != 3 or traj.shape[3] != grid.nx or traj.shape[0] < 1:
+        raise ValueError(f"traj must be [B,K+1,3,{grid.nx}] with B >= 1, K >= 1, got {tuple(traj.shape)}")
+    x = torch.as_tensor(x, dtype=torch.float32, device=traj.device).reshape(-1).contiguous()
+    if x.numel() != grid.nx:
+        raise ValueError("x must hold nx positions")
+    return x
+
+
+class _UnrolledLoss(torch.autograd.Function):
+    """unrolled_loss as one Function: forward = K taped FluxGNN forwards and
+    hybrid updates, backward = K adjoint / FluxGNN-backward pairs."""
+
+    @staticmethod
+    def forward(ctx, traj, x, grid, weights, through_state, dims, *params):
+        dev = traj.device
+        flat = _flat_view(params, dev)
+        if flat is None:
+            flat = torch.cat([q.detach().reshape(-1).to(device=dev, dtype=torch.float32) for q in params])
+        loss, rec = _unrolled_forward(flat, dims, traj, x, grid, weights)
+        ctx.rec, ctx.flat, ctx.grid, ctx.weights, ctx.through, ctx.dims = rec, flat, grid, weights, through_state, dims
+        ctx.shapes = [q.shape for q in params]
+        ctx.mark_non_differentiable(rec["pred"])
+        return loss, rec["pred"]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss, g_pred):
+        gp = _unrolled_backward(ctx.flat, ctx.dims, ctx.rec, ctx.grid, ctx.weights, ctx.through)
+        ctx.rec = None  # the tapes are consumed
+        gp = gp.mul_(g_loss)  # (exact for autograd's seed 1)
+        grads, o = [], 0
+        for shp in ctx.shapes:
+            n = int(np.prod(shp)) if len(shp) else 1
+            grads.append(gp[o:o + n].view(shp))
+            o += n
+        return (None, None, None, None, None, None, *grads)
+
+
+def unrolled_loss(model, traj, x, grid, channel_weights=(1.0, 1.0, 1.0), through_state=True, return_states=False):
+    """L = (1/K) sum_{k=1..K} mean_{b,ch,i} w_ch (s^_k - s*_k)^2 of the hybrid
+    solver (src/hybrid_solver.py:45-63) unrolled K steps from traj[:, 0], against
+    the targets traj[:, 1:] (classical solver states): traj [B,K+1,3,nx] on the
+    device, x [nx], grid the engine.Grid of the step (spectral Poisson, nx <=
+    6144).  A scalar with autograd into the model's parameters, through every
+    step's FluxGNN call and, with through_state, through the state the steps hand
+    on (continuity, velocity, the Poisson solve and the next node features).
+    through_state=False cuts the state gradient between steps (the pushforward
+    form): each step's loss reaches only its own FluxGNN call.  Per unrolled step
+    the forward is hf_graph_forward_train + one hf_unroll_update launch, the
+    backward one hf_unroll_adjoint launch + hf_graph_backward.  return_states:
+    also the predicted states [K,B,3,nx] (no gradient)."""
+    if type(model) is not FluxGNN:
+        raise TypeError("unrolled_loss trains FluxGNN")
+    x = _unrolled_check(traj, x, grid)
+    dims = (model.input_dim, model.hidden_dim, model.num_layers)
+    w = tuple(float(v) for v in channel_weights)
+    loss, pred = _UnrolledLoss.apply(traj, x, grid, w, bool(through_state), dims, *model.parameters())
+    return (loss, pred) if return_states else loss
+
+
+def unrolled_step(model, opt, traj, x, grid, channel_weights=(1.0, 1.0, 1.0), through_state=True):
+    """unrolled_loss -> backward -> opt.step() without autograd, after
+    direct_step: FluxGNN with flat parameters (flatten_parameters_), FlatAdam
+    over exactly those parameters, grad enabled.  The same forwards, adjoints,
+    backwards and gradient sum as the autograd step, in the same order, so the
+    same parameters bit for bit, without autograd's seed, product and
+    bookkeeping launches.  Returns the detached loss, or None when the case does
+    not apply (the caller then takes the autograd step)."""
+    if type(model) is not FluxGNN or not isinstance(opt, FlatAdam) or not torch.is_grad_enabled():
+        return None
+    params = list(model.parameters())
+    if len(opt.param_groups) != 1 or [id(q) for q in opt.param_groups[0]["params"]] != [id(q) for q in params] \
+            or not all(q.requires_grad for q in params):
+        return None
+    flat = _flat_view(params, traj.device)
+    if flat is None:
+        return None
+    x = _unrolled_check(traj, x, grid)
+    dims = (model.input_dim, model.hidden_dim, model.num_layers)
+    w = tuple(float(v) for v in channel_weights)
+    loss, rec = _unrolled_forward(flat, dims, traj, x, grid, w)
+    gp = _unrolled_backward(flat, dims, rec, grid, w, bool(through_state))
+    o = 0
+    for q in params:
+        q.grad = gp[o:o + q.numel()].view_as(q)
+        o += q.numel()
+    opt.step()
+    return loss.detach()
+
+
+def unrolled_train_flop_per_sample(K=4, nx=64, H=128, L=4, F=4):
+    """Algorithmic FLOPs of one sample (one K-step window) of the unrolled
+    training step, after train_flop_per_sample: K FluxGNN forwards and K
+    backwards (data + weight gradients), plus the input layer's data gradient
+    2FH per cell for the K - 1 steps whose node features carry a gradient back
+    to the previous step.  The hybrid updates, their adjoints and the Poisson
+    solves (elementwise and float64 work outside the MFMA GEMMs) are not counted."""
+    fwd = 2 * F * H + L * 2 * 2 * H * H + 2 * H * 2 * H + 2 * 2 * H
+    bwd = (L * 2 * 2 * H * H + 2 * 2 * H * H) * 2 + 2 * F * H
+    return (K * (fwd + bwd) + (K - 1) * 2 * F * H) * nx
+
+
+class WindowDataset:
+    """Device-resident K-step windows of classical trajectories [N,T+1,3,nx]:
+    sample ic * (T - K + 1) + t0 is trajectories[ic, t0 : t0 + K + 1], for every
+    (ic, t0) with t0 + K <= T."""
+
+    def __init__(self, trajectories, K, device="cuda"):
+        self.traj = torch.as_tensor(np.asarray(trajectories, dtype=np.float32), device=device) \
+            if not isinstance(trajectories, torch.Tensor) else trajectories.to(device=device, dtype=torch.float32)
+        if self.traj.dim() != 4 or self.traj.shape[2] != 3:
+            raise ValueError(f"trajectories must be [N,T+1,3,nx], got {tuple(self.traj.shape)}")
+        self.N, T1, _, self.nx = self.traj.shape
+        self.K, self.T = int(K), T1 - 1
+        if self.K < 1 or self.K > self.T:
+            raise ValueError(f"need 1 <= K <= T (K = {K}, T = {self.T})")
+        self.per_ic = self.T - self.K + 1
+        self._steps = torch.arange(self.K + 1, device=self.traj.device)
+
+    def __len__(self):
+        return self.N * self.per_ic
+
+    def batch(self, idx):
+        """Windows [B,K+1,3,nx] of the sample indices idx (each in [0, len))."""
+        idx = torch.as_tensor(idx, device=self.traj.device).to(torch.long).reshape(-1)
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= len(self)):
+            raise IndexError(f"sample index out of range for a dataset of {len(self)} windows")
+        ic = torch.div(idx, self.per_ic, rounding_mode="floor")
+        t0 = idx - ic * self.per_ic
+        return self.traj[ic[:, None], t0[:, None] + self._steps[None, :]]
+
+
+def train_unrolled(trajectories, x, dt, dx, nu, K=4, epochs=10, lr=1e-3, batch_size=32, seed=None, init=None,
+                   channel_weights=(1.0, 1.0, 1.0), through_state=True, device="cuda", save_dir="checkpoints",
+                   log=print):
+    """Train (or fine-tune) FluxGNN on K-step windows of classical trajectories
+    [N,T+1,3,nx] (datagen.generate_trajectories) with the unrolled loss: Adam(lr)
+    over shuffled batches of batch_size windows, one unrolled_step each.  init:
+    a reference state dict to start from (e.g. a one-step-trained checkpoint).
+    Returns (model, history) with history keys epoch, loss (the mean over the
+    epoch's windows), seconds, and writes checkpoints/hybrid_unrolled_K<K>.pt
+    and history_unrolled_K<K>.json as train_model writes its files (save_dir=None
+    skips)."""
+    engine.require_device(torch.empty(0, device=device), "device")
+    if seed is not None:
+        torch.manual_seed(seed)
+    data = WindowDataset(trajectories, K, device)
+    grid = BaselineSolver(nx=data.nx, dt=dt, nu=nu, device=device).grid
+    if abs(dt / dx - grid.dt / grid.dx) > 1e-12 * abs(dt / dx):
+        raise ValueError(f"dx = {dx} is not the periodic grid's {grid.dx} for nx = {data.nx}")
+    x_dev = torch.as_tensor(np.asarray(x, dtype=np.float32), device=device)
+    model = FluxGNN(MODEL_CONFIG["input_dim"], MODEL_CONFIG["hidden_dim"], MODEL_CONFIG["num_layers"])
+    if init is not None:
+        model.load_state_dict({k: torch.as_tensor(np.asarray(v)) if not isinstance(v, torch.Tensor) else v
+                               for k, v in init.items()})
+    model = model.to(device)
+    model.flatten_parameters_()
+    opt = FlatAdam(model.parameters(), lr=lr)
+    gen = torch.Generator().manual_seed(0 if seed is None else seed)
+    history = {"epoch": [], "loss": [], "seconds": []}
+    model.train()
+    for epoch in range(1, epochs + 1):
+        order = torch.randperm(len(data), generator=gen).to(device)
+        t0 = time.perf_counter()
+        losses = []
+        for b0 in range(0, len(order), batch_size):
+            win = data.batch(order[b0:b0 + batch_size])
+            loss = unrolled_step(model, opt, win, x_dev, grid, channel_weights, through_state)
+            if loss is None:
+                loss = unrolled_loss(model, win, x_dev, grid, channel_weights, through_state)
+                opt.zero_grad()
+                loss.backward()
+                opt.step()
+                loss = loss.detach()
+            losses.append((loss, win.shape[0]))
+        tot = sum(float(l) * n for l, n in losses)  # one host sync per epoch
+        torch.cuda.synchronize(device)
+        history["epoch"].append(epoch)
+        history["loss"].append(tot / len(data))
+        history["seconds"].append(time.perf_counter() - t0)
+        if log:
+            log(f"[Epoch {epoch}/{epochs}] Unrolled loss (K = {K}): {history['loss'][-1]:.6e}")
+    if save_dir is not None:
+        os.makedirs(save_dir, exist_ok=True)
+        torch.save({k: v.clone() for k, v in model.state_dict().items()},
+                   os.path.join(save_dir, f"hybrid_unrolled_K{K}.pt"))
+        with open(os.path.join(save_dir, f"history_unrolled_K{K}.json"), "w") as f:
+            json.dump(history, f, indent=2)
     return model, history

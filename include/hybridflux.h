@@ -237,6 +237,70 @@ int hf_adam_flat(float *dev_params, const float *dev_grads, float *dev_exp_avg, 
                  float *dev_step, unsigned *dev_done, float lr, float beta1, float beta2, float eps, void *stream);
 
 /*
+ * Unrolled training: FluxGNN differentiated through K hybrid solver steps.
+ * Replaces: the torch ops a user would put around FluxGNN's autograd Function
+ * to train through the solver's feedback loop n -> E -> u -> node features
+ * (src/hybrid_solver.py:45-63 under autograd: torch.roll for the two upwind
+ * differences, torch.fft for a differentiable Poisson solve, the MSE against
+ * the classical trajectory), dozens of small launches per unrolled step, by
+ * one launch per forward step and one per backward step around
+ * hf_graph_forward_train / hf_graph_backward.  The reference trains one step
+ * only (its rollout term carries no gradient, hf_ablation_loss_ex above).
+ *
+ * Step k maps s_k = (n, u, E) [B][3][nx] to s_{k+1} with fe = FluxGNN([n, u, E,
+ * x]) [B][2nx] and c = f32(dt/dx), dt = f32(dt):
+ *   F_i = 0.5 (fe[i] + fe[nx+i]),  n'_i = n_i - c (F_i - F_{i-1}),
+ *   u'_i = u_i - c (u_i^2/2 - u_{i-1}^2/2) + dt E_i,  E' = P(n' - 1)
+ * (periodic indices; P the spectral operator of dev_plan = hf_poisson_coeffs),
+ * and the loss is L = (1/K) sum_k mean_{b,ch,i} w_ch (s_k - s*_k)^2, k = 1..K.
+ *
+ * hf_unroll_update: one forward step from dev_flux_edge.  Writes dev_state_next
+ * (bit-identical to hf_step's finite-volume update given the same face flux:
+ * the same device functions) and, when not NULL, dev_node_features_next
+ * [B*nx][4] = [n', u', E', x], the next step's FluxGNN input.  With dev_target
+ * [B][3][nx] (else NULL: no loss) it also writes dev_loss[0] = loss_scale *
+ * sum_{b,ch,i} weights[ch] (s' - target)^2 (weights: 3 HOST floats;
+ * loss_scale = 1 / (K 3 B nx) gives the step's term of L): float64 partials
+ * per IC through dev_workspace (hf_unroll_workspace_bytes(B, nx); the call
+ * zeroes its arrival counter itself with a memset node), summed in IC order by
+ * the last workgroup to arrive, no float atomics: two calls give the same bits.
+ *
+ * hf_unroll_adjoint: the adjoint of that step.  The total gradient of L with
+ * respect to s_{k+1} is g = dev_direct_next + dev_grad_nf_next[:, 0:3]^T +
+ * 2 weights loss_scale (dev_state_next - dev_target): the direct part this
+ * call wrote for step k+1 and hf_graph_backward's dL/dnode_features of step
+ * k+1 ([B*nx][4]; column 3, dL/dx, is not used), each NULL at the last step
+ * (and both NULL at every step for the pushforward form, which cuts the state
+ * gradient between steps).  With a = g_n, b = g_u, e = g_E and a~ = a + P^T e
+ * = a - P e (P is an antisymmetric circulant with zero row sums; e goes
+ * through the operator as it is, with no n - 1 subtraction):
+ *   dev_grad_flux_edge[i] = dev_grad_flux_edge[nx+i] = -0.5 c (a~_i - a~_{i+1})
+ *   dev_direct = (a~_i,  b_i - c u_i (b_i - b_{i+1}),  dt b_i)   [B][3][nx]
+ * with u of dev_state (s_k); dev_direct may be NULL (step 0).  dL/ds_k is then
+ * dev_direct + dL/dnode_features of step k (+ the seed of s_k for k >= 1, which
+ * the next call adds).  Every value is computed by one thread in a fixed
+ * order.
+ *
+ * Kernels: power-of-two nx in [256, 2048] one wave per pair of ICs (the
+ * float64 FFT passes); every other nx <= 6144 one 256-thread workgroup per IC
+ * with the circulant column and the rows in LDS.  Before any device call: NULL
+ * required pointers, B < 1, nx < 1, aliased states or a workspace_bytes too
+ * small return HF_EINVAL (hf_unroll_workspace_bytes: -1); nx > 6144 and
+ * HF_POISSON_TRIDIAG return HF_EUNSUPPORTED.
+ */
+int64_t hf_unroll_workspace_bytes(int B, int nx);
+int hf_unroll_update(const float *dev_flux_edge, const float *dev_state, const float *dev_x, const double *dev_plan,
+                     int poisson_mode, int B, int nx, float c, float dt, float *dev_state_next,
+                     float *dev_node_features_next /* or NULL */, const float *dev_target /* or NULL */,
+                     const float *weights, float loss_scale, float *dev_loss, void *dev_workspace,
+                     int64_t workspace_bytes, void *stream);
+int hf_unroll_adjoint(const float *dev_state, const float *dev_state_next, const float *dev_target,
+                      const float *weights, float loss_scale, const float *dev_direct_next /* or NULL */,
+                      const float *dev_grad_nf_next /* or NULL */, const double *dev_plan, int poisson_mode, int B,
+                      int nx, float c, float dt, float *dev_grad_flux_edge, float *dev_direct /* or NULL */,
+                      void *stream);
+
+/*
  * The reference's other rollout models, inference.
  * dev_params: every parameter, float32, state-dict order, on the device.
  *
