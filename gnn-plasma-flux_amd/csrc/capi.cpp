@@ -551,6 +551,42 @@ int hf_unroll_adjoint(const float *st, const float *st_next, const float *target
   return HF_OK;
 }
 
+// ------------------------------------------------------- unrolled training, PureGNN
+int64_t hf_pure_unroll_workspace_bytes(int B, int nx) {
+  if (!hf::pure_unroll_shape_ok(B, nx)) return -1;
+  return hf::pure_unroll_ws_bytes(B, nx);
+}
+
+int hf_pure_unroll_update(const float *delta, const float *st, const float *x, int B, int nx, float *st_next,
+                          float *nf_next, const float *target, const float *weights, float scale, float *loss, void *ws,
+                          int64_t ws_bytes, void *stream) {
+  if (B < 1 || nx < 1) return fail(HF_EINVAL, "hf_pure_unroll_update: need B >= 1, nx >= 1");
+  if (!delta || !st || !x || !st_next) return fail(HF_EINVAL, "hf_pure_unroll_update: NULL pointer");
+  if (st == st_next) return fail(HF_EINVAL, "hf_pure_unroll_update: state and state_next must not alias");
+  if (!hf::pure_unroll_shape_ok(B, nx)) return fail(HF_EINVAL, "hf_pure_unroll_update: B * ceil(nx / 1024) >= 2^31");
+  if (target) {
+    if (!weights || !loss || !ws)
+      return fail(HF_EINVAL, "hf_pure_unroll_update: NULL weights, loss or workspace with a target");
+    if (ws_bytes < hf::pure_unroll_ws_bytes(B, nx))
+      return fail(HF_EINVAL, "hf_pure_unroll_update: workspace smaller than hf_pure_unroll_workspace_bytes");
+  }
+  HF_CHECK_HIP(hf::launch_pure_unroll_update(delta, st, x, B, nx, st_next, nf_next, target, weights, scale, loss, ws,
+                                             as_stream(stream)),
+               "hf_pure_unroll_update");
+  return HF_OK;
+}
+
+int hf_pure_unroll_adjoint(const float *st_next, const float *target, const float *weights, float scale,
+                           const float *gd_next, const float *gnf_next, int B, int nx, float *gd, void *stream) {
+  if (B < 1 || nx < 1) return fail(HF_EINVAL, "hf_pure_unroll_adjoint: need B >= 1, nx >= 1");
+  if (!st_next || !target || !weights || !gd) return fail(HF_EINVAL, "hf_pure_unroll_adjoint: NULL pointer");
+  if (!hf::pure_unroll_shape_ok(B, nx)) return fail(HF_EINVAL, "hf_pure_unroll_adjoint: B * ceil(nx / 1024) >= 2^31");
+  HF_CHECK_HIP(hf::launch_pure_unroll_adjoint(st_next, target, weights, scale, gd_next, gnf_next, B, nx, gd,
+                                              as_stream(stream)),
+               "hf_pure_unroll_adjoint");
+  return HF_OK;
+}
+
 // ------------------------------------------------------- PureGNN / PINN
 int64_t hf_pure_gnn_param_count(int in_dim, int hidden, int layers) {
   if (in_dim < 1 || hidden < 1 || layers < 0) return -1;

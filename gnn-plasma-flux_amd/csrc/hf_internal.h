@@ -251,6 +251,25 @@ hipError_t launch_unroll_adjoint(const float *st, const float *st_next, const fl
                                  const float *direct_next, const float *gnf_next, const double *pc, int B, int nx,
                                  float c, float dt, float *g_fe, float *direct, hipStream_t s);
 
+// Unrolled training of PureGNN (pure_unroll.hip): the residual update of one
+// rollout step from PureGNN's delta [B*nx][3] with the step's extras, and its
+// adjoint; any nx >= 1, tiled over cells.  Contiguous [B][3][nx] states.
+//  update:  st_next[b][ch][i] = st[b][ch][i] + delta[b*nx+i][ch] (one float32
+//           add); nf_next [B*nx][4] = [n', u', E', x] (or NULL); with target
+//           [B][3][nx]: loss[0] = scale * sum w_ch (st_next - target)^2, summed
+//           in a fixed order through ws (pure_unroll_ws_bytes; w: 3 host floats).
+//  adjoint: gd[b*nx+i][ch] = (2 w_ch scale (st_next - target)[b][ch][i] +
+//           gd_next[b*nx+i][ch]) + gnf_next[b*nx+i][ch] (gd_next [B*nx][3],
+//           gnf_next [B*nx][4], each or NULL: the term is left out).
+bool pure_unroll_shape_ok(int B, int nx);  // B, nx >= 1 and at most 2^31 - 1 tiles of 1024 cells
+int64_t pure_unroll_ws_bytes(int B, int nx);
+hipError_t launch_pure_unroll_update(const float *delta, const float *st, const float *x, int B, int nx, float *st_next,
+                                     float *nf_next, const float *target, const float *w, float scale, float *loss,
+                                     void *ws, hipStream_t s);
+hipError_t launch_pure_unroll_adjoint(const float *st_next, const float *target, const float *w, float scale,
+                                      const float *gd_next, const float *gnf_next, int B, int nx, float *gd,
+                                      hipStream_t s);
+
 // The whole classical rollout (T steps of launch_fv_step's classical update)
 // in one launch, states held in registers: FFT nx up to 1024 (fv_run_fused).
 // state0 [B] x IC stride ld_s0 floats, state_final [B][3][nx] (may alias

@@ -1,0 +1,194 @@
+// Unrolled training of PureGNN: the residual update of one rollout step with
+// the next step's node features and the step's loss term
+// (hf_pure_unroll_update), and its adjoint (hf_pure_unroll_adjoint), one launch
+// each (scripts/evaluation/evaluate_multi_ic.py:53-64 under a K-step loss;
+// include/hybridflux.h has the mathematics).
+//
+// The two sides of the update live in two layouts: delta is [B*nx][3] (cell,
+// channel), the states are [B][3][nx] (channel, cell).  A workgroup owns a tile
+// of kPuTile consecutive cells of one IC: the tile's delta block (3 n
+// contiguous floats) is read lane after lane into LDS and read back per cell
+// (stride 3 words: 3 is odd, so no two lanes of a half wave share a bank), the
+// three state rows are read and written lane after lane, and a cell's features
+// go out as one 16-byte store.  The adjoint runs the same tile the other way.
+// The loss follows unroll.hip: float64 partials, one per workgroup, summed in
+// workgroup order by the last wave to arrive.
+#include "hf_internal.h"
+
+namespace hf {
+namespace {
+
+constexpr int kPuThreads = 256;
+constexpr int kPuTile = 1024;  // cells of one IC per workgroup: 12 KiB of LDS per staged block
+typedef float pu_f4 __attribute__((ext_vector_type(4)));
+
+inline size_t al256(size_t b) { return (b + 255) / 256 * 256; }
+inline int64_t tiles_of(int nx) { return ((int64_t)nx + kPuTile - 1) / kPuTile; }
+
+// Workspace: [0, 256) the arrival counter (zeroed by the launcher's memset
+// node before every launch), then one float64 loss partial per workgroup.
+constexpr size_t kPuCounterBytes = 256;
+
+struct LossArgs {
+  const float *tgt;  // [B][3][nx] or NULL: no loss term
+  float w0, w1, w2;
+  double scale;
+  double *part;      // [B * tiles]
+  unsigned *cnt;
+  float *loss;
+};
+
+__device__ __forceinline__ double wave_sum(double a) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) a += __shfl_xor(a, o, 64);
+  return a;
+}
+
+// The step's loss from the per-workgroup partials, by the wave that arrives
+// last (unroll.hip's scheme).  Called by a whole wave after its partial store;
+// `total` waves call it per launch.  Agent-scope release before the ticket,
+// agent-scope acquire after the last one (the per-XCD L2s are not coherent);
+// the partials are summed in workgroup order per lane and then across the lanes
+// in a fixed tree, so the value does not depend on which wave arrives last.
+__device__ __forceinline__ void loss_arrive(const LossArgs &la, unsigned total, int lane) {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  unsigned t = 0;
+  if (lane == 0) t = __hip_atomic_fetch_add(la.cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  t = __shfl(t, 0, 64);
+  if (t != total - 1) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  const double *part = la.part;
+  double a = 0.0;
+  for (unsigned i = lane; i < total; i += 64) a += part[i];
+  a = wave_sum(a);
+  if (lane == 0) la.loss[0] = (float)(a * la.scale);
+}
+
+// w (pred - target)^2 of one value, the difference rounded to float32
+__device__ __forceinline__ double sq_err(float pred, float tgt, float w) {
+  const double d = (double)__fsub_rn(pred, tgt);
+  return (double)w * (d * d);
+}
+
+// ---------------------------------------------------------------------- forward
+// Workgroup blockIdx.x = b * tiles + t owns cells [t kPuTile, t kPuTile + n) of IC b.
+__global__ __launch_bounds__(kPuThreads) void pure_unroll_update_kernel(const float *__restrict__ delta,
+                                                                        const float *__restrict__ in,
+                                                                        const float *__restrict__ x, int nx, int tiles,
+                                                                        float *__restrict__ out, float *__restrict__ nf,
+                                                                        LossArgs la) {
+  __shared__ __attribute__((aligned(16))) float Ld[3 * kPuTile];
+  __shared__ double red[kPuThreads / 64];
+  const int64_t b = blockIdx.x / (unsigned)tiles;
+  const int c0 = (int)(blockIdx.x % (unsigned)tiles) * kPuTile;
+  const int n = min(kPuTile, nx - c0);
+  const float *db = delta + (b * nx + c0) * 3;  // the tile's delta block, (cell, channel) order
+  for (int j = threadIdx.x; j < 3 * n; j += kPuThreads) Ld[j] = db[j];
+  __syncthreads();
+  const int64_t sb = b * 3 * nx + c0;  // row 0 of the tile in the [B][3][nx] tensors
+  const float *tg = la.tgt ? la.tgt + sb : nullptr;
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < n; i += kPuThreads) {
+    const float n_new = __fadd_rn(in[sb + i], Ld[3 * i]);
+    const float u_new = __fadd_rn(in[sb + nx + i], Ld[3 * i + 1]);
+    const float E_new = __fadd_rn(in[sb + 2 * (int64_t)nx + i], Ld[3 * i + 2]);
+    out[sb + i] = n_new;
+    out[sb + nx + i] = u_new;
+    out[sb + 2 * (int64_t)nx + i] = E_new;
+    if (nf) *reinterpret_cast<pu_f4 *>(nf + 4 * (b * nx + c0 + i)) = pu_f4{n_new, u_new, E_new, x[c0 + i]};
+    if (tg)
+      acc += sq_err(n_new, tg[i], la.w0) + sq_err(u_new, tg[nx + i], la.w1) +
+             sq_err(E_new, tg[2 * (int64_t)nx + i], la.w2);
+  }
+  if (!tg) return;  // (uniform)
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x >= 64) return;
+  if (threadIdx.x == 0) la.part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+  loss_arrive(la, gridDim.x, threadIdx.x);
+}
+
+// ---------------------------------------------------------------------- adjoint
+// grad_delta[cell][ch] = (seed + grad_delta_next[cell][ch]) + grad_nf_next[cell][ch],
+// seed = gs_ch (s' - target)[ch][cell]; a NULL term is left out.
+__global__ __launch_bounds__(kPuThreads) void pure_unroll_adjoint_kernel(const float *__restrict__ sn,
+                                                                         const float *__restrict__ tgt, float gs0,
+                                                                         float gs1, float gs2,
+                                                                         const float *__restrict__ gd_next,
+                                                                         const float *__restrict__ gnf_next, int nx,
+                                                                         int tiles, float *__restrict__ gd) {
+  __shared__ __attribute__((aligned(16))) float Ls[3 * kPuTile];  // the seeds, (cell, channel) order
+  __shared__ __attribute__((aligned(16))) float Lg[3 * kPuTile];  // columns 0..2 of grad_nf_next
+  const int64_t b = blockIdx.x / (unsigned)tiles;
+  const int c0 = (int)(blockIdx.x % (unsigned)tiles) * kPuTile;
+  const int n = min(kPuTile, nx - c0);
+  const int64_t sb = b * 3 * nx + c0;
+  for (int i = threadIdx.x; i < n; i += kPuThreads) {
+    Ls[3 * i] = gs0 * (sn[sb + i] - tgt[sb + i]);
+    Ls[3 * i + 1] = gs1 * (sn[sb + nx + i] - tgt[sb + nx + i]);
+    Ls[3 * i + 2] = gs2 * (sn[sb + 2 * (int64_t)nx + i] - tgt[sb + 2 * (int64_t)nx + i]);
+    if (gnf_next) {
+      const pu_f4 g = *reinterpret_cast<const pu_f4 *>(gnf_next + 4 * (b * nx + c0 + i));
+      Lg[3 * i] = g.x;
+      Lg[3 * i + 1] = g.y;
+      Lg[3 * i + 2] = g.z;
+    }
+  }
+  __syncthreads();
+  const int64_t db = (b * nx + c0) * 3;
+  for (int j = threadIdx.x; j < 3 * n; j += kPuThreads) {
+    float v = Ls[j];
+    if (gd_next) v = v + gd_next[db + j];
+    if (gnf_next) v = v + Lg[j];
+    gd[db + j] = v;
+  }
+}
+
+}  // namespace
+
+int64_t pure_unroll_ws_bytes(int B, int nx) {
+  return (int64_t)(kPuCounterBytes + al256(sizeof(double) * (size_t)((int64_t)B * tiles_of(nx))));
+}
+
+// one workgroup per tile: B * tiles of them must fit a grid
+bool pure_unroll_shape_ok(int B, int nx) { return B >= 1 && nx >= 1 && (int64_t)B * tiles_of(nx) <= 0x7fffffffLL; }
+
+hipError_t launch_pure_unroll_update(const float *delta, const float *st, const float *x, int B, int nx, float *st_next,
+                                     float *nf_next, const float *target, const float *w, float scale, float *loss,
+                                     void *ws, hipStream_t s) {
+  if (!pure_unroll_shape_ok(B, nx)) return hipErrorInvalidValue;
+  const int tiles = (int)tiles_of(nx);
+  const unsigned grid = (unsigned)((int64_t)B * tiles);
+  LossArgs la{};
+  if (target) {
+    la.tgt = target;
+    la.w0 = w[0], la.w1 = w[1], la.w2 = w[2];
+    la.scale = (double)scale;
+    la.cnt = static_cast<unsigned *>(ws);
+    la.part = reinterpret_cast<double *>(static_cast<char *>(ws) + kPuCounterBytes);
+    la.loss = loss;
+    // the arrival counter starts every launch at 0 (a memset node, not a kernel)
+    if (hipError_t e = hipMemsetAsync(ws, 0, 16, s)) return e;
+  }
+  hipLaunchKernelGGL(pure_unroll_update_kernel, dim3(grid), dim3(kPuThreads), 0, s, delta, st, x, nx, tiles, st_next,
+                     nf_next, la);
+  return hipGetLastError();
+}
+
+hipError_t launch_pure_unroll_adjoint(const float *st_next, const float *target, const float *w, float scale,
+                                      const float *gd_next, const float *gnf_next, int B, int nx, float *gd,
+                                      hipStream_t s) {
+  if (!pure_unroll_shape_ok(B, nx)) return hipErrorInvalidValue;
+  const int tiles = (int)tiles_of(nx);
+  const unsigned grid = (unsigned)((int64_t)B * tiles);
+  float gs[3];
+  for (int k = 0; k < 3; ++k) gs[k] = (float)(2.0 * (double)w[k] * (double)scale);
+  hipLaunchKernelGGL(pure_unroll_adjoint_kernel, dim3(grid), dim3(kPuThreads), 0, s, st_next, target, gs[0], gs[1],
+                     gs[2], gd_next, gnf_next, nx, tiles, gd);
+  return hipGetLastError();
+}
+
+}  // namespace hf

@@ -112,6 +112,11 @@ SIGNATURES = {
                                  c_void_p]),
     "hf_unroll_adjoint": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p,
                                   c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p]),
+    "hf_pure_unroll_workspace_bytes": (c_int64, [c_int, c_int]),
+    "hf_pure_unroll_update": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_float, c_void_p, c_void_p, c_int64, c_void_p]),
+    "hf_pure_unroll_adjoint": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_int,
+                                       c_void_p, c_void_p]),
 }
 
 _lib = None

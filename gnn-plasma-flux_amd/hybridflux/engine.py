@@ -632,6 +632,88 @@ def unroll_adjoint(grid, state, state_next, target, weights, scale, direct_next=
     return g_fe, direct
 
 
+def pure_unroll_workspace(B, nx, dev):
+    """hf_pure_unroll_workspace_bytes of scratch for pure_unroll_update on `dev` (a uint8 tensor)."""
+    nb = int(lib().hf_pure_unroll_workspace_bytes(B, nx))
+    if nb < 0:
+        raise ValueError(f"pure unroll workspace: need B >= 1, nx >= 1 (B = {B}, nx = {nx})")
+    return torch.empty(nb, dtype=torch.uint8, device=dev)
+
+
+def _unroll_cells(t, B, nx, width, dev, what):
+    """A per-cell tensor [B*nx, width] of the PureGNN side (delta, node features and their gradients)."""
+    require_device(t, what)
+    if t.dtype != torch.float32 or tuple(t.shape) != (B * nx, width) or t.device != dev or not t.is_contiguous():
+        raise ValueError(f"{what} must be contiguous float32 [{B * nx},{width}] on {dev}, got {tuple(t.shape)} "
+                         f"{t.dtype}")
+    return t
+
+
+def pure_unroll_update(delta, state, x, target=None, weights=(1.0, 1.0, 1.0), scale=0.0, want_nf=True, out=None,
+                       loss=None, ws=None):
+    """hf_pure_unroll_update: one step of PureGNN's rollout, state_next = state
+    + delta^T for `state` [B,3,nx] and PureGNN's delta [B*nx,3]
+    (evaluate_multi_ic.py:53-64).  Returns (state_next [B,3,nx],
+    node_features_next [B*nx,4] = [n', u', E', x] or None, loss [1] or None):
+    the next step's PureGNN input, and with `target` [B,3,nx] the term scale *
+    sum w_ch (state_next - target)^2.  x: the positions [nx].  out / loss / ws:
+    preallocated state_next, loss element and workspace (pure_unroll_workspace)."""
+    require_device(state, "state")
+    if state.dim() != 3:
+        raise ValueError(f"state must be [B,3,nx], got {tuple(state.shape)}")
+    B, _, nx = state.shape
+    dev = state.device
+    st = _unroll_state(state, B, nx, dev, "state")
+    d = _unroll_cells(delta.detach(), B, nx, 3, dev, "delta")
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.numel() != nx or x.device != dev \
+            or not x.is_contiguous():
+        raise ValueError(f"pure unroll update: x must be contiguous float32 [{nx}] on {dev}")
+    out = torch.empty_like(st) if out is None else _unroll_state(out, B, nx, dev, "out")
+    nf = torch.empty(B * nx, 4, device=dev) if want_nf else None
+    w, nb = None, 0
+    if target is not None:
+        target = _unroll_state(target, B, nx, dev, "target")
+        w = _weights3(weights)
+        loss = torch.empty(1, device=dev) if loss is None else loss
+        if loss.dtype != torch.float32 or loss.numel() != 1 or loss.device != dev:
+            raise ValueError("pure unroll update: loss must be one float32 element on the state's device")
+        ws = pure_unroll_workspace(B, nx, dev) if ws is None else ws
+        if ws.device != dev or not ws.is_contiguous():
+            raise ValueError(f"pure unroll update: the workspace must be contiguous on {dev}")
+        nb = ws.numel() * ws.element_size()
+    else:
+        loss = ws = None
+    with torch.cuda.device(dev):
+        check(lib().hf_pure_unroll_update(ptr(d), ptr(st), ptr(x), B, nx, ptr(out), ptr(nf), ptr(target), ptr(w),
+                                          float(scale), ptr(loss), ptr(ws), nb, stream_of(dev)))
+    return out, nf, loss
+
+
+def pure_unroll_adjoint(state_next, target, weights, scale, grad_delta_next=None, gnf_next=None):
+    """hf_pure_unroll_adjoint: the adjoint of pure_unroll_update's step.
+    state_next (the predicted s_{k+1}) and target (s*_{k+1}) [B,3,nx];
+    grad_delta_next [B*nx,3] / gnf_next [B*nx,4]: what this call returned for
+    step k+1 and PureGNN's d node_features of step k+1 (None at the last step,
+    or to cut the state gradient).  Returns d loss / d delta [B*nx,3]."""
+    require_device(state_next, "state_next")
+    if state_next.dim() != 3:
+        raise ValueError(f"state_next must be [B,3,nx], got {tuple(state_next.shape)}")
+    B, _, nx = state_next.shape
+    dev = state_next.device
+    sn = _unroll_state(state_next, B, nx, dev, "state_next")
+    tg = _unroll_state(target, B, nx, dev, "target")
+    if grad_delta_next is not None:
+        grad_delta_next = _unroll_cells(grad_delta_next, B, nx, 3, dev, "grad_delta_next")
+    if gnf_next is not None:
+        gnf_next = _unroll_cells(gnf_next, B, nx, 4, dev, "gnf_next")
+    w = _weights3(weights)
+    gd = torch.empty(B * nx, 3, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().hf_pure_unroll_adjoint(ptr(sn), ptr(tg), ptr(w), float(scale), ptr(grad_delta_next),
+                                           ptr(gnf_next), B, nx, ptr(gd), stream_of(dev)))
+    return gd
+
+
 def ablation_loss_terms(grid, flux_edge, st, ft, sn, lam, rollout_steps=0, dt=None):
     """hf_ablation_loss_ex: the reference trainer's loss (scripts/training/
     train_ablation.py:120-206) for B samples.  flux_edge [B, 2nx], st / sn

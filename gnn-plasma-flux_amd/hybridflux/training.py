@@ -23,6 +23,12 @@ PureGNN (scripts/training/train_pure_gnn.py:79-151) trains here too, at the
 end of this module: state_mse_loss (hf_state_mse), pure_gnn_step and
 train_pure_gnn, over PureGNN's own autograd Function (baselines.py,
 pure_train.hip).
+
+Both models also train through their rollouts, K steps deep: unrolled_loss /
+unrolled_step / train_unrolled for FluxGNN through the hybrid solver
+(unroll.hip), pure_unrolled_loss / pure_unrolled_step /
+train_pure_gnn_unrolled for PureGNN through state <- state + PureGNN(...)
+(pure_unroll.hip).
 """
 import json
 import os
@@ -810,5 +816,221 @@ def train_unrolled(trajectories, x, dt, dx, nu, K=4, epochs=10, lr=1e-3, batch_s
         torch.save({k: v.clone() for k, v in model.state_dict().items()},
                    os.path.join(save_dir, f"hybrid_unrolled_K{K}.pt"))
         with open(os.path.join(save_dir, f"history_unrolled_K{K}.json"), "w") as f:
+            json.dump(history, f, indent=2)
+    return model, history
+
+
+# ------------------------------------------------ unrolled training, PureGNN
+# PureGNN differentiated through K steps of its own rollout state <- state +
+# PureGNN([n, u, E, x]) (evaluate_multi_ic.py:53-64; include/hybridflux.h,
+# hf_pure_unroll_update / hf_pure_unroll_adjoint): the baseline's loss sees the
+# loop it is scored on, as FluxGNN's does above.
+def _pure_unrolled_forward(flat, dims, traj, x, weights):
+    """The K taped forwards and residual updates.  Returns (loss [], rec): rec
+    holds what the backward needs and the predicted states `pred` [K,B,3,nx]."""
+    B, K1, _, nx = traj.shape
+    K = K1 - 1
+    dev = traj.device
+    tr = traj.detach().to(torch.float32).transpose(0, 1).contiguous()  # [K+1,B,3,nx]: a step's rows contiguous
+    ei = shared_chain_edge_index(nx, B, dev)
+    scale = 1.0 / (K * 3 * B * nx)
+    pred = torch.empty(K, B, 3, nx, device=dev)
+    terms = torch.empty(K, device=dev)
+    ws = engine.pure_unroll_workspace(B, nx, dev)
+    st = tr[0]
+    nf = pure_gnn_features(st, x)
+    tapes, nfs, chain_nx = [], [], 0
+    for k in range(K):
+        delta, tape, nf_d, ei_d, chain_nx = engine.pure_gnn_forward_train(flat, dims, nf, ei)
+        _, nf, _ = engine.pure_unroll_update(delta, st, x, tr[k + 1], weights, scale, want_nf=k + 1 < K, out=pred[k],
+                                             loss=terms[k:k + 1], ws=ws)
+        tapes.append(tape)
+        nfs.append(nf_d)
+        st = pred[k]
+    rec = dict(tr=tr, pred=pred, tapes=tapes, nfs=nfs, ei=ei_d, chain_nx=chain_nx, scale=scale, K=K)
+    return terms.sum(), rec
+
+
+def _pure_unrolled_backward(flat, dims, rec, weights, through_state):
+    """The K adjoint / PureGNN-backward pairs, last step first; the parameter
+    gradients of the steps are added in that order (K-1, K-2, ..., 0).
+    Returns d loss / d params as one flat buffer."""
+    tr, pred, K = rec["tr"], rec["pred"], rec["K"]
+    total, gd, gnf = None, None, None
+    for k in range(K - 1, -1, -1):
+        # dL/ds_{k+1} transposed is dL/ddelta_k: the seed of s_{k+1}, what reached s_{k+2} (the
+        # residual update is the identity in the state) and step k+1's feature gradient
+        gd = engine.pure_unroll_adjoint(pred[k], tr[k + 1], weights, rec["scale"], gd if through_state else None, gnf)
+        gp, gnf = engine.pure_gnn_backward(flat, dims, rec["nfs"][k], rec["ei"], rec["chain_nx"], rec["tapes"][k], gd,
+                                           through_state and k > 0)
+        total = gp if total is None else total.add_(gp)
+    return total
+
+
+def _pure_unrolled_check(model, traj, x):
+    from .baselines import PureGNN
+    if type(model) is not PureGNN:
+        raise TypeError("pure_unrolled_loss trains PureGNN")
+    if model.input_dim != 4:
+        raise ValueError("the rollout builds [n,u,E,x] node features: input_dim must be 4")
+    engine.require_device(traj, "traj")
+    if traj.dim() != 4 or traj.shape[1] < 2 or traj.shape[2] != 3 or traj.shape[3] < 1 or traj.shape[0] < 1:
+        raise ValueError(f"traj must be [B,K+1,3,nx] with B >= 1, K >= 1, nx >= 1, got {tuple(traj.shape)}")
+    x = torch.as_tensor(x, dtype=torch.float32, device=traj.device).reshape(-1).contiguous()
+    if x.numel() != traj.shape[3]:
+        raise ValueError("x must hold nx positions")
+    return x
+
+
+class _PureUnrolledLoss(torch.autograd.Function):
+    """pure_unrolled_loss as one Function: forward = K taped PureGNN forwards
+    and residual updates, backward = K adjoint / PureGNN-backward pairs."""
+
+    @staticmethod
+    def forward(ctx, traj, x, weights, through_state, dims, *params):
+        dev = traj.device
+        flat = _flat_view(params, dev)
+        if flat is None:
+            flat = torch.cat([q.detach().reshape(-1).to(device=dev, dtype=torch.float32) for q in params])
+        loss, rec = _pure_unrolled_forward(flat, dims, traj, x, weights)
+        ctx.rec, ctx.flat, ctx.weights, ctx.through, ctx.dims = rec, flat, weights, through_state, dims
+        ctx.shapes = [q.shape for q in params]
+        ctx.param_devices = [q.device for q in params]
+        ctx.mark_non_differentiable(rec["pred"])
+        return loss, rec["pred"]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss, g_pred):
+        gp = _pure_unrolled_backward(ctx.flat, ctx.dims, ctx.rec, ctx.weights, ctx.through)
+        ctx.rec = None  # the tapes are consumed
+        gp = gp.mul_(g_loss)  # (exact for autograd's seed 1)
+        grads, o = [], 0
+        for shp, pd in zip(ctx.shapes, ctx.param_devices):
+            n = shp.numel()
+            grads.append(gp[o:o + n].view(shp).to(pd))
+            o += n
+        return (None, None, None, None, None, *grads)
+
+
+def pure_unrolled_loss(model, traj, x, channel_weights=(1.0, 1.0, 1.0), through_state=True, return_states=False):
+    """L = (1/K) sum_{k=1..K} mean_{b,ch,i} w_ch (s^_k - s*_k)^2 of PureGNN's own
+    rollout s^_{k+1} = s^_k + PureGNN([n, u, E, x])^T (evaluate_multi_ic.py:53-64)
+    unrolled K steps from traj[:, 0], against the targets traj[:, 1:] (classical
+    solver states): traj [B,K+1,3,nx] on the device, x [nx]; any nx.  The same
+    loss as unrolled_loss.  A scalar with autograd into the model's parameters,
+    through every step's PureGNN call and, with through_state, through the state
+    the steps hand on (the residual update and the next node features).
+    through_state=False cuts the state gradient between steps (the pushforward
+    form): each step's loss reaches only its own PureGNN call.  Per unrolled step
+    the forward is hf_pure_gnn_forward_train + one hf_pure_unroll_update launch,
+    the backward one hf_pure_unroll_adjoint launch + hf_pure_gnn_backward.
+    model: a PureGNN with input_dim 4.  return_states: also the predicted states
+    [K,B,3,nx] (no gradient)."""
+    x = _pure_unrolled_check(model, traj, x)
+    dims = (model.input_dim, model.hidden_dim, model.num_layers)
+    w = tuple(float(v) for v in channel_weights)
+    loss, pred = _PureUnrolledLoss.apply(traj, x, w, bool(through_state), dims, *model.parameters())
+    return (loss, pred) if return_states else loss
+
+
+def pure_unrolled_step(model, opt, traj, x, channel_weights=(1.0, 1.0, 1.0), through_state=True):
+    """pure_unrolled_loss -> backward -> opt.step() without autograd, after
+    unrolled_step: PureGNN with flat parameters (flatten_parameters_), FlatAdam
+    over exactly those parameters, grad enabled.  The same forwards, adjoints,
+    backwards and gradient sum as the autograd step, in the same order, so the
+    same parameters bit for bit, without autograd's seed, product and
+    bookkeeping launches.  Returns the detached loss, or None when the case does
+    not apply (the caller then takes the autograd step)."""
+    from .baselines import PureGNN
+    if type(model) is not PureGNN or not isinstance(opt, FlatAdam) or not torch.is_grad_enabled():
+        return None
+    params = list(model.parameters())
+    if len(opt.param_groups) != 1 or [id(q) for q in opt.param_groups[0]["params"]] != [id(q) for q in params] \
+            or not all(q.requires_grad for q in params):
+        return None
+    flat = _flat_view(params, traj.device)
+    if flat is None:
+        return None
+    x = _pure_unrolled_check(model, traj, x)
+    dims = (model.input_dim, model.hidden_dim, model.num_layers)
+    w = tuple(float(v) for v in channel_weights)
+    loss, rec = _pure_unrolled_forward(flat, dims, traj, x, w)
+    gp = _pure_unrolled_backward(flat, dims, rec, w, bool(through_state))
+    o = 0
+    for q in params:
+        q.grad = gp[o:o + q.numel()].view_as(q)
+        o += q.numel()
+    opt.step()
+    return loss.detach()
+
+
+def pure_unrolled_train_flop_per_sample(K=4, nx=64, H=128, L=4, F=4):
+    """Algorithmic FLOPs of one sample (one K-step window) of PureGNN's unrolled
+    training step: K times the forward and backward terms of
+    pure_gnn_train_flop_per_sample, plus the input layer's data gradient 2FH per
+    cell for the K - 1 steps whose node features carry a gradient back to the
+    previous step.  The residual updates, their adjoints and the loss
+    (elementwise work outside the GEMMs) are not counted."""
+    return K * pure_gnn_train_flop_per_sample(nx, H, L, F) + (K - 1) * 2 * F * H * nx
+
+
+def train_pure_gnn_unrolled(trajectories, x, K=4, epochs=10, lr=1e-3, batch_size=32, hidden_dim=None, num_layers=None,
+                            seed=None, init=None, channel_weights=(1.0, 1.0, 1.0), through_state=True, device="cuda",
+                            save_dir="checkpoints", log=print):
+    """Train (or fine-tune) PureGNN on K-step windows of classical trajectories
+    [N,T+1,3,nx] (datagen.generate_trajectories) with the unrolled loss:
+    train_unrolled's loop -- Adam(lr) over shuffled batches of batch_size windows
+    (WindowDataset), one pure_unrolled_step each, one host sync per epoch -- on
+    PureGNN(4, hidden_dim, num_layers) (default MODEL_CONFIG's, as
+    train_pure_gnn).  seed also seeds the initial weights; init: a reference
+    state dict to start from (e.g. a one-step-trained checkpoint).  Returns
+    (model, history) with history keys epoch, loss (the mean over the epoch's
+    windows), seconds, and writes checkpoints/pure_gnn_unrolled_K<K>.pt (a state
+    dict the reference's PureGNN loads) and history_pure_gnn_unrolled_K<K>.json
+    (save_dir=None skips)."""
+    from .baselines import PureGNN
+    engine.require_device(torch.empty(0, device=device), "device")
+    if seed is not None:
+        torch.manual_seed(seed)
+    data = WindowDataset(trajectories, K, device)
+    x_dev = torch.as_tensor(np.asarray(x, dtype=np.float32), device=device)
+    model = PureGNN(MODEL_CONFIG["input_dim"], hidden_dim or MODEL_CONFIG["hidden_dim"],
+                    MODEL_CONFIG["num_layers"] if num_layers is None else num_layers)
+    if init is not None:
+        model.load_state_dict({k: torch.as_tensor(np.asarray(v)) if not isinstance(v, torch.Tensor) else v
+                               for k, v in init.items()})
+    model = model.to(device)
+    model.flatten_parameters_()
+    opt = FlatAdam(model.parameters(), lr=lr)
+    gen = torch.Generator().manual_seed(0 if seed is None else seed)
+    history = {"epoch": [], "loss": [], "seconds": []}
+    model.train()
+    for epoch in range(1, epochs + 1):
+        order = torch.randperm(len(data), generator=gen).to(device)
+        t0 = time.perf_counter()
+        losses = []
+        for b0 in range(0, len(order), batch_size):
+            win = data.batch(order[b0:b0 + batch_size])
+            loss = pure_unrolled_step(model, opt, win, x_dev, channel_weights, through_state)
+            if loss is None:
+                loss = pure_unrolled_loss(model, win, x_dev, channel_weights, through_state)
+                opt.zero_grad()
+                loss.backward()
+                opt.step()
+                loss = loss.detach()
+            losses.append((loss, win.shape[0]))
+        tot = sum(float(l) * n for l, n in losses)  # one host sync per epoch
+        torch.cuda.synchronize(device)
+        history["epoch"].append(epoch)
+        history["loss"].append(tot / len(data))
+        history["seconds"].append(time.perf_counter() - t0)
+        if log:
+            log(f"[Epoch {epoch}/{epochs}] PureGNN unrolled loss (K = {K}): {history['loss'][-1]:.6e}")
+    if save_dir is not None:
+        os.makedirs(save_dir, exist_ok=True)
+        torch.save({k: v.clone() for k, v in model.state_dict().items()},
+                   os.path.join(save_dir, f"pure_gnn_unrolled_K{K}.pt"))
+        with open(os.path.join(save_dir, f"history_pure_gnn_unrolled_K{K}.json"), "w") as f:
             json.dump(history, f, indent=2)
     return model, history

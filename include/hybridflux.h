@@ -396,6 +396,66 @@ int hf_state_mse(const float *dev_delta, const float *dev_state_t, const float *
                  int B, int nx, float *dev_loss, float *dev_grad_delta, void *dev_workspace,
                  int64_t workspace_bytes, void *stream);
 
+/*
+ * Unrolled training of PureGNN: the model differentiated through K steps of
+ * its own rollout.  Replaces: scripts/evaluation/evaluate_multi_ic.py:53-64
+ * under autograd -- the torch ops a user would put around PureGNN's autograd
+ * Function to train through state <- state + PureGNN([n, u, E, x]) (permute,
+ * reshape, cat, add, the weighted MSE against the classical trajectory and
+ * their autograd mirrors, about 20 small launches per unrolled step on tensors
+ * in two layouts) -- by one launch per forward step and one per backward step
+ * around hf_pure_gnn_forward_train / hf_pure_gnn_backward.  The reference
+ * trains PureGNN one step at a time (hf_state_mse above).
+ *
+ * Step k maps s_k [B][3][nx] to s_{k+1} = s_k + delta_k^T with delta_k =
+ * PureGNN([n, u, E, x]) [B*nx][3], and the loss is hf_unroll_update's:
+ * L = (1/K) sum_k mean_{b,ch,i} w_ch (s_k - s*_k)^2, k = 1..K.
+ *
+ * hf_pure_unroll_update (replaces evaluate_multi_ic.py:53-64 under autograd,
+ * forward): dev_state_next[b][ch][i] = dev_state[b][ch][i] +
+ * dev_delta[b*nx+i][ch], one float32 add per value (bit-equal to the torch
+ * expression), and, when not NULL, dev_node_features_next [B*nx][4] =
+ * [n', u', E', x_i], exact copies: the next step's PureGNN input.  With
+ * dev_target [B][3][nx] (else NULL: no loss, and dev_loss, weights and the
+ * workspace are not used) it also writes dev_loss[0] = loss_scale *
+ * sum_{b,ch,i} weights[ch] (s' - target)^2 (weights: 3 HOST floats; loss_scale
+ * = 1 / (K 3 B nx) gives the step's term of L): float64 partials per workgroup
+ * through dev_workspace (hf_pure_unroll_workspace_bytes(B, nx); the call zeroes
+ * its arrival counter itself with a memset node), summed in workgroup order by
+ * the last workgroup to arrive, no float atomics: two calls give the same bits.
+ *
+ * hf_pure_unroll_adjoint (replaces evaluate_multi_ic.py:53-64 under autograd,
+ * backward): with seed = 2 weights[ch] loss_scale (dev_state_next - dev_target)
+ * [b][ch][i],
+ *   dev_grad_delta[b*nx+i][ch] = (seed + dev_grad_delta_next[b*nx+i][ch])
+ *                                + dev_grad_nf_next[b*nx+i][ch].
+ * dev_grad_delta_next [B*nx][3] is what this call wrote for step k+1 and
+ * dev_grad_nf_next [B*nx][4] hf_pure_gnn_backward's dL/dnode_features of step
+ * k+1 (column 3, dL/dx, is not used); both NULL at the last step, and at every
+ * step for the pushforward form, which cuts the state gradient between steps.
+ * A NULL term is left out of the sum, not added as zero.  The residual update
+ * is the identity in the state, so dL/ds_{k+1} transposed IS dL/ddelta_k: no
+ * separate direct part.  Every value is written by one thread in that order.
+ *
+ * Kernels: one 256-thread workgroup per tile of 1024 cells of an IC, the
+ * (cell, channel) <-> (channel, cell) transposition staged through LDS so both
+ * layouts move lane after lane; node features as 16-byte stores.  Any nx >= 1
+ * and B >= 1 with B * ceil(nx / 1024) < 2^31.  Before any device call: NULL
+ * required pointers, B < 1, nx < 1, that product too large, dev_state_next ==
+ * dev_state, a target without dev_loss, weights or workspace, or a
+ * workspace_bytes too small return HF_EINVAL (hf_pure_unroll_workspace_bytes:
+ * -1).
+ */
+int64_t hf_pure_unroll_workspace_bytes(int B, int nx);
+int hf_pure_unroll_update(const float *dev_delta, const float *dev_state, const float *dev_x, int B, int nx,
+                          float *dev_state_next, float *dev_node_features_next /* or NULL */,
+                          const float *dev_target /* or NULL */, const float *weights, float loss_scale,
+                          float *dev_loss, void *dev_workspace, int64_t workspace_bytes, void *stream);
+int hf_pure_unroll_adjoint(const float *dev_state_next, const float *dev_target, const float *weights,
+                           float loss_scale, const float *dev_grad_delta_next /* or NULL */,
+                           const float *dev_grad_nf_next /* or NULL */, int B, int nx, float *dev_grad_delta,
+                           void *stream);
+
 int64_t hf_pinn_param_count(int dim, int hidden, int layers);
 int64_t hf_pinn_workspace_bytes(int dim, int hidden, int64_t B);
 int hf_pinn_forward(const float *dev_params, int dim, int hidden, int layers, const float *dev_state,
