@@ -204,6 +204,136 @@ PinnW pinn_view(const float *p, int D, int H, int L) {
 }
 
 // ---------------------------------------------------------------------------
+// Scoring inside the one-launch rollouts (pure_score_kernel, pinn_score_kernel):
+// what scripts/evaluation/evaluate_multi_ic.py:21-94 ('pure_gnn', 'pinn') and
+// evaluate_long_rollout.py:18-81 compute from a model trajectory and a
+// BaselineSolver trajectory of the same IC, formed step by step from the state
+// in LDS, so neither trajectory goes through HBM.  One wave scores an IC with
+// one cell per lane (nx <= 64):
+//  * the metric row of hf_traj_metrics (state_metrics_kernel: a 256-thread
+//    workgroup whose cells all sit in wave 0, so block_metrics adds this wave's
+//    reduction and three +0.0 partials, as fv_run_small_kernel reproduces);
+//  * the classical twin: the wave keeps the IC's classical n, u, E in registers
+//    for the whole rollout and steps them with the expressions of
+//    fv_run_small_kernel in its order, so the twin's states are hf_run(model =
+//    NULL)'s bit for bit; rho (or the tridiagonal solve's psi) goes through a
+//    wave-private LDS row;
+//  * the MSE row of hf_traj_mse (traj_mse_kernel: float64 difference and
+//    square, the xor butterfly, wave 0's partial + three 0 partials, / nx).
+struct ScoreArgs {
+  float *metrics;     // [B][T+1][HF_NUM_METRICS] or NULL
+  float *mse;         // [B][T+1][3] or NULL; the twin runs exactly when it is given
+  float *metrics_cl;  // [B][T+1][HF_NUM_METRICS] of the twin, or NULL
+  const double *pc;   // the twin's Poisson plan (spectral: c[nx]; tridiagonal: h)
+  int tri;
+  float c, dt, nu, dx2;
+};
+constexpr int kScorePartials = 4;  // wave partials the 256-thread scoring kernels add (3 of them zero here)
+
+struct TwinCell {
+  float n, u, E;
+};
+
+// block_metrics' result for a workgroup whose cells all sit in its wave 0
+__device__ __forceinline__ void score_store_metrics(MetricAcc &m, float *dst, int nx, int lane) {
+  m.wave_reduce();
+  if (lane == 0) {
+    MetricAcc w;
+    w.init();
+    w.energy += m.energy;
+    w.charge += m.charge;
+    w.maxdev = m.maxdev > w.maxdev ? m.maxdev : w.maxdev;
+    w.finite &= m.finite;
+    for (int k = 1; k < kScorePartials; ++k) {
+      w.energy += 0.0;
+      w.charge += 0.0;
+    }
+    w.store(dst, nx);
+  }
+}
+
+// One BaselineSolver step of the twin (src/baseline_solver.py:80-101), cell i =
+// lane: fv_run_small_kernel's loop body.  row: NX doubles private to this wave
+// (spectral: rho as float; tridiagonal: the cyclic-reduction row).
+template <int NX>
+__device__ __forceinline__ void twin_step(TwinCell &tw, double *row, const double *s_c, int i, const ScoreArgs &sc,
+                                          double h) {
+  const bool on = i < NX;
+  const int im = i == 0 ? NX - 1 : i - 1, ip = i >= NX - 1 ? 0 : i + 1;
+  float *rho = reinterpret_cast<float *>(row);
+  const float F = __fmul_rn(tw.n, tw.u);  // F_n = n*u (:70-71)
+  const float um = __shfl(tw.u, im, 64), up = __shfl(tw.u, ip, 64), Fm = __shfl(F, im, 64);
+  const float n_new = continuity(tw.n, F, Fm, sc.c);
+  const float u_new = velocity_classical(tw.u, um, up, tw.E, sc.c, sc.dt, sc.nu, sc.dx2);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the previous step's row reads are done
+  if (sc.tri) {
+    if (on) row[i] = (double)__fsub_rn(n_new, 1.0f);
+  } else if (on) {
+    rho[i] = __fsub_rn(n_new, 1.0f);
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // every lane's rho is in LDS
+  // the solves loop over a run-time nx, as in fv_run_small_kernel: unrolled over a
+  // constant NX they hold a whole row in registers (220 VGPRs at NX = 64: one
+  // workgroup per CU instead of two)
+  int nx = NX;
+  asm volatile("" : "+s"(nx));
+  if (sc.tri) tridiag_psi_wave<double>(row, nx, i);
+  const float E_new = !on ? 0.f : sc.tri ? (float)tri_E(row, i, nx, h) : poisson_cell(rho, s_c, i, nx);
+  tw.n = n_new;
+  tw.u = u_new;
+  tw.E = E_new;
+}
+
+// Rows r of the series of one IC.  get(ch): the model's value of channel ch at
+// cell `lane` (called for lane < NX only).  met / mse / met_cl: this row's
+// destinations (NULL: not asked; the twin exists when mse is given).
+template <int NX, class Get>
+__device__ __forceinline__ void score_row(const Get &get, TwinCell &tw, bool first, double *row, const double *s_c,
+                                          int lane, const ScoreArgs &sc, double h, float *met, float *mse,
+                                          float *met_cl) {
+  const bool on = lane < NX;
+  float mv[3] = {0.f, 0.f, 0.f};
+  if (on) {
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) mv[ch] = get(ch);
+  }
+  if (met) {
+    MetricAcc m;
+    m.init();
+    if (on) m.add(mv[0], mv[1], mv[2]);
+    score_store_metrics(m, met, NX, lane);
+  }
+  if (!mse) return;
+  if (first) {
+    tw.n = mv[0], tw.u = mv[1], tw.E = mv[2];
+  } else {
+    twin_step<NX>(tw, row, s_c, lane, sc, h);
+  }
+  const float cv[3] = {tw.n, tw.u, tw.E};
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    double acc = 0.0;
+    if (on) {
+      const double d = (double)mv[ch] - (double)cv[ch];
+      acc += d * d;
+    }
+    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if (lane == 0) {
+      double t = 0.0;
+      t += acc;
+      for (int k = 1; k < kScorePartials; ++k) t += 0.0;
+      mse[ch] = (float)(t / NX);
+    }
+  }
+  if (met_cl) {
+    MetricAcc m;
+    m.init();
+    if (on) m.add(tw.n, tw.u, tw.E);
+    score_store_metrics(m, met_cl, NX, lane);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // PINN rollout in one launch (train_pinn.py:48-61 iterated as
 // evaluate_multi_ic.py:75-81): a workgroup owns 16 ICs for all T steps, with
 // their state and the hidden activations in LDS, and runs every layer as
@@ -349,10 +479,14 @@ __device__ __forceinline__ void pinn_layer(const PinnRows<NT> &wrow, const float
 // LDS index of feature k of IC n in the [k-block][lane][4] order above
 __device__ __forceinline__ int pinn_at(int k, int n) { return (k >> 4) * 256 + (((k >> 2) & 3) * 16 + n) * 4 + (k & 3); }
 
-template <int D, int H>
-__global__ __launch_bounds__(64 * kPinnWaves, 1) void pinn_run_kernel(PinnW w, const float *__restrict__ state0,
-                                                          float *__restrict__ final_state, float *__restrict__ traj,
-                                                          int64_t B, int T) {
+// SCORE (pinn_score_kernel): before each step's first layer (s_state is not
+// written again until the last layer, barriers later) each of the 8 waves
+// scores 2 of the workgroup's 16 ICs, reading s_state through pinn_at; s_c: the
+// spectral plan's row, s_rows: one NX-double row per wave (ScoreArgs above).
+// Without SCORE none of it is compiled: pinn_run_kernel is the body as it was.
+template <int D, int H, bool SCORE>
+__device__ __forceinline__ void pinn_run_body(const PinnW &w, const float *state0, float *final_state, float *traj,
+                                              int64_t B, int T, const ScoreArgs &sc, double *s_c, double *s_rows) {
   static_assert(D % 16 == 0 && H % 16 == 0, "16-feature tiles");
   constexpr int NT = (H / 16 + kPinnWaves - 1) / kPinnWaves;  // output tiles per wave (H >= D)
   static_assert(H >= D, "the widest layer sets the tiles per wave");
@@ -384,7 +518,30 @@ __global__ __launch_bounds__(64 * kPinnWaves, 1) void pinn_run_kernel(PinnW w, c
   float *const s_bias = reinterpret_cast<float *>(s_bias4);
   for (int l = 0; l < L; ++l)
     for (int i = tid; i < (l == L - 1 ? D : H); i += NTH) s_bias[l * H + i] = w.b[l][i];
+  constexpr int NX = D / 3, kPerWave = kPinnIcs / kPinnWaves;  // SCORE: cells per IC, ICs scored per wave
+  [[maybe_unused]] TwinCell tw[kPerWave];
+  [[maybe_unused]] double tri_h = 0.0;
+  if constexpr (SCORE) {
+    static_assert(D % 3 == 0 && NX <= 64 && kPinnIcs % kPinnWaves == 0, "one cell per lane, whole ICs per wave");
+    if (sc.mse && !sc.tri)
+      for (int i = tid; i < NX; i += NTH) s_c[i] = sc.pc[i];
+    if (sc.mse && sc.tri) tri_h = sc.pc[0];
+  }
   __syncthreads();
+  // rows r of the series of this wave's ICs, from s_state (state r)
+  [[maybe_unused]] auto score = [&](int r) {
+    if constexpr (SCORE) {
+#pragma unroll
+      for (int k = 0; k < kPerWave; ++k) {
+        const int n = kPerWave * wave + k;
+        if (b0 + n >= B) continue;  // a missing IC mirrors the last one and writes no row (wave-uniform)
+        const int64_t rr = (b0 + n) * (int64_t)(T + 1) + r;
+        score_row<NX>([&](int ch) { return s_state[pinn_at(ch * NX + lane, n)]; }, tw[k], r == 0, s_rows + wave * NX,
+                      s_c, lane, sc, tri_h, sc.metrics ? sc.metrics + rr * HF_NUM_METRICS : nullptr,
+                      sc.mse ? sc.mse + rr * 3 : nullptr, sc.metrics_cl ? sc.metrics_cl + rr * HF_NUM_METRICS : nullptr);
+      }
+    }
+  };
   // this wave's packed weight rows of layer l: output tiles min(wave + kPinnWaves j, tiles - 1), k-block 0
   auto row = [&](int l) {
     const int tiles = l == L - 1 ? D / 16 : H / 16, kb = l == 0 ? D / 16 : H / 16;
@@ -406,6 +563,7 @@ __global__ __launch_bounds__(64 * kPinnWaves, 1) void pinn_run_kernel(PinnW w, c
       for (int j = 0; j < NT; ++j) wq[kb][j] = *reinterpret_cast<const f4v *>(r0.p[j] + 256 * kb);
   }
   for (int t = 0; t < T; ++t) {
+    if constexpr (SCORE) score(t);
     pinn_layer<D, H / 16, 0, H / 16, NT>(row(0), s_bias, s_state, act0, wave, lane, wq, row(1));
     __syncthreads();
     for (int l = 1; l < L - 1; ++l) {
@@ -427,10 +585,28 @@ __global__ __launch_bounds__(64 * kPinnWaves, 1) void pinn_run_kernel(PinnW w, c
       }
     }
   }
+  if constexpr (SCORE) score(T);
   for (int idx = tid; idx < kPinnIcs * D; idx += NTH) {
     const int n = idx / D, d = idx - n * D;
     if (b0 + n < B) final_state[(b0 + n) * D + d] = s_state[pinn_at(d, n)];
   }
+}
+
+template <int D, int H>
+__global__ __launch_bounds__(64 * kPinnWaves, 1) void pinn_run_kernel(PinnW w, const float *__restrict__ state0,
+                                                          float *__restrict__ final_state, float *__restrict__ traj,
+                                                          int64_t B, int T) {
+  pinn_run_body<D, H, false>(w, state0, final_state, traj, B, T, ScoreArgs{}, nullptr, nullptr);
+}
+
+// the scored form (hf_pinn_run_scored): the same rollout, bit for bit, plus the series of ScoreArgs
+template <int D, int H>
+__global__ __launch_bounds__(64 * kPinnWaves, 1) void pinn_score_kernel(PinnW w, const float *__restrict__ state0,
+                                                            float *__restrict__ final_state,
+                                                            float *__restrict__ traj, int64_t B, int T, ScoreArgs sc) {
+  __shared__ double s_c[D / 3];
+  __shared__ double s_rows[kPinnWaves * (D / 3)];
+  pinn_run_body<D, H, true>(w, state0, final_state, traj, B, T, sc, s_c, s_rows);
 }
 
 // ---------------------------------------------------------------------------
@@ -552,11 +728,16 @@ __global__ void pure_pack_kernel(const float *__restrict__ W, int64_t ld, int ro
 }
 
 constexpr int kPureWG = 2;  // workgroups per CU (launch bounds)
-template <int H, int NC, bool PACKED>
-__global__ __launch_bounds__(64 * (H / 16), kPureWG) void pure_run_kernel(PureW w, const float *__restrict__ state0,
-                                                                    float *__restrict__ final_state,
-                                                                    const float *__restrict__ x,
-                                                                    float *__restrict__ traj, int B, int T) {
+// SCORE (pure_score_kernel): after the barrier that follows the state update
+// (and after the one that follows the load of state0) the last wave scores the
+// state in s_st, which is not written again until the end of the next step,
+// barriers later, while the other waves start the input layer; s_c: the
+// spectral plan's row, s_row: the scoring wave's NX doubles (ScoreArgs above).
+// Without SCORE none of it is compiled: pure_run_kernel is the body as it was.
+template <int H, int NC, bool PACKED, bool SCORE>
+__device__ __forceinline__ void pure_run_body(const PureW &w, const float *state0, float *final_state,
+                                              const float *x, float *traj, int T, const ScoreArgs &sc, double *s_c,
+                                              double *s_row) {
   constexpr int NX = 16 * NC, NTH = 64 * (H / 16);
   __shared__ float s_st[3 * NX];
   __shared__ float s_x[NX];
@@ -574,8 +755,26 @@ __global__ __launch_bounds__(64 * (H / 16), kPureWG) void pure_run_kernel(PureW 
     if (traj) traj[b * ldt + i] = v;
   }
   for (int i = tid; i < NX; i += NTH) s_x[i] = x[i];
+  [[maybe_unused]] TwinCell tw;
+  [[maybe_unused]] double tri_h = 0.0;
+  if constexpr (SCORE) {
+    if (sc.mse && !sc.tri)
+      for (int i = tid; i < NX; i += NTH) s_c[i] = sc.pc[i];
+    if (sc.mse && sc.tri) tri_h = sc.pc[0];
+  }
   __syncthreads();
+  // row r of the series, from s_st (state r), by the last wave
+  [[maybe_unused]] auto score = [&](int r) {
+    if constexpr (SCORE) {
+      if (u != H / 16 - 1) return;
+      const int64_t rr = b * (int64_t)(T + 1) + r;
+      score_row<NX>([&](int ch) { return s_st[ch * NX + lane]; }, tw, r == 0, s_row, s_c, lane, sc, tri_h,
+                    sc.metrics ? sc.metrics + rr * HF_NUM_METRICS : nullptr, sc.mse ? sc.mse + rr * 3 : nullptr,
+                    sc.metrics_cl ? sc.metrics_cl + rr * HF_NUM_METRICS : nullptr);
+    }
+  };
   for (int t = 0; t < T; ++t) {
+    if constexpr (SCORE) score(t);
     // input_mlp: h = tanh(W_in [n, u, E, x] + b_in)
     {
       // on the matrix core: one v_mfma_f32_16x16x4f32 per cell group, A = rows
@@ -688,7 +887,29 @@ __global__ __launch_bounds__(64 * (H / 16), kPureWG) void pure_run_kernel(PureW 
     if (traj)
       for (int i = tid; i < 3 * NX; i += NTH) traj[b * ldt + (int64_t)(t + 1) * 3 * NX + i] = s_st[i];
   }
+  if constexpr (SCORE) score(T);
   for (int i = tid; i < 3 * NX; i += NTH) final_state[b * 3 * NX + i] = s_st[i];
+}
+
+template <int H, int NC, bool PACKED>
+__global__ __launch_bounds__(64 * (H / 16), kPureWG) void pure_run_kernel(PureW w, const float *__restrict__ state0,
+                                                                    float *__restrict__ final_state,
+                                                                    const float *__restrict__ x,
+                                                                    float *__restrict__ traj, int B, int T) {
+  pure_run_body<H, NC, PACKED, false>(w, state0, final_state, x, traj, T, ScoreArgs{}, nullptr, nullptr);
+}
+
+// the scored form (hf_pure_gnn_run_scored): the same rollout, bit for bit, plus the series of ScoreArgs
+// (the launch bounds of the unscored kernel: asking for 4 waves per SIMD makes the compiler spill)
+template <int H, int NC, bool PACKED>
+__global__ __launch_bounds__(64 * (H / 16), kPureWG) void pure_score_kernel(PureW w, const float *__restrict__ state0,
+                                                                      float *__restrict__ final_state,
+                                                                      const float *__restrict__ x,
+                                                                      float *__restrict__ traj, int B, int T,
+                                                                      ScoreArgs sc) {
+  __shared__ double s_c[16 * NC];
+  __shared__ double s_row[16 * NC];
+  pure_run_body<H, NC, PACKED, true>(w, state0, final_state, x, traj, T, sc, s_c, s_row);
 }
 
 bool pure_fused_ok(int H, int nx) { return (H == 64 || H == 128) && nx % 16 == 0 && nx >= 16 && nx <= 64; }
@@ -706,12 +927,23 @@ void pure_fused_launch(const PureW &w, const float *state0, float *final_state, 
     default: hipLaunchKernelGGL((pure_run_kernel<H, 4, PACKED>), dim3(B), dim3(64 * (H / 16)), 0, s, w, state0, final_state, x, traj, B, T); break;
   }
 }
+template <int H, bool PACKED>
+void pure_score_launch(const PureW &w, const float *state0, float *final_state, const float *x, int B, int nx, int T,
+                       float *traj, const ScoreArgs &sc, hipStream_t s) {
+  switch (nx / 16) {
+    case 1: hipLaunchKernelGGL((pure_score_kernel<H, 1, PACKED>), dim3(B), dim3(64 * (H / 16)), 0, s, w, state0, final_state, x, traj, B, T, sc); break;
+    case 2: hipLaunchKernelGGL((pure_score_kernel<H, 2, PACKED>), dim3(B), dim3(64 * (H / 16)), 0, s, w, state0, final_state, x, traj, B, T, sc); break;
+    case 3: hipLaunchKernelGGL((pure_score_kernel<H, 3, PACKED>), dim3(B), dim3(64 * (H / 16)), 0, s, w, state0, final_state, x, traj, B, T, sc); break;
+    default: hipLaunchKernelGGL((pure_score_kernel<H, 4, PACKED>), dim3(B), dim3(64 * (H / 16)), 0, s, w, state0, final_state, x, traj, B, T, sc); break;
+  }
+}
 
 // ws: the packed copy (pure_packed_floats(H, kMaxChainLayers) floats, hf_pure_gnn_run_workspace_bytes),
-// made here from the state-dict-order weights; more layers than that run on nn.Linear's rows
+// made here from the state-dict-order weights; more layers than that run on nn.Linear's rows.
+// sc: the scored form (pure_score_kernel) instead, when given.
 template <int H>
 hipError_t pure_fused_h(const PureW &w0, const float *state0, float *final_state, const float *x, int B, int nx, int T,
-                        float *traj, void *ws, hipStream_t s) {
+                        float *traj, void *ws, hipStream_t s, const ScoreArgs *sc = nullptr) {
   PureW w = w0;
   if (ws && w.L <= kMaxChainLayers) {
     float *packed = static_cast<float *>(ws);
@@ -723,9 +955,11 @@ hipError_t pure_fused_h(const PureW &w0, const float *state0, float *final_state
                        1, (int64_t)0, packed + nl);
     w.w_lp = packed;
     w.w_o1p = packed + nl;
-    pure_fused_launch<H, true>(w, state0, final_state, x, B, nx, T, traj, s);
+    if (sc) pure_score_launch<H, true>(w, state0, final_state, x, B, nx, T, traj, *sc, s);
+    else pure_fused_launch<H, true>(w, state0, final_state, x, B, nx, T, traj, s);
   } else {
-    pure_fused_launch<H, false>(w, state0, final_state, x, B, nx, T, traj, s);
+    if (sc) pure_score_launch<H, false>(w, state0, final_state, x, B, nx, T, traj, *sc, s);
+    else pure_fused_launch<H, false>(w, state0, final_state, x, B, nx, T, traj, s);
   }
   return hipGetLastError();
 }
@@ -767,7 +1001,7 @@ int64_t pinn_packed_floats(int D, int H, int L) {
 }
 
 hipError_t pinn_fused(const PinnW &w0, const float *state0, float *final_state, int64_t B, int T, float *traj,
-                      void *ws, hipStream_t s) {
+                      void *ws, hipStream_t s, const ScoreArgs *sc = nullptr) {
   const int64_t blocks = (B + kPinnIcs - 1) / kPinnIcs;
   if (blocks > 0x7fffffff) return hipErrorInvalidValue;
   PinnW w = w0;
@@ -781,8 +1015,12 @@ hipError_t pinn_fused(const PinnW &w0, const float *state0, float *final_state, 
     w.wp[l] = packed + pk.off[l];
   }
   hipLaunchKernelGGL(pinn_pack_kernel, dim3((unsigned)((pk.off[w.L] + 255) / 256)), dim3(256), 0, s, pk, packed);
-  hipLaunchKernelGGL((pinn_run_kernel<192, 256>), dim3((unsigned)blocks), dim3(64 * kPinnWaves), 0, s, w, state0, final_state,
-                     traj, B, T);
+  if (sc)
+    hipLaunchKernelGGL((pinn_score_kernel<192, 256>), dim3((unsigned)blocks), dim3(64 * kPinnWaves), 0, s, w, state0,
+                       final_state, traj, B, T, *sc);
+  else
+    hipLaunchKernelGGL((pinn_run_kernel<192, 256>), dim3((unsigned)blocks), dim3(64 * kPinnWaves), 0, s, w, state0, final_state,
+                       traj, B, T);
   return hipGetLastError();
 }
 
@@ -896,6 +1134,53 @@ hipError_t launch_pinn_run(const float *params, int D, int H, int L, const float
     cur = nxt;
   }
   return hipSuccess;
+}
+
+// ---- scored rollouts (hf_pure_gnn_run_scored / hf_pinn_run_scored) ----------
+bool pure_score_fused(int H, int nx) { return pure_fused_ok(H, nx); }
+bool pinn_score_fused(int D, int H) { return pinn_fused_ok(D, H, 2); }
+
+int64_t score_traj_bytes(int64_t B, int T, int64_t S) {  // -1: more than 2^60 bytes
+  const unsigned __int128 n = (unsigned __int128)sizeof(float) * (uint64_t)B * (uint64_t)((int64_t)T + 1) * (uint64_t)S;
+  return n > ((unsigned __int128)1 << 60) ? -1 : (int64_t)a256((size_t)n);
+}
+int64_t score_state_bytes(int64_t B, int64_t S) { return (int64_t)a256(sizeof(float) * B * S); }
+
+// fused shapes: the unscored rollout's workspace; otherwise that (rounded up),
+// the model's and the classical trajectory and the classical final state
+int64_t pure_score_ws_bytes(int H, int B, int nx, int T) {
+  const int64_t run = pure_gnn_run_ws_bytes(H, B, nx, T);
+  if (B == 0 || pure_score_fused(H, nx)) return run;
+  const int64_t tb = score_traj_bytes(B, T, 3LL * nx);
+  if (tb < 0 || run < 0 || run > (int64_t(1) << 60)) return -1;
+  return (int64_t)a256(run) + 2 * tb + score_state_bytes(B, 3LL * nx);
+}
+int64_t pinn_score_ws_bytes(int D, int H, int64_t B, int T) {
+  const int64_t run = pinn_run_ws_bytes(D, H, B);
+  if (B == 0 || pinn_score_fused(D, H)) return run;
+  const int64_t tb = score_traj_bytes(B, T, D);
+  if (tb < 0 || run < 0 || run > (int64_t(1) << 60)) return -1;
+  return (int64_t)a256(run) + 2 * tb + score_state_bytes(B, D);
+}
+
+// One launch (pure_score_fused shapes, any T >= 0; ws: the packed weights or NULL).
+hipError_t launch_pure_gnn_score(const float *params, int H, int L, const float *state0, float *final_state,
+                                 const float *x, const double *pc, int tri, int B, int nx, int T, float c, float dt,
+                                 float nu, float dx2, float *traj, float *metrics, float *mse, float *metrics_cl,
+                                 void *ws, hipStream_t s) {
+  const PureW w = pure_view(params, 4, H, L);
+  const ScoreArgs sc{metrics, mse, metrics_cl, pc, tri, c, dt, nu, dx2};
+  if (T == 0) ws = nullptr;  // no step reads a weight: nothing to pack
+  return H == 64 ? pure_fused_h<64>(w, state0, final_state, x, B, nx, T, traj, ws, s, &sc)
+                 : pure_fused_h<128>(w, state0, final_state, x, B, nx, T, traj, ws, s, &sc);
+}
+
+// One launch (pinn_fused_ok shapes, any T >= 0; ws: the packed weights).
+hipError_t launch_pinn_score(const float *params, int D, int H, int L, const float *state0, float *final_state,
+                             const double *pc, int tri, int64_t B, int T, float c, float dt, float nu, float dx2,
+                             float *traj, float *metrics, float *mse, float *metrics_cl, void *ws, hipStream_t s) {
+  const ScoreArgs sc{metrics, mse, metrics_cl, pc, tri, c, dt, nu, dx2};
+  return pinn_fused(pinn_view(params, D, H, L), state0, final_state, B, T, traj, ws, s, &sc);
 }
 
 }  // namespace hf

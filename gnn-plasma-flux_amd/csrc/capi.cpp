@@ -1317,6 +1317,129 @@ int hf_traj_mse(const float *a, const float *b, int B, int T1, int nx, float *ms
   return HF_OK;
 }
 
+// ------------------------------------------- scored PureGNN / PINN rollouts
+// evaluate_multi_ic.py:21-94 ('pure_gnn', 'pinn') and evaluate_long_rollout.py:18-81.
+}  // extern "C"
+
+namespace {
+
+// The checks the two scored entry points share, all before any device call.
+// need: hf_*_score_workspace_bytes of the shape.
+int score_args(const char *fn, const void *params, const void *state0, const void *final_state, const double *pc,
+               int pm, int nx, int64_t B, const float *metrics, const float *mse, const float *metrics_cl,
+               const void *ws, int64_t ws_bytes, int64_t need) {
+  const std::string f(fn);
+  if (int rc = check_mode(pm, nx, fn)) return rc;
+  if (!metrics && !mse) return fail(HF_EINVAL, f + ": nothing to score (dev_metrics and dev_mse are both NULL)");
+  if (metrics_cl && !mse)
+    return fail(HF_EINVAL, f + ": dev_metrics_classical needs dev_mse (the classical twin runs when dev_mse is given)");
+  if (B == 0) return HF_OK;
+  if (!params || !state0 || !final_state || (mse && !pc)) return fail(HF_EINVAL, f + ": NULL pointer");
+  if (need < 0) return fail(HF_EINVAL, f + ": bad shape");
+  if (need > 0 && (!ws || ws_bytes < need))
+    return fail(HF_EINVAL, f + ": workspace smaller than the score workspace bytes of this shape");
+  return HF_OK;
+}
+
+// Shapes without a one-launch kernel: the model's rollout into a trajectory
+// (the caller's, or one in the workspace), the classical hf_run into a second,
+// then hf_traj_metrics and hf_traj_mse — hf_run_compare's generic sequence.
+// The classical rollout goes first: state_final may alias state0, and the
+// model's rollout is the one that writes it.  run_model(traj, model_ws).
+template <class RunModel>
+int score_sequenced(const char *fn, const RunModel &run_model, const float *state0, const double *pc, int pm, int B,
+                    int nx, int T, float c, float dt, float nu, float dx2, float *traj, float *metrics, float *mse,
+                    float *metrics_cl, void *ws, int64_t model_ws_bytes, void *stream) {
+  if ((int64_t)B * (T + 1) > 0x7fffffffLL) return fail(HF_EUNSUPPORTED, std::string(fn) + ": > 2^31 states");
+  hipStream_t s = as_stream(stream);
+  const int64_t S = 3LL * nx, tb = hf::score_traj_bytes(B, T, S);
+  char *p = static_cast<char *>(ws) + (model_ws_bytes + 255) / 256 * 256;
+  float *tm = traj ? traj : reinterpret_cast<float *>(p);
+  float *tc = reinterpret_cast<float *>(p + tb), *fin_c = reinterpret_cast<float *>(p + 2 * tb);
+  if (mse) {
+    int rc = hf_run_ex(nullptr, state0, fin_c, nullptr, pc, pm, B, nx, T, c, dt, nu, dx2, tc, nullptr, metrics_cl,
+                       nullptr, 0, stream);
+    if (rc != HF_OK) return rc;
+  }
+  HF_CHECK_HIP(run_model(tm, model_ws_bytes > 0 ? ws : nullptr), fn);
+  if (metrics)
+    HF_CHECK_HIP(hf::launch_state_metrics(tm, S, B * (T + 1), nx, metrics, HF_NUM_METRICS, s), fn);
+  if (mse) HF_CHECK_HIP(hf::launch_traj_mse(tm, tc, B, T + 1, nx, mse, s), fn);
+  return HF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t hf_pure_gnn_score_workspace_bytes(int hidden, int B, int nx, int T) {
+  if (hidden < 1 || B < 0 || nx < 1 || T < 0) return -1;
+  return hf::pure_score_ws_bytes(hidden, B, nx, T);
+}
+
+int hf_pure_gnn_run_scored(const float *params, int hidden, int layers, const float *state0, float *final_state,
+                           const float *x, const double *pc, int pm, int B, int nx, int T, float c, float dt, float nu,
+                           float dx2, float *traj, float *metrics, float *mse, float *metrics_cl, void *ws,
+                           int64_t ws_bytes, void *stream) {
+  const char *fn = "hf_pure_gnn_run_scored";
+  if (hidden < 1 || layers < 0 || B < 0 || nx < 1 || T < 0) return fail(HF_EINVAL, std::string(fn) + ": bad argument");
+  const int64_t need = hf::pure_score_ws_bytes(hidden, B, nx, T);
+  if (int rc = score_args(fn, params, state0, final_state, pc, pm, nx, B, metrics, mse, metrics_cl, ws, ws_bytes, need))
+    return rc;
+  if (B == 0) return HF_OK;
+  if (!x) return fail(HF_EINVAL, std::string(fn) + ": NULL pointer");
+  hipStream_t s = as_stream(stream);
+  if (hf::pure_score_fused(hidden, nx)) {
+    HF_CHECK_HIP(hf::launch_pure_gnn_score(params, hidden, layers, state0, final_state, x, pc,
+                                           pm == HF_POISSON_TRIDIAG, B, nx, T, c, dt, nu, dx2, traj, metrics, mse,
+                                           metrics_cl, ws, s),
+                 fn);
+    return HF_OK;
+  }
+  const int64_t mws = hf::pure_gnn_run_ws_bytes(hidden, B, nx, T);
+  return score_sequenced(
+      fn,
+      [&](float *tr, void *w) {
+        return hf::launch_pure_gnn_run(params, hidden, layers, state0, final_state, x, B, nx, T, tr, w, s);
+      },
+      state0, pc, pm, B, nx, T, c, dt, nu, dx2, traj, metrics, mse, metrics_cl, ws, mws, stream);
+}
+
+int64_t hf_pinn_score_workspace_bytes(int dim, int hidden, int64_t B, int T) {
+  if (dim < 1 || dim % 3 != 0 || hidden < 1 || B < 0 || T < 0) return -1;
+  return hf::pinn_score_ws_bytes(dim, hidden, B, T);
+}
+
+int hf_pinn_run_scored(const float *params, int dim, int hidden, int layers, const float *state0, float *final_state,
+                       const double *pc, int pm, int64_t B, int T, float c, float dt, float nu, float dx2,
+                       float *traj, float *metrics, float *mse, float *metrics_cl, void *ws, int64_t ws_bytes,
+                       void *stream) {
+  const char *fn = "hf_pinn_run_scored";
+  if (int rc = pinn_args(fn, dim, hidden, layers, B)) return rc;
+  if (T < 0) return fail(HF_EINVAL, std::string(fn) + ": T < 0");
+  if (dim % 3 != 0) return fail(HF_EINVAL, std::string(fn) + ": dim must be 3 * nx");
+  const int nx = dim / 3;
+  const int64_t need = hf::pinn_score_ws_bytes(dim, hidden, B, T);
+  if (int rc = score_args(fn, params, state0, final_state, pc, pm, nx, B, metrics, mse, metrics_cl, ws, ws_bytes, need))
+    return rc;
+  if (B == 0) return HF_OK;
+  hipStream_t s = as_stream(stream);
+  if (hf::pinn_score_fused(dim, hidden)) {
+    HF_CHECK_HIP(hf::launch_pinn_score(params, dim, hidden, layers, state0, final_state, pc, pm == HF_POISSON_TRIDIAG,
+                                       B, T, c, dt, nu, dx2, traj, metrics, mse, metrics_cl, ws, s),
+                 fn);
+    return HF_OK;
+  }
+  if (B > 0x7fffffffLL) return fail(HF_EUNSUPPORTED, std::string(fn) + ": > 2^31 ICs on a shape without a one-launch kernel");
+  const int64_t mws = hf::pinn_run_ws_bytes(dim, hidden, B);
+  return score_sequenced(
+      fn,
+      [&](float *tr, void *w) {
+        return hf::launch_pinn_run(params, dim, hidden, layers, state0, final_state, B, T, tr, w, s);
+      },
+      state0, pc, pm, (int)B, nx, T, c, dt, nu, dx2, traj, metrics, mse, metrics_cl, ws, mws, stream);
+}
+
 int hf_rollout_summary(const float *metrics, const float *mse, const float *metrics_ref, int B, int T,
                        float *summary, float *drift, void *stream) {
   if (B < 0 || T < 0) return fail(HF_EINVAL, "hf_rollout_summary: need B >= 0, T >= 0");

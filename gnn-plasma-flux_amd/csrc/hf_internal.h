@@ -136,6 +136,27 @@ hipError_t launch_pinn_forward(const float *params, int D, int H, int L, const f
 hipError_t launch_pinn_run(const float *params, int D, int H, int L, const float *state0, float *final_state,
                            int64_t B, int T, float *traj, void *ws, hipStream_t s);
 
+// Scored rollouts of the comparison models (baselines.hip pure_score_kernel /
+// pinn_score_kernel): the rollout above in one launch that also writes the
+// metric series [B][T+1][HF_NUM_METRICS], steps a classical twin of every IC
+// when mse [B][T+1][3] is given and scores the model against it per step
+// (metrics_cl: the twin's own series).  Fused shapes only (pure_score_fused /
+// pinn_score_fused; any T >= 0, nx <= 64); capi.cpp sequences the existing
+// kernels on the others.  tri: the twin's Poisson mode is HF_POISSON_TRIDIAG.
+bool pure_score_fused(int H, int nx);
+bool pinn_score_fused(int D, int H);
+int64_t score_traj_bytes(int64_t B, int T, int64_t S);  // one [B][T+1][S] float trajectory, 256-aligned
+int64_t score_state_bytes(int64_t B, int64_t S);
+int64_t pure_score_ws_bytes(int H, int B, int nx, int T);
+int64_t pinn_score_ws_bytes(int D, int H, int64_t B, int T);
+hipError_t launch_pure_gnn_score(const float *params, int H, int L, const float *state0, float *final_state,
+                                 const float *x, const double *pc, int tri, int B, int nx, int T, float c, float dt,
+                                 float nu, float dx2, float *traj, float *metrics, float *mse, float *metrics_cl,
+                                 void *ws, hipStream_t s);
+hipError_t launch_pinn_score(const float *params, int D, int H, int L, const float *state0, float *final_state,
+                             const double *pc, int tri, int64_t B, int T, float c, float dt, float nu, float dx2,
+                             float *traj, float *metrics, float *mse, float *metrics_cl, void *ws, hipStream_t s);
+
 // PureGNN training (pure_train.hip): the forward that keeps a tape, the
 // backward, and the fused state-MSE loss with its gradient.  layers <= kMaxChainLayers.
 int64_t pure_tape_bytes(int H, int L, int64_t N, int64_t E);

@@ -95,6 +95,14 @@ SIGNATURES = {
                                c_void_p]),
     "hf_traj_metrics": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "hf_traj_mse": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "hf_pure_gnn_score_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
+    "hf_pure_gnn_run_scored": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                       c_int, c_int, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_int64, c_void_p]),
+    "hf_pinn_score_workspace_bytes": (c_int64, [c_int, c_int, c_int64, c_int]),
+    "hf_pinn_run_scored": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int,
+                                   c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_int64, c_void_p]),
     "hf_rollout_summary": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "hf_ablation_loss_workspace_bytes": (c_int64, [c_int, c_int]),
     "hf_ablation_loss_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_void_p,

@@ -26,7 +26,7 @@ import torch
 import torch.nn as nn
 
 from . import engine
-from ._lib import check, lib, ptr
+from ._lib import HF_NUM_METRICS, check, lib, ptr
 from .flux_gnn import _flat_view
 
 
@@ -52,6 +52,27 @@ class _Flat:
             self.buf = _flat(module).to(device)
             self.sig = sig
         return self.buf
+
+
+def _score_buffers(B, T, dev, metrics, compare):
+    """The series a scored rollout writes (compare_batch's keys): metrics
+    [B,T+1,4] when asked, mse [B,T+1,3] and metrics_classical (with metrics)
+    when a BaselineSolver to compare with is given; None otherwise."""
+    me = torch.empty(B, T + 1, HF_NUM_METRICS, device=dev) if metrics else None
+    mse = torch.empty(B, T + 1, 3, device=dev) if compare is not None else None
+    mc = torch.empty(B, T + 1, HF_NUM_METRICS, device=dev) if (compare is not None and metrics) else None
+    return me, mse, mc
+
+
+def _score_grid(compare, nx, dev):
+    """Grid constants of the classical twin: (plan, pmode, c, dt, nu, dx2).
+    Without a solver to compare with no twin runs and they are unused."""
+    if compare is None:
+        return None, 0, 0.0, 0.0, 0.0, 0.0
+    g = compare.grid
+    if g.nx != nx:
+        raise ValueError(f"compare: the solver's grid has nx = {g.nx}, the states {nx}")
+    return g.on(dev)[1], g.pmode, g.c32, g.dt32, g.nu32, g.dx2_32
 
 
 class _PureTrainForward(torch.autograd.Function):
@@ -134,9 +155,16 @@ class PureGNN(nn.Module):
                 o += q.numel()
         return self
 
-    def rollout(self, states0, n_steps, x, traj=True):
+    def rollout(self, states0, n_steps, x, traj=True, *, metrics=False, compare=None):
         """B ICs [B,3,nx] (device) -> dict(final [B,3,nx], traj [B,T+1,3,nx] or None);
-        the loop of evaluate_multi_ic.py:53-64 with node features [n,u,E,x]."""
+        the loop of evaluate_multi_ic.py:53-64 with node features [n,u,E,x].
+
+        metrics=True and / or compare=<BaselineSolver> run the scored rollout
+        (hf_pure_gnn_run_scored) instead: the same final and traj, and the dict
+        also holds compare_batch's keys, metrics [B,T+1,4], mse [B,T+1,3]
+        against the classical solver stepped from the same ICs on compare's
+        grid (dt, nu, Poisson mode) and metrics_classical [B,T+1,4] (None
+        where not asked), written by the rollout kernel itself."""
         if self.input_dim != 4:
             raise ValueError("rollout builds [n,u,E,x] node features: input_dim must be 4")
         engine.require_device(states0, "states0")
@@ -145,7 +173,18 @@ class PureGNN(nn.Module):
         xd = torch.as_tensor(x, dtype=torch.float32, device=s0.device).contiguous()
         final = torch.empty_like(s0)
         tr = torch.empty(B, n_steps + 1, 3, nx, device=s0.device) if traj else None
-        N = B * nx
+        if metrics or compare is not None:
+            T = int(n_steps)
+            me, mse, mc = _score_buffers(B, T, s0.device, metrics, compare)
+            plan, pmode, c, dt, nu, dx2 = _score_grid(compare, nx, s0.device)
+            nb = int(lib().hf_pure_gnn_score_workspace_bytes(self.hidden_dim, B, nx, T))
+            ws = torch.empty(nb, dtype=torch.uint8, device=s0.device) if nb > 0 else None
+            with torch.no_grad(), torch.cuda.device(s0.device):
+                check(lib().hf_pure_gnn_run_scored(ptr(self._flat.get(self, s0.device)), self.hidden_dim,
+                                                   self.num_layers, ptr(s0), ptr(final), ptr(xd), ptr(plan), pmode,
+                                                   B, nx, T, c, dt, nu, dx2, ptr(tr), ptr(me), ptr(mse), ptr(mc),
+                                                   ptr(ws), max(nb, 0), engine.stream_of(s0.device)))
+            return {"final": final, "traj": tr, "metrics": me, "mse": mse, "metrics_classical": mc}
         nb = int(lib().hf_pure_gnn_run_workspace_bytes(self.hidden_dim, B, nx, int(n_steps)))
         ws = torch.empty(nb, dtype=torch.uint8, device=s0.device) if nb > 0 else None
         with torch.no_grad(), torch.cuda.device(s0.device):
@@ -185,8 +224,9 @@ class PINN(nn.Module):
                                         engine.stream_of(s.device)))
         return out.reshape(state.shape).to(state.device)
 
-    def rollout(self, states0, n_steps, traj=True):
-        """B ICs [B,3,nx] -> dict(final, traj [B,T+1,3,nx] or None) (evaluate_multi_ic.py:75-81)."""
+    def rollout(self, states0, n_steps, traj=True, *, metrics=False, compare=None):
+        """B ICs [B,3,nx] -> dict(final, traj [B,T+1,3,nx] or None) (evaluate_multi_ic.py:75-81).
+        metrics / compare: the scored rollout (hf_pinn_run_scored), as PureGNN.rollout."""
         engine.require_device(states0, "states0")
         s0 = states0.to(torch.float32).contiguous()
         B = s0.shape[0]
@@ -194,6 +234,18 @@ class PINN(nn.Module):
             raise ValueError(f"states0 must hold {self.input_dim} values per IC")
         final = torch.empty_like(s0)
         tr = torch.empty((B, n_steps + 1) + tuple(s0.shape[1:]), device=s0.device) if traj else None
+        if metrics or compare is not None:
+            T = int(n_steps)
+            me, mse, mc = _score_buffers(B, T, s0.device, metrics, compare)
+            plan, pmode, c, dt, nu, dx2 = _score_grid(compare, self.input_dim // 3, s0.device)
+            nb = int(lib().hf_pinn_score_workspace_bytes(self.input_dim, self.hidden_dim, B, T))
+            ws = torch.empty(nb, dtype=torch.uint8, device=s0.device) if nb > 0 else None
+            with torch.no_grad(), torch.cuda.device(s0.device):
+                check(lib().hf_pinn_run_scored(ptr(self._flat.get(self, s0.device)), self.input_dim, self.hidden_dim,
+                                               self.num_layers, ptr(s0), ptr(final), ptr(plan), pmode, B, T, c, dt,
+                                               nu, dx2, ptr(tr), ptr(me), ptr(mse), ptr(mc), ptr(ws), max(nb, 0),
+                                               engine.stream_of(s0.device)))
+            return {"final": final, "traj": tr, "metrics": me, "mse": mse, "metrics_classical": mc}
         nb = int(lib().hf_pinn_workspace_bytes(self.input_dim, self.hidden_dim, B))
         ws = torch.empty(nb, dtype=torch.uint8, device=s0.device) if nb > 0 else None
         with torch.no_grad(), torch.cuda.device(s0.device):

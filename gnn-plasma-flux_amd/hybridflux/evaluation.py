@@ -7,10 +7,16 @@ hf_rollout_summary), so a sharded multi-GPU job can gather them.
   compute_metrics(states_pred, states_true)   scripts/evaluation/evaluate_all.py:118-159
   multi_ic_mse(solver, states0, n_steps)      scripts/evaluation/evaluate_multi_ic.py:21-94
   long_rollout(solver, states0, n_steps)      scripts/evaluation/evaluate_long_rollout.py:18-81
+  compare_models(models, states0, n_steps)    scripts/evaluation/evaluate_multi_ic.py:97-136
+
+`solver` is a HybridSolver or a ModelRollout, the adapter that gives the
+comparison models (PureGNN, PINN: evaluate_multi_ic.py:45-83) the same
+compare_batch / run_batch, scored inside their one-launch rollouts.
 """
 import torch
 
 from . import engine
+from .baselines import PureGNN
 
 SUMMARY_FIELDS = ("exploded_at", "actual_steps", "final_energy_drift", "final_charge_drift", "final_mse",
                   "mean_mse", "final_energy_drift_true", "final_charge_drift_true")
@@ -39,6 +45,60 @@ def compute_metrics(states_pred, states_true):
         # at the last finite step, which is T unless the rollout exploded
         "final_energy_drift": drift[:, -1, 0], "final_charge_drift": drift[:, -1, 1],
     }
+
+
+class ModelRollout:
+    """A PureGNN or PINN with the batched scoring API of HybridSolver:
+    compare_batch and run_batch on the scored rollouts (PureGNN.rollout /
+    PINN.rollout with metrics= / compare=), so multi_ic_mse, long_rollout,
+    compare_models and rollout.gather_rollout take it unchanged.  `baseline` is
+    the BaselineSolver whose grid gives the classical twin its dt, nu and
+    Poisson mode; x (PureGNN's node coordinate) defaults to that grid's cell
+    centres (evaluate_multi_ic.py:49)."""
+
+    def __init__(self, model, baseline, x=None):
+        self.model, self.baseline = model, baseline
+        self.x = baseline.grid.x if x is None else x
+        self._takes_x = isinstance(model, PureGNN)  # PureGNN.rollout(states0, n_steps, x, ...)
+
+    @property
+    def grid(self):
+        return self.baseline.grid
+
+    def _rollout(self, states0, n_steps, **kw):
+        s0 = self.baseline._upload(states0)
+        if self._takes_x:
+            return self.model.rollout(s0, n_steps, self.x, **kw)
+        return self.model.rollout(s0, n_steps, **kw)
+
+    def compare_batch(self, states0, n_steps, metrics=True):
+        """dict(final, mse [B,T+1,3], metrics, metrics_classical): HybridSolver.compare_batch's."""
+        r = self._rollout(states0, n_steps, traj=False, metrics=metrics, compare=self.baseline)
+        return {k: r[k] for k in ("final", "mse", "metrics", "metrics_classical")}
+
+    def run_batch(self, states0, n_steps, traj=True, flux=False, metrics=False):
+        """dict(final, traj, flux (always None), metrics): HybridSolver.run_batch's."""
+        if flux:
+            raise ValueError("ModelRollout.run_batch: these models predict the state change, not a face flux")
+        r = self._rollout(states0, n_steps, traj=traj, metrics=metrics)
+        return {"final": r["final"], "traj": r["traj"], "flux": None, "metrics": r.get("metrics")}
+
+
+def compare_models(models, states0, n_steps):
+    """evaluate_multi_ic.py:97-136 on the device: every model of `models` (name
+    -> HybridSolver or ModelRollout) rolled out from the same ICs and scored
+    against the classical solver.  Returns {name: {mean_mse, std_mse (python
+    floats, np.mean / np.std over the ICs as :128-136), mse_per_ic (list)}};
+    the one host synchronisation is the copy of all per-IC numbers at the end."""
+    names = list(models)
+    if not names:
+        return {}
+    per_ic = torch.stack([multi_ic_mse(models[k], states0, n_steps)[0] for k in names])  # [M, B], device
+    host = per_ic.to(torch.float64).cpu().numpy()
+    return {k: {"mean_mse": float(host[i].mean()) if host.shape[1] else float("nan"),
+                "std_mse": float(host[i].std()) if host.shape[1] else float("nan"),
+                "mse_per_ic": [float(v) for v in host[i]]}
+            for i, k in enumerate(names)}
 
 
 def multi_ic_mse(solver, states0, n_steps):

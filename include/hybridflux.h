@@ -647,6 +647,49 @@ int hf_traj_mse(const float *dev_traj_a, const float *dev_traj_b, int B, int T1,
                 void *stream);
 
 /*
+ * Scored rollouts of the comparison models.  Replace
+ * scripts/evaluation/evaluate_multi_ic.py:21-94 for model types 'pure_gnn'
+ * (:45-66) and 'pinn' (:70-83) — the model's rollout, BaselineSolver.run from
+ * the same IC (:28-33) and the per-step channel MSE (:88-94) — and the
+ * explosion / energy-drift series of evaluate_long_rollout.py:18-81, for B ICs
+ * in one call: hf_pure_gnn_run / hf_pinn_run (same dev_final and dev_traj, bit
+ * for bit) that also write
+ *   dev_metrics           [B][T+1][HF_NUM_METRICS]  = hf_traj_metrics(model trajectory),
+ *   dev_mse               [B][T+1][3]               = hf_traj_mse(model, classical trajectory),
+ *   dev_metrics_classical [B][T+1][HF_NUM_METRICS]  = hf_run(model = NULL)'s metrics,
+ * each bit for bit, without either trajectory going through memory.  dev_traj,
+ * dev_metrics, dev_mse and dev_metrics_classical may each be NULL; the
+ * classical twin (dt, nu, c = dt/dx, dx2 = dx^2, dev_plan of poisson_mode: the
+ * arguments of hf_run_ex) runs exactly when dev_mse is given.
+ * dev_metrics_classical without dev_mse, and dev_metrics and dev_mse both NULL
+ * (nothing to score), are HF_EINVAL; so are NULL required pointers (dev_plan
+ * is required with dev_mse), negative sizes, an unknown Poisson mode, for PINN
+ * dim % 3 != 0 (nx = dim / 3) or layers outside 2..8, and a workspace_bytes
+ * below hf_*_score_workspace_bytes (-1 on bad arguments) or a NULL workspace
+ * where that is > 0 — all before any device call.  dev_final may alias
+ * dev_state0.
+ *
+ * One launch on PureGNN hidden in {64, 128} with nx in {16, 32, 48, 64} and on
+ * PINN(192, 256, 2..8), any T >= 0: one wave per IC scores the state held in
+ * LDS and keeps the twin in registers; the workspace is what the unscored
+ * rollout needs.  Every other shape sequences the existing kernels (the
+ * model's rollout into a trajectory in the workspace, the classical hf_run
+ * into a second, hf_traj_metrics, hf_traj_mse), as hf_run_compare does for its
+ * generic nx; the workspace holds both trajectories.
+ */
+int64_t hf_pure_gnn_score_workspace_bytes(int hidden, int B, int nx, int T);
+int hf_pure_gnn_run_scored(const float *dev_params, int hidden, int layers, const float *dev_state0,
+                           float *dev_state_final, const float *dev_x, const double *dev_plan, int poisson_mode,
+                           int B, int nx, int T, float c, float dt, float nu, float dx2, float *dev_traj,
+                           float *dev_metrics, float *dev_mse, float *dev_metrics_classical, void *dev_workspace,
+                           int64_t workspace_bytes, void *stream);
+int64_t hf_pinn_score_workspace_bytes(int dim, int hidden, int64_t B, int T);
+int hf_pinn_run_scored(const float *dev_params, int dim, int hidden, int layers, const float *dev_state0,
+                       float *dev_state_final, const double *dev_plan, int poisson_mode, int64_t B, int T, float c,
+                       float dt, float nu, float dx2, float *dev_traj, float *dev_metrics, float *dev_mse,
+                       float *dev_metrics_classical, void *dev_workspace, int64_t workspace_bytes, void *stream);
+
+/*
  * Per-IC summary of a T-step rollout from its metric series (SURVEY.md 8f
  * rank 1; fields at HF_NUM_SUMMARY).  dev_metrics [B][T+1][HF_NUM_METRICS]
  * (required), dev_mse [B][T+1][3] (may be NULL), dev_metrics_ref
