@@ -735,6 +735,79 @@ int hf_pinn_run(const float *params, int dim, int hidden, int layers, const floa
   return HF_OK;
 }
 
+// PINN training (scripts/training/train_pinn.py:48-61 under loss.backward(), :64-111, :156-179)
+constexpr int kPinnTrainMaxDim = 65536;  // with B < 2^31 every buffer size stays far inside int64
+static bool pinn_train_dims_ok(int dim, int hidden, int layers, int64_t B) {
+  return dim >= 1 && hidden >= 1 && dim <= kPinnTrainMaxDim && hidden <= kPinnTrainMaxDim && layers >= 2 &&
+         layers <= hf::kMaxChainLayers && B >= 1 && B <= 0x7fffffffLL;
+}
+
+static int pinn_train_args(const char *fn, int dim, int hidden, int layers, int64_t B) {
+  if (dim < 1 || hidden < 1) return fail(HF_EINVAL, std::string(fn) + ": non-positive model dimensions");
+  if (layers < 2 || layers > hf::kMaxChainLayers) return fail(HF_EINVAL, std::string(fn) + ": need 2 <= layers <= 8");
+  if (B < 1) return fail(HF_EINVAL, std::string(fn) + ": need B >= 1");
+  if (dim > kPinnTrainMaxDim || hidden > kPinnTrainMaxDim || B > 0x7fffffffLL)
+    return fail(HF_EUNSUPPORTED, std::string(fn) + ": dim or hidden > 65536, or B >= 2^31");
+  return HF_OK;
+}
+
+int64_t hf_pinn_tape_bytes(int dim, int hidden, int layers, int64_t B) {
+  if (!pinn_train_dims_ok(dim, hidden, layers, B)) return -1;
+  return hf::pinn_tape_bytes(hidden, layers, B);
+}
+
+int64_t hf_pinn_backward_workspace_bytes(int dim, int hidden, int layers, int64_t B) {
+  if (!pinn_train_dims_ok(dim, hidden, layers, B)) return -1;
+  return hf::pinn_backward_ws_bytes(dim, hidden, layers, B);
+}
+
+int64_t hf_pinn_loss_workspace_bytes(int B, int nx) {
+  if (B < 1 || nx < 1) return -1;
+  return hf::pinn_loss_ws_bytes(B, nx);
+}
+
+int hf_pinn_forward_train(const float *params, int dim, int hidden, int layers, const float *state, int64_t B,
+                          float *out, void *tape, void *stream) {
+  const char *fn = "hf_pinn_forward_train";
+  if (int rc = pinn_train_args(fn, dim, hidden, layers, B)) return rc;
+  if (!params || !state || !out || !tape) return fail(HF_EINVAL, std::string(fn) + ": NULL pointer");
+  if (state == out) return fail(HF_EINVAL, std::string(fn) + ": dev_state and dev_out must not alias");
+  HF_CHECK_HIP(hf::launch_pinn_forward_train(params, dim, hidden, layers, state, B, out, tape, as_stream(stream)), fn);
+  return HF_OK;
+}
+
+int hf_pinn_backward(const float *params, int dim, int hidden, int layers, const float *state, int64_t B,
+                     const void *tape, const float *grad_out, float *grad_params, float *grad_state, void *ws,
+                     int64_t ws_bytes, void *stream) {
+  const char *fn = "hf_pinn_backward";
+  if (int rc = pinn_train_args(fn, dim, hidden, layers, B)) return rc;
+  if (!params || !state || !tape || !grad_out || !grad_params || !ws)
+    return fail(HF_EINVAL, std::string(fn) + ": NULL pointer");
+  if (ws_bytes < hf::pinn_backward_ws_bytes(dim, hidden, layers, B))
+    return fail(HF_EINVAL, std::string(fn) + ": workspace smaller than hf_pinn_backward_workspace_bytes");
+  HF_CHECK_HIP(hf::launch_pinn_backward(params, dim, hidden, layers, state, B, tape, grad_out, grad_params, grad_state,
+                                        ws, as_stream(stream)),
+               fn);
+  return HF_OK;
+}
+
+int hf_pinn_loss(const float *pred, const float *state_t, const float *state_next, int B, int nx, double dt, double dx,
+                 double nu, const float *weights, const double *plan, float *losses, float *grad_pred, void *ws,
+                 int64_t ws_bytes, void *stream) {
+  const char *fn = "hf_pinn_loss";
+  if (B < 1 || nx < 1) return fail(HF_EINVAL, std::string(fn) + ": need B >= 1 and nx >= 1");
+  if (!(dt > 0) || !(dx > 0)) return fail(HF_EINVAL, std::string(fn) + ": need dt > 0 and dx > 0");
+  if (!pred || !state_t || !state_next || !weights || !plan || !losses || !grad_pred || !ws)
+    return fail(HF_EINVAL, std::string(fn) + ": NULL pointer");
+  if (!hf::pinn_loss_nx_ok(nx)) return fail(HF_EUNSUPPORTED, std::string(fn) + ": nx > 6144");
+  if (ws_bytes < hf::pinn_loss_ws_bytes(B, nx))
+    return fail(HF_EINVAL, std::string(fn) + ": workspace smaller than hf_pinn_loss_workspace_bytes");
+  HF_CHECK_HIP(hf::launch_pinn_loss(pred, state_t, state_next, B, nx, dt, dx, nu, weights, plan, losses, grad_pred, ws,
+                                    as_stream(stream)),
+               fn);
+  return HF_OK;
+}
+
 int hf_poisson_plan_len(int nx) { return nx < 1 ? -1 : hf::poisson_plan_len(nx); }
 
 int hf_poisson_coeffs(int nx, double length, double *c) {

@@ -171,6 +171,22 @@ int64_t state_mse_ws_bytes(int B, int nx);
 hipError_t launch_state_mse(const float *delta, const float *st, const float *sn, int B, int nx, float *loss,
                             float *grad_delta, void *ws, hipStream_t s);
 
+// PINN training (pinn_train.hip): the forward that keeps the tanh activations,
+// the backward, and the physics loss with its gradient in one launch.
+// 2 <= layers <= kMaxChainLayers, B >= 1; the loss needs nx <= kFvLdsMaxNx.
+int64_t pinn_tape_bytes(int H, int L, int64_t B);
+int64_t pinn_backward_ws_bytes(int D, int H, int L, int64_t B);
+hipError_t launch_pinn_forward_train(const float *params, int D, int H, int L, const float *state, int64_t B, float *out,
+                                     void *tape, hipStream_t s);
+hipError_t launch_pinn_backward(const float *params, int D, int H, int L, const float *state, int64_t B,
+                                const void *tape, const float *grad_out, float *grad_params, float *grad_state,
+                                void *ws, hipStream_t s);
+bool pinn_loss_nx_ok(int nx);
+int64_t pinn_loss_ws_bytes(int B, int nx);
+hipError_t launch_pinn_loss(const float *pred, const float *st, const float *sn, int B, int nx, double dt, double dx,
+                            double nu, const float *w, const double *pc, float *losses, float *grad_pred, void *ws,
+                            hipStream_t s);
+
 // View of a flat float32 parameter buffer in state-dict order (the host_params
 // order of hf_model_create): update layers interleave weight and bias.
 GraphW graph_view_state_dict(const float *p, int in_dim, int hidden, int layers);

@@ -69,6 +69,14 @@ SIGNATURES = {
     "hf_pinn_forward": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "hf_pinn_run": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p,
                             c_void_p]),
+    "hf_pinn_tape_bytes": (c_int64, [c_int, c_int, c_int, c_int64]),
+    "hf_pinn_backward_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int64]),
+    "hf_pinn_loss_workspace_bytes": (c_int64, [c_int, c_int]),
+    "hf_pinn_forward_train": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "hf_pinn_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_int64, c_void_p]),
+    "hf_pinn_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_double, c_void_p,
+                             c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "hf_poisson_plan_len": (c_int, [c_int]),
     "hf_poisson_coeffs": (c_int, [c_int, c_double, c_void_p]),
     "hf_poisson": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),

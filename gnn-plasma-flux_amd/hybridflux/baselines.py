@@ -19,8 +19,13 @@ the device, backward() runs hf_pure_gnn_backward), so the reference's
 grad enabled (examples/smoke_test.py:98-104) work unchanged; gradients land on
 each tensor's own device, and after flatten_parameters_() the kernels read the
 parameters in place (hybridflux.training.train_pure_gnn, FlatAdam).  Under
-torch.no_grad() the inference kernels run as before.  PINN stays inference
-only: it has no backward kernels, so its forward under autograd raises.
+torch.no_grad() the inference kernels run as before.
+
+PINN.forward is the inference call and still raises under autograd; PINN
+trains through hybridflux.training instead: pinn_forward (the training kernels
+of pinn_train.hip under an autograd Function), pinn_physics_loss, pinn_step
+and train_pinn (scripts/training/train_pinn.py:114-201), with
+PINN.flatten_parameters_() for FlatAdam.
 """
 import torch
 import torch.nn as nn
@@ -223,6 +228,22 @@ class PINN(nn.Module):
                                         self.num_layers, ptr(flat), ptr(out), B, ptr(ws) if ws is not None else None,
                                         engine.stream_of(s.device)))
         return out.reshape(state.shape).to(state.device)
+
+    def flatten_parameters_(self):
+        """Re-home every parameter into one contiguous float32 buffer in
+        state-dict order (PureGNN.flatten_parameters_'s contract: the
+        parameters keep their identity, FlatAdam can drive them, and
+        hybridflux.training.pinn_forward / pinn_step hand the kernels that
+        buffer instead of concatenating the parameters each step).  .to() /
+        .cuda() afterwards undo it."""
+        params = list(self.parameters())
+        flat = torch.cat([q.detach().reshape(-1).to(torch.float32) for q in params])
+        o = 0
+        with torch.no_grad():
+            for q in params:
+                q.data = flat[o:o + q.numel()].view(q.shape)
+                o += q.numel()
+        return self
 
     def rollout(self, states0, n_steps, traj=True, *, metrics=False, compare=None):
         """B ICs [B,3,nx] -> dict(final, traj [B,T+1,3,nx] or None) (evaluate_multi_ic.py:75-81).

@@ -420,6 +420,96 @@ def state_mse(delta, state_t, state_next):
     return loss, gd
 
 
+def _pinn_dims(dims, B):
+    dim, hidden, layers = dims
+    nb = int(lib().hf_pinn_tape_bytes(dim, hidden, layers, B))
+    if nb < 0:
+        raise ValueError(f"PINN training needs B >= 1, positive dims and 2..8 layers (B = {B}, dims = {dims})")
+    return dim, hidden, layers, nb
+
+
+def pinn_forward_train(params, dims, state):
+    """PINN's training forward (hf_pinn_forward_train): params is the flat
+    float32 device buffer in state-dict order, state [B, dim] float32 on its
+    device.  Returns (out [B, dim] = state + net(state), tape)."""
+    require_device(state, "state")
+    if state.dtype != torch.float32 or state.dim() != 2 or state.shape[1] != dims[0] or not state.is_contiguous():
+        raise ValueError(f"pinn_forward_train: state must be contiguous float32 [B,{dims[0]}], got "
+                         f"{tuple(state.shape)} {state.dtype}")
+    if params.device != state.device:
+        raise RuntimeError(f"PINN parameters on {params.device} but the state on {state.device}")
+    B = state.shape[0]
+    dim, hidden, layers, nb = _pinn_dims(dims, B)
+    out = torch.empty_like(state)
+    tape = torch.empty(nb, dtype=torch.uint8, device=state.device)
+    with torch.cuda.device(state.device):
+        check(lib().hf_pinn_forward_train(ptr(params), dim, hidden, layers, ptr(state), B, ptr(out), ptr(tape),
+                                          stream_of(state.device)))
+    return out, tape
+
+
+def pinn_backward(params, dims, state, tape, grad_out, want_state_grad, grad_params=None):
+    """hf_pinn_backward: (d params flat [P], d state [B, dim] or None).
+    grad_params: a preallocated flat buffer to overwrite."""
+    dim, hidden, layers = dims
+    B = state.shape[0]
+    g = grad_out.detach().to(device=state.device, dtype=torch.float32).contiguous()
+    if g.numel() != state.numel():
+        raise ValueError(f"pinn_backward: grad_out must hold {B} x {dim} values, got {tuple(g.shape)}")
+    gp = torch.empty_like(params) if grad_params is None else grad_params
+    gs = torch.empty_like(state) if want_state_grad else None
+    nb = int(lib().hf_pinn_backward_workspace_bytes(dim, hidden, layers, B))
+    ws = torch.empty(nb, dtype=torch.uint8, device=state.device)
+    with torch.cuda.device(state.device):
+        check(lib().hf_pinn_backward(ptr(params), dim, hidden, layers, ptr(state), B, ptr(tape), ptr(g), ptr(gp),
+                                     ptr(gs), ptr(ws), nb, stream_of(state.device)))
+    return gp, gs
+
+
+_PINN_PLANS = {}
+
+
+def pinn_loss_plan(nx, length, device):
+    """The spectral Poisson plan hf_pinn_loss reads (hf_poisson_coeffs(nx,
+    length)) on device, cached per (nx, length, device)."""
+    key = (int(nx), float(length), str(device))
+    pc = _PINN_PLANS.get(key)
+    if pc is None:
+        host = np.empty(lib().hf_poisson_plan_len(int(nx)), dtype=np.float64)
+        check(lib().hf_poisson_coeffs(int(nx), float(length), host.ctypes.data_as(c_void_p)))
+        pc = _PINN_PLANS[key] = torch.from_numpy(host).to(device)
+    return pc
+
+
+def pinn_loss(pred, state_t, state_next, dx, dt, nu, weights, length=None):
+    """hf_pinn_loss: (losses [5] = (loss, data, cont, mom, pois), d loss / d pred
+    [B,3,nx]) of the PINN trainer's loss (train_pinn.py:64-111, :163-175) for
+    pred, state_t, state_next [B,3,nx]; pred on the device, the states staged
+    to it.  length: the domain length of the Poisson operator (default nx dx)."""
+    require_device(pred, "pred")
+    p = pred.detach().to(torch.float32).contiguous()
+    st = state_t.detach().to(device=p.device, dtype=torch.float32).contiguous()
+    sn = state_next.detach().to(device=p.device, dtype=torch.float32).contiguous()
+    if p.dim() != 3 or p.shape[1] != 3 or st.shape != p.shape or sn.shape != p.shape:
+        raise ValueError(f"pinn_loss: pred, state_t, state_next must be [B,3,nx], got {tuple(p.shape)}, "
+                         f"{tuple(st.shape)}, {tuple(sn.shape)}")
+    B, _, nx = p.shape
+    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1))
+    if w.size != 4:
+        raise ValueError("pinn_loss: weights must be (w_data, w_continuity, w_momentum, w_poisson)")
+    nb = int(lib().hf_pinn_loss_workspace_bytes(B, nx))
+    if nb < 0:
+        raise ValueError(f"pinn_loss: need B >= 1, nx >= 1 (B = {B}, nx = {nx})")
+    pc = pinn_loss_plan(nx, nx * float(dx) if length is None else length, p.device)
+    losses = torch.empty(5, device=p.device)
+    gp = torch.empty_like(p)
+    ws = torch.empty(nb, dtype=torch.uint8, device=p.device)
+    with torch.cuda.device(p.device):
+        check(lib().hf_pinn_loss(ptr(p), ptr(st), ptr(sn), B, nx, float(dt), float(dx), float(nu), ptr(w), ptr(pc),
+                                 ptr(losses), ptr(gp), ptr(ws), nb, stream_of(p.device)))
+    return losses, gp
+
+
 def poisson(grid, n):
     """Poisson E for densities n [B,nx]: the grid's mode (spectral: src/baseline_solver.py:59-68)."""
     require_device(n, "n")

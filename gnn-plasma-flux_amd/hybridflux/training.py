@@ -29,6 +29,10 @@ unrolled_step / train_unrolled for FluxGNN through the hybrid solver
 (unroll.hip), pure_unrolled_loss / pure_unrolled_step /
 train_pure_gnn_unrolled for PureGNN through state <- state + PureGNN(...)
 (pure_unroll.hip).
+
+PINN (scripts/training/train_pinn.py:64-201) trains at the end of this module:
+pinn_forward (PINN.forward itself stays inference only), pinn_physics_loss
+(hf_pinn_loss), pinn_step and train_pinn, over pinn_train.hip.
 """
 import json
 import os
@@ -1033,4 +1037,231 @@ def train_pure_gnn_unrolled(trajectories, x, K=4, epochs=10, lr=1e-3, batch_size
                    os.path.join(save_dir, f"pure_gnn_unrolled_K{K}.pt"))
         with open(os.path.join(save_dir, f"history_pure_gnn_unrolled_K{K}.json"), "w") as f:
             json.dump(history, f, indent=2)
+    return model, history
+
+
+# --------------------------------------------------------------------- PINN
+# scripts/training/train_pinn.py on the engine (pinn_train.hip).  PINN.forward
+# stays the inference call (under autograd it raises); training goes through
+# pinn_forward below, in the style of direct_step.
+PINN_LOSS_WEIGHTS = (1.0, 0.1, 0.1, 0.01)  # (w_data, w_continuity, w_momentum, w_poisson), train_pinn.py:142-145
+
+
+def _pinn_dims(model):
+    return model.input_dim, model.hidden_dim, model.num_layers
+
+
+class _PinnTrainForward(torch.autograd.Function):
+    """state + net(state) with HIP backward kernels (hf_pinn_forward_train /
+    hf_pinn_backward; parameter order = state dict), the counterpart of
+    baselines._PureTrainForward."""
+
+    @staticmethod
+    def forward(ctx, state, dims, *params):
+        dev = engine.compute_device(state, "state")
+        flat = _flat_view(params, dev)
+        if flat is None:
+            flat = torch.cat([q.detach().reshape(-1).to(device=dev, dtype=torch.float32) for q in params])
+        s = state.detach().to(device=dev, dtype=torch.float32).reshape(-1, dims[0]).contiguous()
+        out, tape = engine.pinn_forward_train(flat, dims, s)
+        ctx.save_for_backward(flat, tape, s)
+        ctx.dims = dims
+        ctx.shapes = [q.shape for q in params]
+        ctx.param_devices = [q.device for q in params]
+        ctx.state_shape, ctx.state_dtype, ctx.state_device = state.shape, state.dtype, state.device
+        return out.reshape(state.shape).to(state.device)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        flat, tape, s = ctx.saved_tensors
+        gp, gs = engine.pinn_backward(flat, ctx.dims, s, tape, grad_out.reshape(-1, ctx.dims[0]),
+                                      ctx.needs_input_grad[0])
+        grads, o = [], 0
+        for shp in ctx.shapes:
+            n = shp.numel()
+            grads.append(gp[o:o + n].view(shp).to(ctx.param_devices[len(grads)]))
+            o += n
+        if gs is not None:
+            gs = gs.reshape(ctx.state_shape).to(device=ctx.state_device, dtype=ctx.state_dtype)
+        return (gs, None, *grads)
+
+
+def pinn_forward(model, state):
+    """PINN's training forward: state [..., 3, nx] -> state + net(state), the
+    same shape, differentiable in the parameters and (when it requires grad)
+    the state.  Gradients land on each tensor's own device; after
+    model.flatten_parameters_() the kernels read the parameters in place."""
+    if state.dim() < 2 or state.shape[-2] * state.shape[-1] != model.input_dim:
+        raise ValueError(f"pinn_forward: state must be [..., 3, nx] with 3 nx = {model.input_dim}, got "
+                         f"{tuple(state.shape)}")
+    return _PinnTrainForward.apply(state, _pinn_dims(model), *model.parameters())
+
+
+class _PinnLoss(torch.autograd.Function):
+    """The PINN trainer's loss and its gradient as one HIP launch (hf_pinn_loss)."""
+
+    @staticmethod
+    def forward(ctx, pred, state_t, state_next, consts):
+        dev = engine.compute_device(pred, "pred")
+        dx, dt, nu, weights, length = consts
+        losses, gp = engine.pinn_loss(pred.detach().to(dev), state_t, state_next, dx, dt, nu, weights, length)
+        ctx.save_for_backward(gp)
+        ctx.home = (pred.device, pred.dtype)
+        terms = losses[1:].to(pred.device)
+        ctx.mark_non_differentiable(terms)
+        return losses[0].to(pred.device), terms
+
+    @staticmethod
+    def backward(ctx, g, _g_terms):
+        (gp,) = ctx.saved_tensors
+        dev, dtype = ctx.home
+        return (gp.to(device=dev, dtype=dtype) * g.to(dev)), None, None, None
+
+
+def pinn_physics_loss(pred, state_t, state_next, dx, dt, nu, weights=PINN_LOSS_WEIGHTS, length=None):
+    """The reference trainer's loss (train_pinn.py:163-175 with
+    compute_physics_losses, :78-111) of pred = model's prediction from state_t
+    against state_next, all [B,3,nx]: (loss, terms), loss = w . (data,
+    continuity, momentum, poisson), terms the detached device tensor [4] of
+    those.  Differentiable in pred only (the Poisson term included, as in the
+    reference).  length: the domain length of the Poisson operator (default
+    nx dx, the reference's fftfreq(nx, d=dx))."""
+    return _PinnLoss.apply(pred, state_t, state_next, (float(dx), float(dt), float(nu), tuple(weights), length))
+
+
+def _pinn_direct_ok(model, opt):
+    """pinn_step's direct path applies: the optimizer drives exactly the
+    model's parameters, no parameter has hooks, anomaly mode is off."""
+    from .baselines import PINN
+    if type(model) is not PINN or not torch.is_grad_enabled() or torch.is_anomaly_enabled():
+        return False
+    params = list(model.parameters())
+    if len(opt.param_groups) != 1 or [id(q) for q in opt.param_groups[0]["params"]] != [id(q) for q in params] \
+            or not all(q.requires_grad for q in params):
+        return False
+    return not any(getattr(q, "_backward_hooks", None) or getattr(q, "_post_accumulate_grad_hooks", None)
+                   for q in params)
+
+
+def pinn_step(model, opt, state_t, state_next, dx, dt, nu, weights=PINN_LOSS_WEIGHTS, length=None):
+    """One optimizer step of the reference's loop (train_pinn.py:156-179) on a
+    batch [B,3,nx] without an autograd graph: hf_pinn_forward_train,
+    hf_pinn_loss, hf_pinn_backward with the loss's gradient as the incoming
+    one, opt.step().  The gradient goes into the parameters' .grad, as pieces
+    of one flat buffer (which FlatAdam on a flattened model reads in place).
+    Returns the losses [5] = (loss, data, continuity, momentum, poisson) on
+    the device; nothing synchronises the host, so with FlatAdam the step can
+    be captured (GraphedPinnStep).  Parameter hooks are not run on this path:
+    when a parameter has hooks, anomaly mode is on or the optimizer drives
+    other parameters, the step is the autograd composition pinn_forward ->
+    pinn_physics_loss -> backward() instead (the same arithmetic)."""
+    params = list(model.parameters())
+    if not _pinn_direct_ok(model, opt):
+        pred = pinn_forward(model, state_t)
+        loss, terms = pinn_physics_loss(pred, state_t, state_next, dx, dt, nu, weights, length)
+        opt.zero_grad()
+        loss.backward()
+        opt.step()
+        return torch.cat([loss.detach().reshape(1), terms])
+    dev = engine.compute_device(state_t, "state_t")
+    dims = _pinn_dims(model)
+    flat = _flat_view(params, dev)
+    home = flat is not None
+    if not home:
+        flat = torch.cat([q.detach().reshape(-1).to(device=dev, dtype=torch.float32) for q in params])
+    st = state_t.detach().to(device=dev, dtype=torch.float32).contiguous()
+    s2 = st.reshape(-1, dims[0])
+    out, tape = engine.pinn_forward_train(flat, dims, s2)
+    losses, gpred = engine.pinn_loss(out.reshape(st.shape), st, state_next, dx, dt, nu, weights, length)
+    gp, _ = engine.pinn_backward(flat, dims, s2, tape, gpred.reshape(-1, dims[0]), False)
+    o = 0
+    for q in params:
+        g = gp[o:o + q.numel()].view_as(q)
+        q.grad = g if home else g.to(q.device)
+        o += q.numel()
+    opt.step()
+    return losses
+
+
+class GraphedPinnStep(GraphedStep):
+    """pinn_step on a fixed batch size, captured once as a HIP graph and
+    replayed per batch (GraphedStep for the PINN trainer): the batch is copied
+    into static device tensors, the losses [5] come back as a fresh tensor.
+    Needs a flattened model and FlatAdam (a capturable optimizer); the steps
+    before capture() are ordinary eager steps."""
+
+    def __init__(self, model, opt, batch_shape, dx, dt, nu, weights=PINN_LOSS_WEIGHTS, length=None, device="cuda"):
+        self.args = (model, opt, dx, dt, nu, weights, length)
+        self.st = torch.zeros(batch_shape, device=device)
+        self.sn = torch.zeros(batch_shape, device=device)
+        self.graph = None
+        self.out = None
+
+    def _body(self):
+        model, opt, dx, dt, nu, weights, length = self.args
+        return pinn_step(model, opt, self.st, self.sn, dx, dt, nu, weights, length)
+
+    def __call__(self, state_t, state_next):
+        self.st.copy_(state_t)
+        self.sn.copy_(state_next)
+        if self.graph is None:
+            return self._body()
+        self.graph.replay()
+        torch.autograd.graph.increment_version(list(self.args[0].parameters()))
+        return self.out.clone()
+
+
+def pinn_train_flop_per_sample(D=192, H=256, L=4):
+    """Algorithmic FLOPs of one sample of the PINN training step: the forward
+    GEMMs once (2 (DH + (L-2) HH + HD)), the weight gradients once (the same)
+    and the data gradients of every layer but the first (none into the state).
+    tanh, the loss and Adam are not counted."""
+    fwd = 2 * (D * H + (L - 2) * H * H + H * D)
+    return fwd + fwd + (fwd - 2 * D * H)
+
+
+def train_pinn(state_t, state_next, dx, dt, nu, epochs=50, lr=1e-3, batch_size=32, hidden_dim=256, num_layers=4,
+               weights=PINN_LOSS_WEIGHTS, seed=None, init=None, device=None, log=None):
+    """scripts/training/train_pinn.py:114-201 on the MI355X: PINN(3 nx,
+    hidden_dim, num_layers), Adam(lr), batches of batch_size samples in a
+    shuffled order (the last one may be partial), one pinn_step per batch.
+    init: a state dict to start from instead of the seeded initialisation.
+    Returns (model, history) with the reference's history keys, each the
+    per-epoch mean of its batch values (:187-197), accumulated on the device
+    and read once per epoch.  model.state_dict() has the reference PINN's keys
+    and shapes."""
+    from .baselines import PINN
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    engine.require_device(torch.empty(0, device=device), "device")
+    if seed is not None:
+        torch.manual_seed(seed)
+    st_all = torch.as_tensor(np.asarray(state_t, dtype=np.float32), device=device)
+    sn_all = torch.as_tensor(np.asarray(state_next, dtype=np.float32), device=device)
+    if st_all.dim() != 3 or st_all.shape[1] != 3 or sn_all.shape != st_all.shape or st_all.shape[0] < 1:
+        raise ValueError(f"state_t / state_next must be [N,3,nx] with N >= 1, got {tuple(st_all.shape)}, "
+                         f"{tuple(sn_all.shape)}")
+    n, _, nx = st_all.shape
+    model = PINN(3 * nx, hidden_dim, num_layers)
+    if init is not None:
+        model.load_state_dict({k: torch.as_tensor(v) for k, v in init.items()})
+    model = model.to(device).flatten_parameters_()
+    opt = FlatAdam(model.parameters(), lr=lr)
+    gen = torch.Generator().manual_seed(0 if seed is None else seed)
+    keys = ("loss", "loss_data", "loss_continuity", "loss_momentum", "loss_poisson")
+    history = {k: [] for k in keys}
+    model.train()
+    for epoch in range(epochs):
+        perm = torch.randperm(n, generator=gen).to(device)
+        total, nb = torch.zeros(5, device=device), 0
+        for k in range(0, n, batch_size):
+            idx = perm[k:k + batch_size]
+            total += pinn_step(model, opt, st_all[idx], sn_all[idx], dx, dt, nu, weights)
+            nb += 1
+        mean = (total / max(nb, 1)).tolist()  # the epoch's one host read
+        for k, v in zip(keys, mean):
+            history[k].append(v)
+        if log:
+            log(f"Epoch {epoch + 1}/{epochs}, Loss: {mean[0]:.6f} (data={mean[1]:.6f}, cont={mean[2]:.6f}, "
+                f"mom={mean[3]:.6f}, pois={mean[4]:.6f})")
     return model, history

@@ -464,6 +464,74 @@ int hf_pinn_run(const float *dev_params, int dim, int hidden, int layers, const 
                 float *dev_final, int64_t B, int T, float *dev_traj, void *dev_workspace, void *stream);
 
 /*
+ * PINN training (scripts/training/train_pinn.py), in the style of the PureGNN
+ * training entry points above.  dev_params and dev_grad_params are flat
+ * float32 device buffers of hf_pinn_param_count values in state-dict order;
+ * 2 <= layers <= 8 (as hf_pinn_run), B >= 1, dim = 3 nx.
+ *
+ * hf_pinn_forward_train (train_pinn.py:51-61 under autograd) writes dev_out
+ * [B][dim] = state + net(state) and a tape (hf_pinn_tape_bytes: the layers - 1
+ * tanh activations) that hf_pinn_backward consumes.  Its values are
+ * hf_pinn_forward's to rounding, not bit for bit (that one-launch kernel sums
+ * k in a permuted order).
+ *
+ * hf_pinn_backward (loss.backward() of :178 through :51-61) reads dev_grad_out
+ * = dL/dout [B][dim] and writes dL/dparams (overwriting, the layout of
+ * dev_params) and, when dev_grad_state is not NULL, dL/dstate = grad_out +
+ * grad_out dnet/dstate; workspace hf_pinn_backward_workspace_bytes.
+ * dev_params must be unchanged between the forward that wrote the tape and
+ * the backward (the backward multiplies by the weights the forward used), so
+ * the optimizer step comes after it.
+ *
+ * hf_pinn_loss (:64-111 and :163-175) is one launch.  With s = dev_state_t, s*
+ * = dev_state_next, p = dev_pred (all [B][3][nx]), d = p - s*, (n, u, E) the
+ * rows of s, periodic indices, N3 = 3 B nx, N1 = B nx:
+ *   r_c[i] = (p_n[i] - n[i])/dt + (n[i+1]u[i+1] - n[i-1]u[i-1])/(2dx)
+ *   r_m[i] = (p_u[i] - u[i])/dt + u[i](u[i+1] - u[i-1])/(2dx) + E[i]
+ *            - nu (u[i+1] - 2u[i] + u[i-1])/dx^2
+ *   r_p[i] = p_E[i] - X[i],  X[0] = 0,  X[i] = -(P p_n)[i] for i >= 1
+ *   dev_losses = (w_d data + w_c cont + w_m mom + w_p pois, data = sum d^2/N3,
+ *                 cont = sum r_c^2/N1, mom = sum r_m^2/N1, pois = sum r_p^2/N1)
+ * with weights = (w_d, w_c, w_m, w_p), 4 HOST floats, and P the spectral
+ * Poisson operator: the circulant whose first column is dev_plan[0..nx) of
+ * hf_poisson_coeffs(nx, nx dx).  X is the reference trainer's
+ * solve_poisson_torch (:64-75), not the solver's field: the opposite sign, and
+ * cell 0 set to zero.  dev_grad_pred [B][3][nx] = dL/dp; the Poisson term is
+ * not detached (P^T = -P, r~ = r_p with r~[0] = 0):
+ *   dL/dp_n = 2 w_d d_n/N3 + 2 w_c r_c/(dt N1) - (2 w_p/N1) (P r~)
+ *   dL/dp_u = 2 w_d d_u/N3 + 2 w_m r_m/(dt N1)
+ *   dL/dp_E = 2 w_d d_E/N3 + 2 w_p r_p/N1            (cell 0 included)
+ * One workgroup per IC with the circulant column, p_n and r~ in LDS
+ * (nx <= 6144; larger: HF_EUNSUPPORTED); residuals and sums in float64, the
+ * per-IC partial sums added in a fixed order by the last workgroup to arrive
+ * (its counter is zeroed by the call), no float atomics.  dev_workspace:
+ * hf_pinn_loss_workspace_bytes(B, nx).
+ *
+ * Shapes with dim and hidden multiples of 32 run on the f32 MFMA GEMMs of
+ * csrc/tgemm.h (layers launches forward, layers + 3 backward), every other
+ * shape on the generic GEMMs.  Every sum runs in a fixed order (split-K
+ * weight gradients reduced in split order): two calls on the same inputs give
+ * the same bits.
+ *
+ * Bad arguments (NULL required pointers, B < 1, nx < 1, layers outside 2..8,
+ * non-positive dims, dev_out == dev_state, a workspace_bytes too small) return
+ * HF_EINVAL before any device call; the size queries return -1.
+ */
+int64_t hf_pinn_tape_bytes(int dim, int hidden, int layers, int64_t B);
+int64_t hf_pinn_backward_workspace_bytes(int dim, int hidden, int layers, int64_t B);
+int64_t hf_pinn_loss_workspace_bytes(int B, int nx);
+int hf_pinn_forward_train(const float *dev_params, int dim, int hidden, int layers, const float *dev_state,
+                          int64_t B, float *dev_out, void *dev_tape, void *stream);
+int hf_pinn_backward(const float *dev_params, int dim, int hidden, int layers, const float *dev_state, int64_t B,
+                     const void *dev_tape, const float *dev_grad_out, float *dev_grad_params,
+                     float *dev_grad_state /* or NULL */, void *dev_workspace, int64_t workspace_bytes,
+                     void *stream);
+int hf_pinn_loss(const float *dev_pred, const float *dev_state_t, const float *dev_state_next, int B, int nx,
+                 double dt, double dx, double nu, const float *weights /* 4 host floats */,
+                 const double *dev_plan, float *dev_losses /* [5] */, float *dev_grad_pred,
+                 void *dev_workspace, int64_t workspace_bytes, void *stream);
+
+/*
  * Host helper (no device work): the Poisson "plan" for nx cells, length
  * hf_poisson_plan_len(nx) doubles.  plan[0..nx) is the first column c of the
  * real circulant matrix equal to the reference's spectral Poisson operator
