@@ -32,7 +32,7 @@ import torch.nn as nn
 
 from . import engine
 from ._lib import HF_NUM_METRICS, check, lib, ptr
-from .flux_gnn import _flat_view
+from .flat import flat_params, flatten_, split_flat
 
 
 def _flat(module):
@@ -87,9 +87,7 @@ class _PureTrainForward(torch.autograd.Function):
     @staticmethod
     def forward(ctx, node_features, edge_index, dims, *params):
         dev = engine.compute_device(node_features, "node_features")
-        flat = _flat_view(params, dev)
-        if flat is None:
-            flat = torch.cat([q.detach().reshape(-1).to(device=dev, dtype=torch.float32) for q in params])
+        flat, _ = flat_params(params, dev)
         delta, tape, nf, ei, chain_nx = engine.pure_gnn_forward_train(flat, dims, node_features.detach().to(dev),
                                                                       edge_index)
         ctx.save_for_backward(flat, tape, nf, ei)
@@ -106,13 +104,8 @@ class _PureTrainForward(torch.autograd.Function):
         flat, tape, nf, ei = ctx.saved_tensors
         gp, gnf = engine.pure_gnn_backward(flat, ctx.dims, nf, ei, ctx.chain_nx, tape, grad_delta,
                                            ctx.needs_input_grad[0])
-        grads, o = [], 0
-        for shp in ctx.shapes:
-            n = shp.numel()
-            grads.append(gp[o:o + n].view(shp).to(ctx.param_devices[len(grads)]))
-            o += n
         gnf = gnf.to(device=ctx.nf_device, dtype=ctx.nf_dtype) if gnf is not None else None
-        return (gnf, None, None, *grads)
+        return (gnf, None, None, *split_flat(gp, ctx.shapes, ctx.param_devices))
 
 
 class PureGNN(nn.Module):
@@ -151,14 +144,7 @@ class PureGNN(nn.Module):
         keep their identity, FlatAdam can drive them, and the training forward
         hands the kernels that buffer instead of concatenating the parameters
         each step).  .to() / .cuda() afterwards undo it."""
-        params = list(self.parameters())
-        flat = torch.cat([q.detach().reshape(-1).to(torch.float32) for q in params])
-        o = 0
-        with torch.no_grad():
-            for q in params:
-                q.data = flat[o:o + q.numel()].view(q.shape)
-                o += q.numel()
-        return self
+        return flatten_(self)
 
     def rollout(self, states0, n_steps, x, traj=True, *, metrics=False, compare=None):
         """B ICs [B,3,nx] (device) -> dict(final [B,3,nx], traj [B,T+1,3,nx] or None);
@@ -236,14 +222,7 @@ class PINN(nn.Module):
         hybridflux.training.pinn_forward / pinn_step hand the kernels that
         buffer instead of concatenating the parameters each step).  .to() /
         .cuda() afterwards undo it."""
-        params = list(self.parameters())
-        flat = torch.cat([q.detach().reshape(-1).to(torch.float32) for q in params])
-        o = 0
-        with torch.no_grad():
-            for q in params:
-                q.data = flat[o:o + q.numel()].view(q.shape)
-                o += q.numel()
-        return self
+        return flatten_(self)
 
     def rollout(self, states0, n_steps, traj=True, *, metrics=False, compare=None):
         """B ICs [B,3,nx] -> dict(final, traj [B,T+1,3,nx] or None) (evaluate_multi_ic.py:75-81).

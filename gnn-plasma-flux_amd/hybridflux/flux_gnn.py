@@ -31,21 +31,8 @@ import torch
 import torch.nn as nn
 
 from . import engine
+from .flat import flat_params, flatten_, split_flat
 from .graph_constructor import chain_tag, shared_chain_edge_index
-
-
-def _flat_view(params, dev):
-    """The parameters as one flat float32 tensor, without a copy, when they are
-    consecutive contiguous pieces of one device buffer (after
-    FluxGNN.flatten_parameters_); otherwise None."""
-    p0 = params[0]
-    base, off, n = p0.untyped_storage().data_ptr(), p0.storage_offset(), 0
-    for q in params:
-        if (q.device != dev or q.dtype != torch.float32 or not q.is_contiguous()
-                or q.untyped_storage().data_ptr() != base or q.storage_offset() != off + n):
-            return None
-        n += q.numel()
-    return p0.detach().as_strided((n,), (1,), off)
 
 
 class _TrainForward(torch.autograd.Function):
@@ -54,9 +41,7 @@ class _TrainForward(torch.autograd.Function):
     @staticmethod
     def forward(ctx, node_features, edge_index, dims, *params):
         dev = engine.compute_device(node_features, "node_features")
-        flat = _flat_view(params, dev)
-        if flat is None:
-            flat = torch.cat([q.detach().reshape(-1).to(device=dev, dtype=torch.float32) for q in params])
+        flat, _ = flat_params(params, dev)
         flux, tape, nf, ei, chain_nx = engine.graph_forward_train(flat, dims, node_features.detach().to(dev),
                                                                   edge_index)
         ctx.save_for_backward(flat, tape, nf, ei)
@@ -73,15 +58,8 @@ class _TrainForward(torch.autograd.Function):
         flat, tape, nf, ei = ctx.saved_tensors
         gp, gnf = engine.graph_backward(flat, ctx.dims, nf, ei, ctx.chain_nx, tape, grad_flux,
                                         ctx.needs_input_grad[0])
-        grads, o = [], 0
-        for shp in ctx.shapes:
-            n = 1
-            for d in shp:
-                n *= d
-            grads.append(gp[o:o + n].view(shp).to(ctx.param_devices[len(grads)]))
-            o += n
         gnf = gnf.to(device=ctx.nf_device, dtype=ctx.nf_dtype) if gnf is not None else None
-        return (gnf, None, None, *grads)
+        return (gnf, None, None, *split_flat(gp, ctx.shapes, ctx.param_devices))
 
 
 class FluxGNN(nn.Module):
@@ -124,13 +102,7 @@ class FluxGNN(nn.Module):
         made before still holds them): the training forward then hands the
         kernels that buffer instead of concatenating the parameters each step.
         .to() / .cuda() afterwards undo it (the forward falls back to the copy)."""
-        params = list(self.parameters())
-        flat = torch.cat([q.detach().reshape(-1).to(torch.float32) for q in params])
-        o = 0
-        with torch.no_grad():
-            for q in params:
-                q.data = flat[o:o + q.numel()].view(q.shape)
-                o += q.numel()
+        flatten_(self)
         for _, (_, dm) in list(self._packed.items()):
             dm.close()
         self._packed = {}

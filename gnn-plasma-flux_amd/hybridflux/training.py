@@ -28,7 +28,12 @@ Both models also train through their rollouts, K steps deep: unrolled_loss /
 unrolled_step / train_unrolled for FluxGNN through the hybrid solver
 (unroll.hip), pure_unrolled_loss / pure_unrolled_step /
 train_pure_gnn_unrolled for PureGNN through state <- state + PureGNN(...)
-(pure_unroll.hip).
+(pure_unroll.hip).  The two are one driver (_rollout_forward /
+_rollout_backward / _RolloutLoss / _rollout_step / _train_windows) over a
+_Rollout description of each model.
+
+Every trainer hands the kernels the parameters as one flat buffer and gets the
+gradient back as one (flat.py).
 
 PINN (scripts/training/train_pinn.py:64-201) trains at the end of this module:
 pinn_forward (PINN.forward itself stays inference only), pinn_physics_loss
@@ -37,14 +42,17 @@ pinn_forward (PINN.forward itself stays inference only), pinn_physics_loss
 import json
 import os
 import time
+from typing import Callable, NamedTuple, Optional
 
 import numpy as np
 import torch
 
 from . import engine
 from .baseline_solver import BaselineSolver
+from .baselines import PINN, PureGNN
 from .config import ABLATION_CONFIGS, MODEL_CONFIG
-from .flux_gnn import FluxGNN, _flat_view
+from .flat import assign_grads, drives_exactly, flat_params, flat_view, split_flat
+from .flux_gnn import FluxGNN
 from .graph_constructor import build_chain_graph_batch, shared_chain_edge_index
 
 
@@ -262,11 +270,9 @@ class FlatAdam(torch.optim.Optimizer):
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
-        from .flux_gnn import _flat_view
-        self._flat_view = _flat_view
         for group in self.param_groups:
             ps = group["params"]
-            flat = _flat_view(ps, ps[0].device)
+            flat = flat_view(ps, ps[0].device)
             if flat is None:
                 raise ValueError("FlatAdam: the parameters must share one float32 buffer in order "
                                  "(call model.flatten_parameters_() first)")
@@ -286,7 +292,7 @@ class FlatAdam(torch.optim.Optimizer):
         for group in self.param_groups:
             ps = group["params"]
             st = self.state[ps[0]]
-            flat = self._flat_view(ps, ps[0].device)
+            flat = flat_view(ps, ps[0].device)
             if flat is None:
                 raise RuntimeError("FlatAdam: the parameters no longer share one buffer (moved or re-created?)")
             if any(p.grad is None for p in ps):
@@ -294,7 +300,7 @@ class FlatAdam(torch.optim.Optimizer):
             for k in ("exp_avg", "exp_avg_sq", "step", "done"):  # (a state_dict loaded elsewhere)
                 if st[k].device != flat.device or st[k].dtype != torch.float32 or not st[k].is_contiguous():
                     st[k] = st[k].to(device=flat.device, dtype=torch.float32).contiguous()
-            g = self._flat_view([p.grad for p in ps], ps[0].device)
+            g = flat_view([p.grad for p in ps], ps[0].device)
             if g is None:
                 g = torch.cat([p.grad.reshape(-1) for p in ps])
             b1, b2 = group["betas"]
@@ -322,15 +328,13 @@ def direct_step(model, opt, st, ft, sn, nf, x, dt, dx, cfg, grid):
     gradient product and bookkeeping launches.  Parameter hooks are not run.
     Returns (loss, flux_loss) detached, or None when the case does not apply
     (the caller then takes the autograd step)."""
-    from .flux_gnn import _flat_view
     if type(model) is not FluxGNN or not isinstance(opt, FlatAdam) or nf is None or not torch.is_grad_enabled():
         return None
     params = list(model.parameters())
-    if len(opt.param_groups) != 1 or [id(q) for q in opt.param_groups[0]["params"]] != [id(q) for q in params] \
-            or not all(q.requires_grad for q in params):
+    if not drives_exactly(opt, params):
         return None
     dev = st.device
-    flat = _flat_view(params, dev)
+    flat = flat_view(params, dev)
     K = cfg["rollout_steps"] if _has_rollout(cfg) else 0
     if flat is None or K > engine.LOSS_MAX_ROLLOUT or abs(dt / dx - grid.dt / grid.dx) > 1e-12 * abs(dt / dx):
         return None
@@ -342,10 +346,7 @@ def direct_step(model, opt, st, ft, sn, nf, x, dt, dx, cfg, grid):
            cfg["lambda_energy_multi"])
     loss, flux_loss, dfe = engine.ablation_loss_terms(grid, flux.reshape(B, 2 * nx), st, ft, sn, lam, K, dt)
     gp, _ = engine.graph_backward(flat, dims, nf_d, ei_d, chain_nx, tape, dfe.reshape(-1), False)
-    o = 0
-    for q in params:
-        q.grad = gp[o:o + q.numel()].view_as(q)
-        o += q.numel()
+    assign_grads(params, gp)
     opt.step()
     return loss.detach(), flux_loss.detach()
 
@@ -541,6 +542,16 @@ def pure_gnn_train_flop_per_sample(nx=64, H=128, L=4, F=4):
     return (2 * F * H + gemm + gemm + gemm + 2 * F * H) * nx
 
 
+def _stage_states(state_t, state_next, device):
+    """state_t / state_next of a one-step trainer as float32 [N,3,nx] on the device."""
+    st_all = torch.as_tensor(np.asarray(state_t, dtype=np.float32), device=device)
+    sn_all = torch.as_tensor(np.asarray(state_next, dtype=np.float32), device=device)
+    if st_all.dim() != 3 or st_all.shape[1] != 3 or sn_all.shape != st_all.shape or st_all.shape[0] < 1:
+        raise ValueError(f"state_t / state_next must be [N,3,nx] with N >= 1, got {tuple(st_all.shape)}, "
+                         f"{tuple(sn_all.shape)}")
+    return st_all, sn_all
+
+
 def train_pure_gnn(state_t, state_next, x, epochs=50, lr=1e-3, batch_size=32, hidden_dim=None, num_layers=None,
                    device="cuda", order=None, seed=None, log=None):
     """scripts/training/train_pure_gnn.py:79-151 on the MI355X: PureGNN(4,
@@ -550,15 +561,10 @@ def train_pure_gnn(state_t, state_next, x, epochs=50, lr=1e-3, batch_size=32, hi
     batch is one batched step (pure_gnn_step).  order: per epoch an explicit
     sample order (a sequence of `epochs` index sequences) instead of the
     shuffle.  Returns (model, {'loss': [...]})."""
-    from .baselines import PureGNN
     engine.require_device(torch.empty(0, device=device), "device")
     if seed is not None:
         torch.manual_seed(seed)
-    st_all = torch.as_tensor(np.asarray(state_t, dtype=np.float32), device=device)
-    sn_all = torch.as_tensor(np.asarray(state_next, dtype=np.float32), device=device)
-    if st_all.dim() != 3 or st_all.shape[1] != 3 or sn_all.shape != st_all.shape or st_all.shape[0] < 1:
-        raise ValueError(f"state_t / state_next must be [N,3,nx] with N >= 1, got {tuple(st_all.shape)}, "
-                         f"{tuple(sn_all.shape)}")
+    st_all, sn_all = _stage_states(state_t, state_next, device)
     n = st_all.shape[0]
     x_dev = torch.as_tensor(np.asarray(x, dtype=np.float32), device=device)
     model = PureGNN(MODEL_CONFIG["input_dim"], hidden_dim or MODEL_CONFIG["hidden_dim"],
@@ -585,11 +591,57 @@ def train_pure_gnn(state_t, state_next, x, epochs=50, lr=1e-3, batch_size=32, hi
 
 
 # -------------------------------------------------------- unrolled training
-# FluxGNN differentiated through K hybrid solver steps (include/hybridflux.h,
-# hf_unroll_update / hf_unroll_adjoint): the loss sees the solver's feedback
-# loop n -> E -> u -> node features that the evaluation rollouts run, which
-# the one-step ablation loss above never does.
-def _unrolled_forward(flat, dims, traj, x, grid, weights):
+# Both rollout models differentiated through K steps of the loop they are
+# scored on, so that the loss sees the feedback the one-step losses above never
+# do.  FluxGNN through K hybrid solver steps (include/hybridflux.h,
+# hf_unroll_update / hf_unroll_adjoint): n -> E -> u -> node features, as the
+# evaluation rollouts run it.  PureGNN through K steps of its own rollout state
+# <- state + PureGNN([n, u, E, x]) (evaluate_multi_ic.py:53-64;
+# hf_pure_unroll_update / hf_pure_unroll_adjoint).  One driver runs both; a
+# _Rollout says where they differ.
+def _flux_adjoint(grid, tr, pred, k, weights, scale, direct, gnf, keep):
+    g_fe, direct = engine.unroll_adjoint(grid, tr[0] if k == 0 else pred[k - 1], pred[k], tr[k + 1], weights, scale,
+                                         direct, gnf, want_direct=keep)
+    return g_fe.reshape(-1), direct
+
+
+def _pure_update(grid, *args, **kwargs):
+    return engine.pure_unroll_update(*args, **kwargs)
+
+
+def _pure_adjoint(grid, tr, pred, k, weights, scale, gd, gnf, keep):
+    # dL/ds_{k+1} transposed is dL/ddelta_k: the seed of s_{k+1}, what reached s_{k+2} (the
+    # residual update is the identity in the state) and step k+1's feature gradient
+    gd = engine.pure_unroll_adjoint(pred[k], tr[k + 1], weights, scale, gd, gnf)
+    return gd, gd
+
+
+class _Rollout(NamedTuple):
+    """Where K-step training of one model differs from the other's."""
+    model_cls: type
+    loss_name: str       # the public loss function, for the TypeError
+    input_dim: Optional[int]  # the rollout's node features need this width (None: the kernels check)
+    features: Callable   # (state [B,3,nx], x) -> node features of the first step
+    forward: Callable    # engine.*_forward_train
+    backward: Callable   # engine.*_backward
+    workspace: Callable  # (B, nx, dev) -> scratch of update
+    update: Callable     # (grid, model output, state, x, target, weights, scale, want_nf=, out=, loss=, ws=)
+    adjoint: Callable    # (grid, tr, pred, k, weights, scale, carry, gnf, keep) -> (the model backward's
+    #                      incoming gradient, carry): step k's, from step k+1's carry and feature gradient
+    log_label: str
+    checkpoint: str      # <checkpoint>_K<K>.pt
+    history: str         # <history>_K<K>.json
+
+
+_FLUX = _Rollout(FluxGNN, "unrolled_loss", None, lambda st, x: build_chain_graph_batch(st, x)[0],
+                 engine.graph_forward_train, engine.graph_backward, engine.unroll_workspace, engine.unroll_update,
+                 _flux_adjoint, "Unrolled loss", "hybrid_unrolled", "history_unrolled")
+_PURE = _Rollout(PureGNN, "pure_unrolled_loss", 4, pure_gnn_features,
+                 engine.pure_gnn_forward_train, engine.pure_gnn_backward, engine.pure_unroll_workspace, _pure_update,
+                 _pure_adjoint, "PureGNN unrolled loss", "pure_gnn_unrolled", "history_pure_gnn_unrolled")
+
+
+def _rollout_forward(m, flat, dims, traj, x, grid, weights):
     """The K taped forwards and updates.  Returns (loss [] , rec): rec holds
     what the backward needs and the predicted states `pred` [K,B,3,nx]."""
     B, K1, _, nx = traj.shape
@@ -600,14 +652,15 @@ def _unrolled_forward(flat, dims, traj, x, grid, weights):
     scale = 1.0 / (K * 3 * B * nx)
     pred = torch.empty(K, B, 3, nx, device=dev)
     terms = torch.empty(K, device=dev)
-    ws = engine.unroll_workspace(B, nx, dev)
+    ws = m.workspace(B, nx, dev)
     st = tr[0]
-    nf, _ = build_chain_graph_batch(st, x)
+    nf = m.features(st, x)
+    forward, update = m.forward, m.update
     tapes, nfs, chain_nx = [], [], 0
     for k in range(K):
-        flux, tape, nf_d, ei_d, chain_nx = engine.graph_forward_train(flat, dims, nf, ei)
-        _, nf, _ = engine.unroll_update(grid, flux, st, x, tr[k + 1], weights, scale, want_nf=k + 1 < K, out=pred[k],
-                                        loss=terms[k:k + 1], ws=ws)
+        y, tape, nf_d, ei_d, chain_nx = forward(flat, dims, nf, ei)
+        _, nf, _ = update(grid, y, st, x, tr[k + 1], weights, scale, want_nf=k + 1 < K, out=pred[k],
+                          loss=terms[k:k + 1], ws=ws)
         tapes.append(tape)
         nfs.append(nf_d)
         st = pred[k]
@@ -615,60 +668,138 @@ def _unrolled_forward(flat, dims, traj, x, grid, weights):
     return terms.sum(), rec
 
 
-def _unrolled_backward(flat, dims, rec, grid, weights, through_state):
-    """The K adjoint / FluxGNN-backward pairs, last step first; the parameter
+def _rollout_backward(m, flat, dims, rec, grid, weights, through_state):
+    """The K adjoint / model-backward pairs, last step first; the parameter
     gradients of the steps are added in that order (K-1, K-2, ..., 0).
     Returns d loss / d params as one flat buffer."""
-    tr, pred, K = rec["tr"], rec["pred"], rec["K"]
-    total, direct, gnf = None, None, None
+    tr, pred, K, scale = rec["tr"], rec["pred"], rec["K"], rec["scale"]
+    nfs, ei, chain_nx, tapes = rec["nfs"], rec["ei"], rec["chain_nx"], rec["tapes"]
+    adjoint, backward = m.adjoint, m.backward
+    total, carry, gnf = None, None, None
     for k in range(K - 1, -1, -1):
         keep = through_state and k > 0  # step k's state gradient feeds step k-1
-        g_fe, direct = engine.unroll_adjoint(grid, tr[0] if k == 0 else pred[k - 1], pred[k], tr[k + 1], weights,
-                                             rec["scale"], direct, gnf, want_direct=keep)
-        gp, gnf = engine.graph_backward(flat, dims, rec["nfs"][k], rec["ei"], rec["chain_nx"], rec["tapes"][k],
-                                        g_fe.reshape(-1), keep)
+        g, carry = adjoint(grid, tr, pred, k, weights, scale, carry if through_state else None, gnf, keep)
+        gp, gnf = backward(flat, dims, nfs[k], ei, chain_nx, tapes[k], g, keep)
         total = gp if total is None else total.add_(gp)
     return total
 
 
-def _unrolled_check(traj, x, grid):
+def _rollout_check(m, model, traj, x, grid):
+    """The model, traj and x of a K-step loss; with a grid nx is the grid's,
+    without one (PureGNN) any.  Returns x [nx] float32 on traj's device."""
+    if type(model) is not m.model_cls:
+        raise TypeError(f"{m.loss_name} trains {m.model_cls.__name__}")
+    if m.input_dim is not None and model.input_dim != m.input_dim:
+        raise ValueError(f"the rollout builds [n,u,E,x] node features: input_dim must be {m.input_dim}")
     engine.require_device(traj, "traj")
-    if traj.dim() != 4 or traj.shape[1] < 2 or traj.shape[2] != 3 or traj.shape[3] != grid.nx or traj.shape[0] < 1:
-        raise ValueError(f"traj must be [B,K+1,3,{grid.nx}] with B >= 1, K >= 1, got {tuple(traj.shape)}")
+    want = f"[B,K+1,3,{grid.nx}] with B >= 1, K >= 1" if grid is not None else \
+        "[B,K+1,3,nx] with B >= 1, K >= 1, nx >= 1"
+    if traj.dim() != 4 or traj.shape[1] < 2 or traj.shape[2] != 3 or traj.shape[0] < 1 \
+            or (traj.shape[3] != grid.nx if grid is not None else traj.shape[3] < 1):
+        raise ValueError(f"traj must be {want}, got {tuple(traj.shape)}")
     x = torch.as_tensor(x, dtype=torch.float32, device=traj.device).reshape(-1).contiguous()
-    if x.numel() != grid.nx:
+    if x.numel() != traj.shape[3]:
         raise ValueError("x must hold nx positions")
     return x
 
 
-class _UnrolledLoss(torch.autograd.Function):
-    """unrolled_loss as one Function: forward = K taped FluxGNN forwards and
-    hybrid updates, backward = K adjoint / FluxGNN-backward pairs."""
+class _RolloutLoss(torch.autograd.Function):
+    """A K-step loss as one Function: forward = K taped model forwards and
+    updates, backward = K adjoint / model-backward pairs."""
 
     @staticmethod
-    def forward(ctx, traj, x, grid, weights, through_state, dims, *params):
-        dev = traj.device
-        flat = _flat_view(params, dev)
-        if flat is None:
-            flat = torch.cat([q.detach().reshape(-1).to(device=dev, dtype=torch.float32) for q in params])
-        loss, rec = _unrolled_forward(flat, dims, traj, x, grid, weights)
-        ctx.rec, ctx.flat, ctx.grid, ctx.weights, ctx.through, ctx.dims = rec, flat, grid, weights, through_state, dims
+    def forward(ctx, m, traj, x, grid, weights, through_state, dims, *params):
+        flat, _ = flat_params(params, traj.device)
+        loss, rec = _rollout_forward(m, flat, dims, traj, x, grid, weights)
+        ctx.m, ctx.rec, ctx.flat, ctx.grid, ctx.weights, ctx.through, ctx.dims = \
+            m, rec, flat, grid, weights, through_state, dims
         ctx.shapes = [q.shape for q in params]
+        ctx.param_devices = [q.device for q in params]
         ctx.mark_non_differentiable(rec["pred"])
         return loss, rec["pred"]
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_loss, g_pred):
-        gp = _unrolled_backward(ctx.flat, ctx.dims, ctx.rec, ctx.grid, ctx.weights, ctx.through)
+        gp = _rollout_backward(ctx.m, ctx.flat, ctx.dims, ctx.rec, ctx.grid, ctx.weights, ctx.through)
         ctx.rec = None  # the tapes are consumed
         gp = gp.mul_(g_loss)  # (exact for autograd's seed 1)
-        grads, o = [], 0
-        for shp in ctx.shapes:
-            n = int(np.prod(shp)) if len(shp) else 1
-            grads.append(gp[o:o + n].view(shp))
-            o += n
-        return (None, None, None, None, None, None, *grads)
+        return (None, None, None, None, None, None, None, *split_flat(gp, ctx.shapes, ctx.param_devices))
+
+
+def _rollout_loss(m, model, traj, x, grid, channel_weights, through_state, return_states=False):
+    x = _rollout_check(m, model, traj, x, grid)
+    dims = (model.input_dim, model.hidden_dim, model.num_layers)
+    w = tuple(float(v) for v in channel_weights)
+    loss, pred = _RolloutLoss.apply(m, traj, x, grid, w, bool(through_state), dims, *model.parameters())
+    return (loss, pred) if return_states else loss
+
+
+def _rollout_step(m, model, opt, traj, x, grid, channel_weights, through_state):
+    if type(model) is not m.model_cls or not isinstance(opt, FlatAdam) or not torch.is_grad_enabled():
+        return None
+    params = list(model.parameters())
+    if not drives_exactly(opt, params):
+        return None
+    flat = flat_view(params, traj.device)
+    if flat is None:
+        return None
+    x = _rollout_check(m, model, traj, x, grid)
+    dims = (model.input_dim, model.hidden_dim, model.num_layers)
+    w = tuple(float(v) for v in channel_weights)
+    loss, rec = _rollout_forward(m, flat, dims, traj, x, grid, w)
+    gp = _rollout_backward(m, flat, dims, rec, grid, w, bool(through_state))
+    assign_grads(params, gp)
+    opt.step()
+    return loss.detach()
+
+
+def _train_windows(m, model, data, x, grid, init, epochs, lr, batch_size, seed, channel_weights, through_state,
+                   device, save_dir, log):
+    """The K-step trainers' loop: Adam(lr) over shuffled batches of batch_size
+    windows of data (a WindowDataset), one direct step each (the autograd step
+    where that does not apply), one host sync per epoch.  model: the freshly
+    initialised host model; init: a state dict to load into it first."""
+    K = data.K
+    x_dev = torch.as_tensor(np.asarray(x, dtype=np.float32), device=device)
+    if init is not None:
+        model.load_state_dict({k: torch.as_tensor(np.asarray(v)) if not isinstance(v, torch.Tensor) else v
+                               for k, v in init.items()})
+    model = model.to(device)
+    model.flatten_parameters_()
+    opt = FlatAdam(model.parameters(), lr=lr)
+    gen = torch.Generator().manual_seed(0 if seed is None else seed)
+    history = {"epoch": [], "loss": [], "seconds": []}
+    model.train()
+    for epoch in range(1, epochs + 1):
+        order = torch.randperm(len(data), generator=gen).to(device)
+        t0 = time.perf_counter()
+        losses = []
+        for b0 in range(0, len(order), batch_size):
+            win = data.batch(order[b0:b0 + batch_size])
+            loss = _rollout_step(m, model, opt, win, x_dev, grid, channel_weights, through_state)
+            if loss is None:
+                loss = _rollout_loss(m, model, win, x_dev, grid, channel_weights, through_state)
+                opt.zero_grad()
+                loss.backward()
+                opt.step()
+                loss = loss.detach()
+            losses.append((loss, win.shape[0]))
+        tot = sum(float(l) * n for l, n in losses)  # one host sync per epoch
+        torch.cuda.synchronize(device)
+        history["epoch"].append(epoch)
+        history["loss"].append(tot / len(data))
+        history["seconds"].append(time.perf_counter() - t0)
+        if log:
+            log(f"[Epoch {epoch}/{epochs}] {m.log_label} (K = {K}): {history['loss'][-1]:.6e}")
+    if save_dir is not None:
+        os.makedirs(save_dir, exist_ok=True)
+        # (cloned: one storage per tensor, not views of the flat buffer)
+        torch.save({k: v.clone() for k, v in model.state_dict().items()},
+                   os.path.join(save_dir, f"{m.checkpoint}_K{K}.pt"))
+        with open(os.path.join(save_dir, f"{m.history}_K{K}.json"), "w") as f:
+            json.dump(history, f, indent=2)
+    return model, history
 
 
 def unrolled_loss(model, traj, x, grid, channel_weights=(1.0, 1.0, 1.0), through_state=True, return_states=False):
@@ -684,13 +815,7 @@ def unrolled_loss(model, traj, x, grid, channel_weights=(1.0, 1.0, 1.0), through
     the forward is hf_graph_forward_train + one hf_unroll_update launch, the
     backward one hf_unroll_adjoint launch + hf_graph_backward.  return_states:
     also the predicted states [K,B,3,nx] (no gradient)."""
-    if type(model) is not FluxGNN:
-        raise TypeError("unrolled_loss trains FluxGNN")
-    x = _unrolled_check(traj, x, grid)
-    dims = (model.input_dim, model.hidden_dim, model.num_layers)
-    w = tuple(float(v) for v in channel_weights)
-    loss, pred = _UnrolledLoss.apply(traj, x, grid, w, bool(through_state), dims, *model.parameters())
-    return (loss, pred) if return_states else loss
+    return _rollout_loss(_FLUX, model, traj, x, grid, channel_weights, through_state, return_states)
 
 
 def unrolled_step(model, opt, traj, x, grid, channel_weights=(1.0, 1.0, 1.0), through_state=True):
@@ -701,26 +826,7 @@ def unrolled_step(model, opt, traj, x, grid, channel_weights=(1.0, 1.0, 1.0), th
     same parameters bit for bit, without autograd's seed, product and
     bookkeeping launches.  Returns the detached loss, or None when the case does
     not apply (the caller then takes the autograd step)."""
-    if type(model) is not FluxGNN or not isinstance(opt, FlatAdam) or not torch.is_grad_enabled():
-        return None
-    params = list(model.parameters())
-    if len(opt.param_groups) != 1 or [id(q) for q in opt.param_groups[0]["params"]] != [id(q) for q in params] \
-            or not all(q.requires_grad for q in params):
-        return None
-    flat = _flat_view(params, traj.device)
-    if flat is None:
-        return None
-    x = _unrolled_check(traj, x, grid)
-    dims = (model.input_dim, model.hidden_dim, model.num_layers)
-    w = tuple(float(v) for v in channel_weights)
-    loss, rec = _unrolled_forward(flat, dims, traj, x, grid, w)
-    gp = _unrolled_backward(flat, dims, rec, grid, w, bool(through_state))
-    o = 0
-    for q in params:
-        q.grad = gp[o:o + q.numel()].view_as(q)
-        o += q.numel()
-    opt.step()
-    return loss.detach()
+    return _rollout_step(_FLUX, model, opt, traj, x, grid, channel_weights, through_state)
 
 
 def unrolled_train_flop_per_sample(K=4, nx=64, H=128, L=4, F=4):
@@ -783,138 +889,9 @@ def train_unrolled(trajectories, x, dt, dx, nu, K=4, epochs=10, lr=1e-3, batch_s
     grid = BaselineSolver(nx=data.nx, dt=dt, nu=nu, device=device).grid
     if abs(dt / dx - grid.dt / grid.dx) > 1e-12 * abs(dt / dx):
         raise ValueError(f"dx = {dx} is not the periodic grid's {grid.dx} for nx = {data.nx}")
-    x_dev = torch.as_tensor(np.asarray(x, dtype=np.float32), device=device)
     model = FluxGNN(MODEL_CONFIG["input_dim"], MODEL_CONFIG["hidden_dim"], MODEL_CONFIG["num_layers"])
-    if init is not None:
-        model.load_state_dict({k: torch.as_tensor(np.asarray(v)) if not isinstance(v, torch.Tensor) else v
-                               for k, v in init.items()})
-    model = model.to(device)
-    model.flatten_parameters_()
-    opt = FlatAdam(model.parameters(), lr=lr)
-    gen = torch.Generator().manual_seed(0 if seed is None else seed)
-    history = {"epoch": [], "loss": [], "seconds": []}
-    model.train()
-    for epoch in range(1, epochs + 1):
-        order = torch.randperm(len(data), generator=gen).to(device)
-        t0 = time.perf_counter()
-        losses = []
-        for b0 in range(0, len(order), batch_size):
-            win = data.batch(order[b0:b0 + batch_size])
-            loss = unrolled_step(model, opt, win, x_dev, grid, channel_weights, through_state)
-            if loss is None:
-                loss = unrolled_loss(model, win, x_dev, grid, channel_weights, through_state)
-                opt.zero_grad()
-                loss.backward()
-                opt.step()
-                loss = loss.detach()
-            losses.append((loss, win.shape[0]))
-        tot = sum(float(l) * n for l, n in losses)  # one host sync per epoch
-        torch.cuda.synchronize(device)
-        history["epoch"].append(epoch)
-        history["loss"].append(tot / len(data))
-        history["seconds"].append(time.perf_counter() - t0)
-        if log:
-            log(f"[Epoch {epoch}/{epochs}] Unrolled loss (K = {K}): {history['loss'][-1]:.6e}")
-    if save_dir is not None:
-        os.makedirs(save_dir, exist_ok=True)
-        torch.save({k: v.clone() for k, v in model.state_dict().items()},
-                   os.path.join(save_dir, f"hybrid_unrolled_K{K}.pt"))
-        with open(os.path.join(save_dir, f"history_unrolled_K{K}.json"), "w") as f:
-            json.dump(history, f, indent=2)
-    return model, history
-
-
-# ------------------------------------------------ unrolled training, PureGNN
-# PureGNN differentiated through K steps of its own rollout state <- state +
-# PureGNN([n, u, E, x]) (evaluate_multi_ic.py:53-64; include/hybridflux.h,
-# hf_pure_unroll_update / hf_pure_unroll_adjoint): the baseline's loss sees the
-# loop it is scored on, as FluxGNN's does above.
-def _pure_unrolled_forward(flat, dims, traj, x, weights):
-    """The K taped forwards and residual updates.  Returns (loss [], rec): rec
-    holds what the backward needs and the predicted states `pred` [K,B,3,nx]."""
-    B, K1, _, nx = traj.shape
-    K = K1 - 1
-    dev = traj.device
-    tr = traj.detach().to(torch.float32).transpose(0, 1).contiguous()  # [K+1,B,3,nx]: a step's rows contiguous
-    ei = shared_chain_edge_index(nx, B, dev)
-    scale = 1.0 / (K * 3 * B * nx)
-    pred = torch.empty(K, B, 3, nx, device=dev)
-    terms = torch.empty(K, device=dev)
-    ws = engine.pure_unroll_workspace(B, nx, dev)
-    st = tr[0]
-    nf = pure_gnn_features(st, x)
-    tapes, nfs, chain_nx = [], [], 0
-    for k in range(K):
-        delta, tape, nf_d, ei_d, chain_nx = engine.pure_gnn_forward_train(flat, dims, nf, ei)
-        _, nf, _ = engine.pure_unroll_update(delta, st, x, tr[k + 1], weights, scale, want_nf=k + 1 < K, out=pred[k],
-                                             loss=terms[k:k + 1], ws=ws)
-        tapes.append(tape)
-        nfs.append(nf_d)
-        st = pred[k]
-    rec = dict(tr=tr, pred=pred, tapes=tapes, nfs=nfs, ei=ei_d, chain_nx=chain_nx, scale=scale, K=K)
-    return terms.sum(), rec
-
-
-def _pure_unrolled_backward(flat, dims, rec, weights, through_state):
-    """The K adjoint / PureGNN-backward pairs, last step first; the parameter
-    gradients of the steps are added in that order (K-1, K-2, ..., 0).
-    Returns d loss / d params as one flat buffer."""
-    tr, pred, K = rec["tr"], rec["pred"], rec["K"]
-    total, gd, gnf = None, None, None
-    for k in range(K - 1, -1, -1):
-        # dL/ds_{k+1} transposed is dL/ddelta_k: the seed of s_{k+1}, what reached s_{k+2} (the
-        # residual update is the identity in the state) and step k+1's feature gradient
-        gd = engine.pure_unroll_adjoint(pred[k], tr[k + 1], weights, rec["scale"], gd if through_state else None, gnf)
-        gp, gnf = engine.pure_gnn_backward(flat, dims, rec["nfs"][k], rec["ei"], rec["chain_nx"], rec["tapes"][k], gd,
-                                           through_state and k > 0)
-        total = gp if total is None else total.add_(gp)
-    return total
-
-
-def _pure_unrolled_check(model, traj, x):
-    from .baselines import PureGNN
-    if type(model) is not PureGNN:
-        raise TypeError("pure_unrolled_loss trains PureGNN")
-    if model.input_dim != 4:
-        raise ValueError("the rollout builds [n,u,E,x] node features: input_dim must be 4")
-    engine.require_device(traj, "traj")
-    if traj.dim() != 4 or traj.shape[1] < 2 or traj.shape[2] != 3 or traj.shape[3] < 1 or traj.shape[0] < 1:
-        raise ValueError(f"traj must be [B,K+1,3,nx] with B >= 1, K >= 1, nx >= 1, got {tuple(traj.shape)}")
-    x = torch.as_tensor(x, dtype=torch.float32, device=traj.device).reshape(-1).contiguous()
-    if x.numel() != traj.shape[3]:
-        raise ValueError("x must hold nx positions")
-    return x
-
-
-class _PureUnrolledLoss(torch.autograd.Function):
-    """pure_unrolled_loss as one Function: forward = K taped PureGNN forwards
-    and residual updates, backward = K adjoint / PureGNN-backward pairs."""
-
-    @staticmethod
-    def forward(ctx, traj, x, weights, through_state, dims, *params):
-        dev = traj.device
-        flat = _flat_view(params, dev)
-        if flat is None:
-            flat = torch.cat([q.detach().reshape(-1).to(device=dev, dtype=torch.float32) for q in params])
-        loss, rec = _pure_unrolled_forward(flat, dims, traj, x, weights)
-        ctx.rec, ctx.flat, ctx.weights, ctx.through, ctx.dims = rec, flat, weights, through_state, dims
-        ctx.shapes = [q.shape for q in params]
-        ctx.param_devices = [q.device for q in params]
-        ctx.mark_non_differentiable(rec["pred"])
-        return loss, rec["pred"]
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g_loss, g_pred):
-        gp = _pure_unrolled_backward(ctx.flat, ctx.dims, ctx.rec, ctx.weights, ctx.through)
-        ctx.rec = None  # the tapes are consumed
-        gp = gp.mul_(g_loss)  # (exact for autograd's seed 1)
-        grads, o = [], 0
-        for shp, pd in zip(ctx.shapes, ctx.param_devices):
-            n = shp.numel()
-            grads.append(gp[o:o + n].view(shp).to(pd))
-            o += n
-        return (None, None, None, None, None, *grads)
+    return _train_windows(_FLUX, model, data, x, grid, init, epochs, lr, batch_size, seed, channel_weights,
+                          through_state, device, save_dir, log)
 
 
 def pure_unrolled_loss(model, traj, x, channel_weights=(1.0, 1.0, 1.0), through_state=True, return_states=False):
@@ -931,11 +908,7 @@ def pure_unrolled_loss(model, traj, x, channel_weights=(1.0, 1.0, 1.0), through_
     the backward one hf_pure_unroll_adjoint launch + hf_pure_gnn_backward.
     model: a PureGNN with input_dim 4.  return_states: also the predicted states
     [K,B,3,nx] (no gradient)."""
-    x = _pure_unrolled_check(model, traj, x)
-    dims = (model.input_dim, model.hidden_dim, model.num_layers)
-    w = tuple(float(v) for v in channel_weights)
-    loss, pred = _PureUnrolledLoss.apply(traj, x, w, bool(through_state), dims, *model.parameters())
-    return (loss, pred) if return_states else loss
+    return _rollout_loss(_PURE, model, traj, x, None, channel_weights, through_state, return_states)
 
 
 def pure_unrolled_step(model, opt, traj, x, channel_weights=(1.0, 1.0, 1.0), through_state=True):
@@ -946,27 +919,7 @@ def pure_unrolled_step(model, opt, traj, x, channel_weights=(1.0, 1.0, 1.0), thr
     same parameters bit for bit, without autograd's seed, product and
     bookkeeping launches.  Returns the detached loss, or None when the case does
     not apply (the caller then takes the autograd step)."""
-    from .baselines import PureGNN
-    if type(model) is not PureGNN or not isinstance(opt, FlatAdam) or not torch.is_grad_enabled():
-        return None
-    params = list(model.parameters())
-    if len(opt.param_groups) != 1 or [id(q) for q in opt.param_groups[0]["params"]] != [id(q) for q in params] \
-            or not all(q.requires_grad for q in params):
-        return None
-    flat = _flat_view(params, traj.device)
-    if flat is None:
-        return None
-    x = _pure_unrolled_check(model, traj, x)
-    dims = (model.input_dim, model.hidden_dim, model.num_layers)
-    w = tuple(float(v) for v in channel_weights)
-    loss, rec = _pure_unrolled_forward(flat, dims, traj, x, w)
-    gp = _pure_unrolled_backward(flat, dims, rec, w, bool(through_state))
-    o = 0
-    for q in params:
-        q.grad = gp[o:o + q.numel()].view_as(q)
-        o += q.numel()
-    opt.step()
-    return loss.detach()
+    return _rollout_step(_PURE, model, opt, traj, x, None, channel_weights, through_state)
 
 
 def pure_unrolled_train_flop_per_sample(K=4, nx=64, H=128, L=4, F=4):
@@ -993,51 +946,14 @@ def train_pure_gnn_unrolled(trajectories, x, K=4, epochs=10, lr=1e-3, batch_size
     windows), seconds, and writes checkpoints/pure_gnn_unrolled_K<K>.pt (a state
     dict the reference's PureGNN loads) and history_pure_gnn_unrolled_K<K>.json
     (save_dir=None skips)."""
-    from .baselines import PureGNN
     engine.require_device(torch.empty(0, device=device), "device")
     if seed is not None:
         torch.manual_seed(seed)
     data = WindowDataset(trajectories, K, device)
-    x_dev = torch.as_tensor(np.asarray(x, dtype=np.float32), device=device)
     model = PureGNN(MODEL_CONFIG["input_dim"], hidden_dim or MODEL_CONFIG["hidden_dim"],
                     MODEL_CONFIG["num_layers"] if num_layers is None else num_layers)
-    if init is not None:
-        model.load_state_dict({k: torch.as_tensor(np.asarray(v)) if not isinstance(v, torch.Tensor) else v
-                               for k, v in init.items()})
-    model = model.to(device)
-    model.flatten_parameters_()
-    opt = FlatAdam(model.parameters(), lr=lr)
-    gen = torch.Generator().manual_seed(0 if seed is None else seed)
-    history = {"epoch": [], "loss": [], "seconds": []}
-    model.train()
-    for epoch in range(1, epochs + 1):
-        order = torch.randperm(len(data), generator=gen).to(device)
-        t0 = time.perf_counter()
-        losses = []
-        for b0 in range(0, len(order), batch_size):
-            win = data.batch(order[b0:b0 + batch_size])
-            loss = pure_unrolled_step(model, opt, win, x_dev, channel_weights, through_state)
-            if loss is None:
-                loss = pure_unrolled_loss(model, win, x_dev, channel_weights, through_state)
-                opt.zero_grad()
-                loss.backward()
-                opt.step()
-                loss = loss.detach()
-            losses.append((loss, win.shape[0]))
-        tot = sum(float(l) * n for l, n in losses)  # one host sync per epoch
-        torch.cuda.synchronize(device)
-        history["epoch"].append(epoch)
-        history["loss"].append(tot / len(data))
-        history["seconds"].append(time.perf_counter() - t0)
-        if log:
-            log(f"[Epoch {epoch}/{epochs}] PureGNN unrolled loss (K = {K}): {history['loss'][-1]:.6e}")
-    if save_dir is not None:
-        os.makedirs(save_dir, exist_ok=True)
-        torch.save({k: v.clone() for k, v in model.state_dict().items()},
-                   os.path.join(save_dir, f"pure_gnn_unrolled_K{K}.pt"))
-        with open(os.path.join(save_dir, f"history_pure_gnn_unrolled_K{K}.json"), "w") as f:
-            json.dump(history, f, indent=2)
-    return model, history
+    return _train_windows(_PURE, model, data, x, None, init, epochs, lr, batch_size, seed, channel_weights,
+                          through_state, device, save_dir, log)
 
 
 # --------------------------------------------------------------------- PINN
@@ -1059,9 +975,7 @@ class _PinnTrainForward(torch.autograd.Function):
     @staticmethod
     def forward(ctx, state, dims, *params):
         dev = engine.compute_device(state, "state")
-        flat = _flat_view(params, dev)
-        if flat is None:
-            flat = torch.cat([q.detach().reshape(-1).to(device=dev, dtype=torch.float32) for q in params])
+        flat, _ = flat_params(params, dev)
         s = state.detach().to(device=dev, dtype=torch.float32).reshape(-1, dims[0]).contiguous()
         out, tape = engine.pinn_forward_train(flat, dims, s)
         ctx.save_for_backward(flat, tape, s)
@@ -1077,14 +991,9 @@ class _PinnTrainForward(torch.autograd.Function):
         flat, tape, s = ctx.saved_tensors
         gp, gs = engine.pinn_backward(flat, ctx.dims, s, tape, grad_out.reshape(-1, ctx.dims[0]),
                                       ctx.needs_input_grad[0])
-        grads, o = [], 0
-        for shp in ctx.shapes:
-            n = shp.numel()
-            grads.append(gp[o:o + n].view(shp).to(ctx.param_devices[len(grads)]))
-            o += n
         if gs is not None:
             gs = gs.reshape(ctx.state_shape).to(device=ctx.state_device, dtype=ctx.state_dtype)
-        return (gs, None, *grads)
+        return (gs, None, *split_flat(gp, ctx.shapes, ctx.param_devices))
 
 
 def pinn_forward(model, state):
@@ -1133,12 +1042,10 @@ def pinn_physics_loss(pred, state_t, state_next, dx, dt, nu, weights=PINN_LOSS_W
 def _pinn_direct_ok(model, opt):
     """pinn_step's direct path applies: the optimizer drives exactly the
     model's parameters, no parameter has hooks, anomaly mode is off."""
-    from .baselines import PINN
     if type(model) is not PINN or not torch.is_grad_enabled() or torch.is_anomaly_enabled():
         return False
     params = list(model.parameters())
-    if len(opt.param_groups) != 1 or [id(q) for q in opt.param_groups[0]["params"]] != [id(q) for q in params] \
-            or not all(q.requires_grad for q in params):
+    if not drives_exactly(opt, params):
         return False
     return not any(getattr(q, "_backward_hooks", None) or getattr(q, "_post_accumulate_grad_hooks", None)
                    for q in params)
@@ -1166,20 +1073,13 @@ def pinn_step(model, opt, state_t, state_next, dx, dt, nu, weights=PINN_LOSS_WEI
         return torch.cat([loss.detach().reshape(1), terms])
     dev = engine.compute_device(state_t, "state_t")
     dims = _pinn_dims(model)
-    flat = _flat_view(params, dev)
-    home = flat is not None
-    if not home:
-        flat = torch.cat([q.detach().reshape(-1).to(device=dev, dtype=torch.float32) for q in params])
+    flat, home = flat_params(params, dev)
     st = state_t.detach().to(device=dev, dtype=torch.float32).contiguous()
     s2 = st.reshape(-1, dims[0])
     out, tape = engine.pinn_forward_train(flat, dims, s2)
     losses, gpred = engine.pinn_loss(out.reshape(st.shape), st, state_next, dx, dt, nu, weights, length)
     gp, _ = engine.pinn_backward(flat, dims, s2, tape, gpred.reshape(-1, dims[0]), False)
-    o = 0
-    for q in params:
-        g = gp[o:o + q.numel()].view_as(q)
-        q.grad = g if home else g.to(q.device)
-        o += q.numel()
+    assign_grads(params, gp, home)
     opt.step()
     return losses
 
@@ -1231,16 +1131,11 @@ def train_pinn(state_t, state_next, dx, dt, nu, epochs=50, lr=1e-3, batch_size=3
     per-epoch mean of its batch values (:187-197), accumulated on the device
     and read once per epoch.  model.state_dict() has the reference PINN's keys
     and shapes."""
-    from .baselines import PINN
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     engine.require_device(torch.empty(0, device=device), "device")
     if seed is not None:
         torch.manual_seed(seed)
-    st_all = torch.as_tensor(np.asarray(state_t, dtype=np.float32), device=device)
-    sn_all = torch.as_tensor(np.asarray(state_next, dtype=np.float32), device=device)
-    if st_all.dim() != 3 or st_all.shape[1] != 3 or sn_all.shape != st_all.shape or st_all.shape[0] < 1:
-        raise ValueError(f"state_t / state_next must be [N,3,nx] with N >= 1, got {tuple(st_all.shape)}, "
-                         f"{tuple(sn_all.shape)}")
+    st_all, sn_all = _stage_states(state_t, state_next, device)
     n, _, nx = st_all.shape
     model = PINN(3 * nx, hidden_dim, num_layers)
     if init is not None:

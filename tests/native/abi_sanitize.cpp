@@ -10,20 +10,10 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdio>
 #include <cstdlib>
 #include <vector>
 
-#include "hybridflux.h"
-
-static int g_fail = 0;
-#define EXPECT(cond)                                                   \
-  do {                                                                 \
-    if (!(cond)) {                                                     \
-      std::fprintf(stderr, "FAIL %s:%d: %s (%s)\n", __FILE__, __LINE__, #cond, hf_last_error()); \
-      ++g_fail;                                                        \
-    }                                                                  \
-  } while (0)
+#include "expect.h"
 
 static float lcg(unsigned &s) {
   s = s * 1664525u + 1013904223u;
@@ -135,6 +125,5 @@ int main() {
     for (int nx : {64, 100, 256, 1024}) rollouts(nullptr, 5, nx, 4);  // classical: circulant, FFT one-launch
     std::printf("device checks done\n");
   }
-  std::printf("%s: %d failures\n", g_fail ? "FAILED" : "OK", g_fail);
-  return g_fail ? 1 : 0;
+  return finish("abi_sanitize");
 }

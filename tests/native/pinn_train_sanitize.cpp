@@ -13,21 +13,8 @@
 // HF_EHIP (on one with a device the dummy pointers would be dereferenced, so
 // that part is skipped there).  Exit 0 = clean.
 #include <cstdint>
-#include <cstdio>
-#include <cstring>
 
-#include "hybridflux.h"
-
-static int g_fail = 0;
-#define EXPECT(cond)                                                   \
-  do {                                                                 \
-    if (!(cond)) {                                                     \
-      std::fprintf(stderr, "FAIL %s:%d: %s (%s)\n", __FILE__, __LINE__, #cond, hf_last_error()); \
-      ++g_fail;                                                        \
-    }                                                                  \
-  } while (0)
-
-static bool named(const char *fn) { return std::strstr(hf_last_error(), fn) != nullptr; }
+#include "expect.h"
 
 static const float kW[4] = {1.f, 0.1f, 0.1f, 0.01f};
 
@@ -194,10 +181,5 @@ int main() {
     a.dim = 15, a.hidden = 16, a.layers = 2;  // the generic path
     EXPECT(forward(a) == HF_EHIP && named(fw));
   }
-  if (g_fail) {
-    std::fprintf(stderr, "pinn_train_sanitize: %d failure(s)\n", g_fail);
-    return 1;
-  }
-  std::printf("pinn_train_sanitize: clean\n");
-  return 0;
+  return finish("pinn_train_sanitize");
 }

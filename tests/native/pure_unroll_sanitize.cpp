@@ -11,21 +11,8 @@
 // device the dummy pointers would be dereferenced, so that part is skipped
 // there).  Exit 0 = clean.
 #include <cstdint>
-#include <cstdio>
-#include <cstring>
 
-#include "hybridflux.h"
-
-static int g_fail = 0;
-#define EXPECT(cond)                                                   \
-  do {                                                                 \
-    if (!(cond)) {                                                     \
-      std::fprintf(stderr, "FAIL %s:%d: %s (%s)\n", __FILE__, __LINE__, #cond, hf_last_error()); \
-      ++g_fail;                                                        \
-    }                                                                  \
-  } while (0)
-
-static bool named(const char *fn) { return std::strstr(hf_last_error(), fn) != nullptr; }
+#include "expect.h"
 
 static const float kW[3] = {1.f, 1.f, 1.f};
 
@@ -131,10 +118,5 @@ int main() {
     a.gdn = a.gnf = nullptr;
     EXPECT(adjoint(a) == HF_EHIP && named(ad));
   }
-  if (g_fail) {
-    std::fprintf(stderr, "pure_unroll_sanitize: %d failure(s)\n", g_fail);
-    return 1;
-  }
-  std::printf("pure_unroll_sanitize: clean\n");
-  return 0;
+  return finish("pure_unroll_sanitize");
 }

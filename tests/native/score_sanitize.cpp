@@ -9,21 +9,8 @@
 // they need no device and launch nothing; the dummy device pointers are never
 // dereferenced.  Exit 0 = clean.
 #include <cstdint>
-#include <cstdio>
-#include <cstring>
 
-#include "hybridflux.h"
-
-static int g_fail = 0;
-#define EXPECT(cond)                                                   \
-  do {                                                                 \
-    if (!(cond)) {                                                     \
-      std::fprintf(stderr, "FAIL %s:%d: %s (%s)\n", __FILE__, __LINE__, #cond, hf_last_error()); \
-      ++g_fail;                                                        \
-    }                                                                  \
-  } while (0)
-
-static bool named(const char *fn) { return std::strstr(hf_last_error(), fn) != nullptr; }
+#include "expect.h"
 
 struct Args {
   float *params = reinterpret_cast<float *>(16), *s0 = reinterpret_cast<float *>(32);
@@ -165,10 +152,5 @@ int main() {
     a.dim = 48, a.phidden = 32, a.ws_short = 1;  // no one-launch kernel: the workspace holds two trajectories
     EXPECT(pinn(a) == HF_EINVAL && named(pn));
   }
-  if (g_fail) {
-    std::fprintf(stderr, "score_sanitize: %d failure(s)\n", g_fail);
-    return 1;
-  }
-  std::printf("score_sanitize: clean\n");
-  return 0;
+  return finish("score_sanitize");
 }

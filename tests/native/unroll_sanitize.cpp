@@ -7,21 +7,8 @@
 // call, so the program needs no device and launches nothing; the dummy device
 // pointers are never dereferenced.  Exit 0 = clean.
 #include <cstdint>
-#include <cstdio>
-#include <cstring>
 
-#include "hybridflux.h"
-
-static int g_fail = 0;
-#define EXPECT(cond)                                                   \
-  do {                                                                 \
-    if (!(cond)) {                                                     \
-      std::fprintf(stderr, "FAIL %s:%d: %s (%s)\n", __FILE__, __LINE__, #cond, hf_last_error()); \
-      ++g_fail;                                                        \
-    }                                                                  \
-  } while (0)
-
-static bool named(const char *fn) { return std::strstr(hf_last_error(), fn) != nullptr; }
+#include "expect.h"
 
 static const float kW[3] = {1.f, 1.f, 1.f};
 
@@ -140,10 +127,5 @@ int main() {
       EXPECT(adjoint(a) == HF_EUNSUPPORTED && named(ad));
     }
   }
-  if (g_fail) {
-    std::fprintf(stderr, "unroll_sanitize: %d failure(s)\n", g_fail);
-    return 1;
-  }
-  std::printf("unroll_sanitize: clean\n");
-  return 0;
+  return finish("unroll_sanitize");
 }

@@ -441,8 +441,8 @@ def test_flattened_parameters_same_step(hf):
     torch.manual_seed(4)
     a = hf.FluxGNN(4, 128, 4).to(DEV)
     b = copy.deepcopy(a).flatten_parameters_()
-    assert hf.flux_gnn._flat_view(list(b.parameters()), torch.device(DEV)) is not None
-    assert hf.flux_gnn._flat_view(list(a.parameters()), torch.device(DEV)) is None
+    assert hf.flat.flat_view(list(b.parameters()), torch.device(DEV)) is not None
+    assert hf.flat.flat_view(list(a.parameters()), torch.device(DEV)) is None
     st = torch.randn(6, 3, 64, device=DEV)
     x = torch.linspace(0, 2 * np.pi, 65, device=DEV)[:-1]
     out = []
