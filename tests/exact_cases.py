@@ -528,9 +528,10 @@ def accept(b):
 _BUILT = {}
 
 
-def find_case(case):
+def find_case(case, build=build, accept=accept):
     """The case at the first seed (of SEEDS) that is valid for all its
-    precisions and non-vacuous; cached per case.  CPU only."""
+    precisions and non-vacuous; cached per case.  CPU only.  build / accept:
+    another case family's own (tests/saturating_cases.py; its names are its own)."""
     if case.name not in _BUILT:
         why = []
         for seed in range(case.seed0, SEEDS):
