@@ -808,6 +808,58 @@ int hf_pinn_loss(const float *pred, const float *state_t, const float *state_nex
   return HF_OK;
 }
 
+// ------------------------------------------------------- unrolled training, PINN
+int64_t hf_pinn_unroll_workspace_bytes(int B, int nx) {
+  if (B < 1 || nx < 1) return -1;
+  return hf::pinn_unroll_ws_bytes(B, nx);
+}
+
+// what hf_pinn_unroll_loss and hf_pinn_unroll_adjoint check alike
+static int pinn_unroll_args(const char *name, const float *pred, const float *state, const float *target, int B,
+                            int nx, const float *weights, const float *phys, double dt, double dx,
+                            const double *plan) {
+  const std::string fn = name;
+  if (B < 1 || nx < 1) return fail(HF_EINVAL, fn + ": need B >= 1 and nx >= 1");
+  if (!pred || !target || !weights) return fail(HF_EINVAL, fn + ": NULL pointer");
+  if (phys) {
+    if (!plan || !state) return fail(HF_EINVAL, fn + ": phys needs dev_plan and dev_state (NULL pointer)");
+    if (!(dt > 0) || !(dx > 0)) return fail(HF_EINVAL, fn + ": phys needs dt > 0 and dx > 0");
+  }
+  if (!hf::pinn_unroll_nx_ok(nx)) return fail(HF_EUNSUPPORTED, fn + ": nx > 6144");
+  return HF_OK;
+}
+
+int hf_pinn_unroll_loss(const float *pred, const float *state, const float *target, int B, int nx, const float *weights,
+                        float loss_scale, const float *phys, float phys_scale, double dt, double dx, double nu,
+                        const double *plan, float *losses, void *ws, int64_t ws_bytes, void *stream) {
+  const char *fn = "hf_pinn_unroll_loss";
+  if (int rc = pinn_unroll_args(fn, pred, state, target, B, nx, weights, phys, dt, dx, plan)) return rc;
+  if (!losses || !ws) return fail(HF_EINVAL, std::string(fn) + ": NULL pointer");
+  if (ws_bytes < hf::pinn_unroll_ws_bytes(B, nx))
+    return fail(HF_EINVAL, std::string(fn) + ": workspace smaller than hf_pinn_unroll_workspace_bytes");
+  HF_CHECK_HIP(hf::launch_pinn_unroll_loss(pred, state, target, B, nx, weights, loss_scale, phys, phys_scale, dt, dx, nu,
+                                           plan, losses, ws, as_stream(stream)),
+               fn);
+  return HF_OK;
+}
+
+int hf_pinn_unroll_adjoint(const float *pred, const float *state, const float *target, const float *pred_next,
+                           const float *grad_state_next, int B, int nx, const float *weights, float loss_scale,
+                           const float *phys, float phys_scale, double dt, double dx, double nu, const double *plan,
+                           float *grad_out, void *stream) {
+  const char *fn = "hf_pinn_unroll_adjoint";
+  if (int rc = pinn_unroll_args(fn, pred, state, target, B, nx, weights, phys, dt, dx, plan)) return rc;
+  if (!grad_out) return fail(HF_EINVAL, std::string(fn) + ": NULL pointer");
+  // every phase reads the inputs after the first values of dev_grad_out are written
+  for (const float *in : {pred, state, target, pred_next, grad_state_next})
+    if (in == grad_out) return fail(HF_EINVAL, std::string(fn) + ": dev_grad_out must not alias an input");
+  HF_CHECK_HIP(hf::launch_pinn_unroll_adjoint(pred, state, target, pred_next, grad_state_next, B, nx, weights,
+                                              loss_scale, phys, phys_scale, dt, dx, nu, plan, grad_out,
+                                              as_stream(stream)),
+               fn);
+  return HF_OK;
+}
+
 int hf_poisson_plan_len(int nx) { return nx < 1 ? -1 : hf::poisson_plan_len(nx); }
 
 int hf_poisson_coeffs(int nx, double length, double *c) {

@@ -307,6 +307,24 @@ hipError_t launch_pure_unroll_adjoint(const float *st_next, const float *target,
                                       const float *gd_next, const float *gnf_next, int B, int nx, float *gd,
                                       hipStream_t s);
 
+// Unrolled training of PINN (pinn_unroll.hip): the loss term of one rollout
+// step and the gradient its hf_pinn_backward takes in; include/hybridflux.h has
+// the formulas.  Contiguous [B][3][nx] states, nx <= kFvLdsMaxNx, B >= 1.
+//  loss:    losses[5] = (total, data, cont, mom, pois) of pred against target,
+//           residuals on (pred, state); phys (3 host floats) NULL: data only,
+//           state and pc not read.  ws: pinn_unroll_ws_bytes.
+//  adjoint: grad_out = d term / d pred + d next term / d (state slot) (with
+//           phys and pred_next) + grad_state_next (or NULL: left out).
+bool pinn_unroll_nx_ok(int nx);
+int64_t pinn_unroll_ws_bytes(int B, int nx);
+hipError_t launch_pinn_unroll_loss(const float *pred, const float *state, const float *target, int B, int nx,
+                                   const float *w, float scale, const float *phys, float phys_scale, double dt,
+                                   double dx, double nu, const double *pc, float *losses, void *ws, hipStream_t s);
+hipError_t launch_pinn_unroll_adjoint(const float *pred, const float *state, const float *target, const float *pred_next,
+                                      const float *grad_state_next, int B, int nx, const float *w, float scale,
+                                      const float *phys, float phys_scale, double dt, double dx, double nu,
+                                      const double *pc, float *grad_out, hipStream_t s);
+
 // The whole classical rollout (T steps of launch_fv_step's classical update)
 // in one launch, states held in registers: FFT nx up to 1024 (fv_run_fused).
 // state0 [B] x IC stride ld_s0 floats, state_final [B][3][nx] (may alias

@@ -1,0 +1,315 @@
+// Unrolled training of PINN: the loss term of one rollout step
+// (hf_pinn_unroll_loss) and the gradient that step's hf_pinn_backward takes in
+// (hf_pinn_unroll_adjoint), one launch each (scripts/evaluation/
+// evaluate_multi_ic.py:70-83 under a K-step loss; include/hybridflux.h has the
+// mathematics).
+//
+// Both kernels: one 256-thread workgroup per IC, thread t owns cells t, t +
+// 256, ... in every phase.  Residuals and sums in float64.  The circulant
+// column of the spectral Poisson operator P (double), p_n - 1 and r~ live in
+// LDS (16 nx bytes, pinn_loss_kernel's budget: nx <= kFvLdsMaxNx); the adjoint
+// reuses those bytes for q_c and q_m of the following step once P is done.
+//
+// The loss follows pure_unroll.hip term for term (the float32 difference,
+// squared and weighted in float64, a cell's three channels added first), so
+// with phys == NULL and nx <= 1024 (one tile of that kernel per IC) it gives
+// hf_pure_unroll_update's loss bit for bit; beyond 1024 cells the partials are
+// cut differently.  Per-IC float64 partials, summed in IC order by the last
+// workgroup to arrive (pinn_loss_kernel's scheme).  No float atomics; every
+// output value is written by one thread in a fixed order.
+#include "hf_device.h"
+#include "hf_internal.h"
+
+namespace hf {
+namespace {
+
+constexpr int kPuThreads = 256;
+// Workspace: [0, 256) the arrival counter (zeroed by the launcher's memset
+// node before every launch), then four float64 partials per IC (data, cont, mom, pois).
+constexpr size_t kPuCounterBytes = 256;
+
+inline size_t al256(size_t b) { return (b + 255) / 256 * 256; }
+
+__device__ __forceinline__ double wave_sum(double a) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) a += __shfl_xor(a, o, 64);
+  return a;
+}
+
+// w (pred - target)^2 of one value, the difference rounded to float32 (pure_unroll.hip's sq_err)
+__device__ __forceinline__ double sq_err(float pred, float tgt, float w) {
+  const double d = (double)__fsub_rn(pred, tgt);
+  return (double)w * (d * d);
+}
+
+// The residuals' constants; phys == false: only the data term.
+struct Phys {
+  bool on, pois;         // pois: lambda_p != 0 (else no O(nx^2) work)
+  const float *s;        // the state slot (n, u, E) [B][3][nx]
+  const double *pc;      // the circulant column, plan[0..nx)
+  double inv_dt, inv_2dx, nu_dx2;
+};
+
+// r_c and r_m of cell i: p = (pn, pu) the prediction, S the state slot's rows of this IC
+__device__ __forceinline__ void residuals(const float *S, int i, int nx, double pn, double pu, const Phys &f,
+                                          double &rc, double &rm) {
+  const int ip = i == nx - 1 ? 0 : i + 1, im = i == 0 ? nx - 1 : i - 1;
+  const double n = S[i], u = S[nx + i], E = S[2 * nx + i];
+  const double up = S[nx + ip], um = S[nx + im];
+  rc = (pn - n) * f.inv_dt + ((double)S[ip] * up - (double)S[im] * um) * f.inv_2dx;
+  rm = (pu - u) * f.inv_dt + u * (up - um) * f.inv_2dx + E - f.nu_dx2 * (up - 2.0 * u + um);
+}
+
+// ------------------------------------------------------------------------ loss
+struct LossArgs {
+  const float *p, *t;  // pred, target [B][3][nx]
+  Phys f;
+  int B, nx;
+  float w0, w1, w2;
+  double scale;         // loss_scale
+  double sc, sm, sp;    // phys_scale * lambda_c, _m, _p
+  double *part;         // [B][4]
+  unsigned *cnt;
+  float *losses;
+};
+
+__global__ __launch_bounds__(kPuThreads) void pinn_unroll_loss_kernel(LossArgs a) {
+  extern __shared__ double s_dyn[];
+  __shared__ double red[4][4];
+  const int nx = a.nx;
+  double *Lc = s_dyn;  // (used with f.pois only)
+  float *Lrho = reinterpret_cast<float *>(Lc + nx);
+  const int64_t b = blockIdx.x;
+  const float *P = a.p + b * 3 * nx, *T = a.t + b * 3 * nx;
+  const float *S = a.f.on ? a.f.s + b * 3 * nx : nullptr;
+  if (a.f.pois) {  // (uniform)
+    for (int i = threadIdx.x; i < nx; i += kPuThreads) {
+      Lc[i] = a.f.pc[i];
+      Lrho[i] = __fsub_rn(P[i], 1.0f);  // P has zero row sums: P p_n = P (p_n - 1), the solver's operand
+    }
+    __syncthreads();
+  }
+  double sd = 0.0, sc = 0.0, sm = 0.0, sp = 0.0;
+  for (int i = threadIdx.x; i < nx; i += kPuThreads) {
+    const float pn = P[i], pu = P[nx + i], pE = P[2 * nx + i];
+    sd += sq_err(pn, T[i], a.w0) + sq_err(pu, T[nx + i], a.w1) + sq_err(pE, T[2 * nx + i], a.w2);
+    if (a.f.on) {
+      double rc, rm;
+      residuals(S, i, nx, pn, pu, a.f, rc, rm);
+      sc += rc * rc;
+      sm += rm * rm;
+      if (a.f.pois) {
+        // X[0] = 0, X[i] = -(P p_n)[i] (train_pinn.py:72-74)
+        const double X = i == 0 ? 0.0 : -(double)poisson_cell(Lrho, Lc, i, nx);
+        const double rp = (double)pE - X;
+        sp += rp * rp;
+      }
+    }
+  }
+  sd = wave_sum(sd);
+  sc = wave_sum(sc);
+  sm = wave_sum(sm);
+  sp = wave_sum(sp);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) red[wave][0] = sd, red[wave][1] = sc, red[wave][2] = sm, red[wave][3] = sp;
+  __syncthreads();
+  if (threadIdx.x >= 64) return;
+  if (lane < 4) a.part[b * 4 + lane] = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
+  // The last workgroup to arrive sums the partials: agent-scope release before
+  // the ticket, agent-scope acquire after the last one (the per-XCD L2s are not
+  // coherent).  Each lane sums its ICs in ascending order, then the lanes in a
+  // fixed tree: the value does not depend on which workgroup arrives last.
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  unsigned t = 0;
+  if (lane == 0) t = __hip_atomic_fetch_add(a.cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  t = __shfl(t, 0, 64);
+  if (t != gridDim.x - 1) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  double q[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int i = lane; i < a.B; i += 64) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) q[k] += a.part[(int64_t)i * 4 + k];
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) q[k] = wave_sum(q[k]);
+  if (lane == 0) {
+    const double ld = q[0] * a.scale, lc = q[1] * a.sc, lm = q[2] * a.sm, lp = q[3] * a.sp;
+    a.losses[0] = (float)(((ld + lc) + lm) + lp);
+    a.losses[1] = (float)ld;
+    a.losses[2] = (float)lc;
+    a.losses[3] = (float)lm;
+    a.losses[4] = (float)lp;
+  }
+}
+
+// --------------------------------------------------------------------- adjoint
+struct AdjArgs {
+  const float *p, *t;  // pred = s^_k, target = s*_k [B][3][nx]
+  Phys f;              // f.s = s^_{k-1}
+  const float *pnext;  // s^_{k+1} or NULL (read with f.on only)
+  const float *carry;  // hf_pinn_backward's dL/dstate of step k+1, or NULL
+  int nx;
+  double gd0, gd1, gd2;  // 2 w_ch loss_scale
+  double gc, gm, gp;     // 2 phys_scale lambda_c / dt, ... lambda_m / dt, ... lambda_p
+  double qc, qm;         // 2 phys_scale lambda_c, ... lambda_m
+  float *g;
+};
+
+__global__ __launch_bounds__(kPuThreads) void pinn_unroll_adjoint_kernel(AdjArgs a) {
+  extern __shared__ double s_dyn[];
+  const int nx = a.nx;
+  const int64_t b = blockIdx.x;
+  const float *P = a.p + b * 3 * nx, *T = a.t + b * 3 * nx;
+  const float *S = a.f.on ? a.f.s + b * 3 * nx : nullptr;
+  float *G = a.g + b * 3 * nx;
+  // ---- part 1: d term_k / d p, hf_pinn_loss's dL/dp
+  double *Lc = s_dyn;
+  float *Lrho = reinterpret_cast<float *>(Lc + nx), *Lrt = Lrho + nx;
+  if (a.f.pois) {  // (uniform)
+    for (int i = threadIdx.x; i < nx; i += kPuThreads) {
+      Lc[i] = a.f.pc[i];
+      Lrho[i] = __fsub_rn(P[i], 1.0f);
+    }
+    __syncthreads();
+  }
+  for (int i = threadIdx.x; i < nx; i += kPuThreads) {
+    const double pn = P[i], pu = P[nx + i], pE = P[2 * nx + i];
+    double gn = a.gd0 * (pn - (double)T[i]), gu = a.gd1 * (pu - (double)T[nx + i]),
+           gE = a.gd2 * (pE - (double)T[2 * nx + i]);
+    if (a.f.on) {
+      double rc, rm;
+      residuals(S, i, nx, pn, pu, a.f, rc, rm);
+      gn += a.gc * rc;  // the P r~ term is added below
+      gu += a.gm * rm;
+      if (a.f.pois) {
+        const double X = i == 0 ? 0.0 : -(double)poisson_cell(Lrho, Lc, i, nx);
+        const double rp = pE - X;
+        Lrt[i] = i == 0 ? 0.f : (float)rp;  // r~ = r_p with cell 0 zeroed
+        gE += a.gp * rp;
+      }
+    }
+    G[i] = (float)gn;
+    G[nx + i] = (float)gu;
+    G[2 * nx + i] = (float)gE;
+  }
+  if (a.f.pois) {
+    __syncthreads();
+    // dL/dp_n -= 2 phys_scale lambda_p (P r~)   (P^T = -P; this thread's own store above)
+    for (int i = threadIdx.x; i < nx; i += kPuThreads)
+      G[i] = (float)((double)G[i] - a.gp * (double)poisson_cell(Lrt, Lc, i, nx));
+  }
+  const bool back = a.f.on && a.pnext;  // part 2 is present
+  if (!back && !a.carry) return;          // (uniform)
+  // ---- part 2: d term_{k+1} / d (state slot), residuals of step k+1 with p' =
+  // s^_{k+1} and (n, u, E) = s^_k; q_c, q_m over the bytes P no longer needs
+  double *Lqc = s_dyn, *Lqm = s_dyn + nx;
+  if (back) {
+    const float *N = a.pnext + b * 3 * nx;
+    __syncthreads();
+    for (int i = threadIdx.x; i < nx; i += kPuThreads) {
+      double rc, rm;
+      residuals(P, i, nx, (double)N[i], (double)N[nx + i], a.f, rc, rm);
+      Lqc[i] = a.qc * rc;
+      Lqm[i] = a.qm * rm;
+    }
+    __syncthreads();
+  }
+  // ---- the sum: (part 1 + part 2) + part 3, this thread's own stores above
+  const float *C = a.carry ? a.carry + b * 3 * nx : nullptr;
+  for (int i = threadIdx.x; i < nx; i += kPuThreads) {
+    double gn = G[i], gu = G[nx + i], gE = G[2 * nx + i];
+    if (back) {
+      const int ip = i == nx - 1 ? 0 : i + 1, im = i == 0 ? nx - 1 : i - 1;
+      const double n = P[i], u = P[nx + i], up = P[nx + ip], um = P[nx + im];
+      const double dqc = (Lqc[im] - Lqc[ip]) * a.f.inv_2dx;
+      gn += -Lqc[i] * a.f.inv_dt + u * dqc;
+      gu += ((n * dqc + Lqm[i] * (-a.f.inv_dt + (up - um) * a.f.inv_2dx + 2.0 * a.f.nu_dx2)) +
+             Lqm[im] * (um * a.f.inv_2dx - a.f.nu_dx2)) +
+            Lqm[ip] * (-up * a.f.inv_2dx - a.f.nu_dx2);
+      gE += Lqm[i];
+    }
+    if (C) gn += (double)C[i], gu += (double)C[nx + i], gE += (double)C[2 * nx + i];
+    G[i] = (float)gn;
+    G[nx + i] = (float)gu;
+    G[2 * nx + i] = (float)gE;
+  }
+}
+
+Phys phys_of(const float *state, const float *phys, double dt, double dx, double nu, const double *pc) {
+  Phys f{};
+  f.on = phys != nullptr;
+  if (!f.on) return f;
+  f.pois = phys[2] != 0.f;
+  f.s = state;
+  f.pc = pc;
+  f.inv_dt = 1.0 / dt;
+  f.inv_2dx = 1.0 / (2.0 * dx);
+  f.nu_dx2 = nu / (dx * dx);
+  return f;
+}
+
+// LDS: c[nx] (double) | p_n - 1, r~ (float), later q_c, q_m (double)
+inline size_t lds_bytes(const Phys &f, int nx) { return f.on ? (size_t)nx * 16 : 0; }
+
+}  // namespace
+
+bool pinn_unroll_nx_ok(int nx) { return nx >= 1 && nx <= kFvLdsMaxNx; }
+
+int64_t pinn_unroll_ws_bytes(int B, int nx) {
+  (void)nx;
+  return (int64_t)(kPuCounterBytes + al256(sizeof(double) * 4 * (size_t)B));
+}
+
+hipError_t launch_pinn_unroll_loss(const float *pred, const float *state, const float *target, int B, int nx,
+                                   const float *w, float scale, const float *phys, float phys_scale, double dt,
+                                   double dx, double nu, const double *pc, float *losses, void *ws, hipStream_t s) {
+  if (!pinn_unroll_nx_ok(nx) || B < 1) return hipErrorInvalidValue;
+  LossArgs a{};
+  a.p = pred, a.t = target;
+  a.f = phys_of(state, phys, dt, dx, nu, pc);
+  a.B = B, a.nx = nx;
+  a.w0 = w[0], a.w1 = w[1], a.w2 = w[2];
+  a.scale = (double)scale;
+  if (phys) {
+    a.sc = (double)phys_scale * (double)phys[0];
+    a.sm = (double)phys_scale * (double)phys[1];
+    a.sp = (double)phys_scale * (double)phys[2];
+  }
+  a.cnt = static_cast<unsigned *>(ws);
+  a.part = reinterpret_cast<double *>(static_cast<char *>(ws) + kPuCounterBytes);
+  a.losses = losses;
+  // the arrival counter starts every launch at 0 (a memset node, not a kernel)
+  if (hipError_t e = hipMemsetAsync(ws, 0, 16, s)) return e;
+  hipLaunchKernelGGL(pinn_unroll_loss_kernel, dim3((unsigned)B), dim3(kPuThreads), lds_bytes(a.f, nx), s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_pinn_unroll_adjoint(const float *pred, const float *state, const float *target, const float *pred_next,
+                                      const float *grad_state_next, int B, int nx, const float *w, float scale,
+                                      const float *phys, float phys_scale, double dt, double dx, double nu,
+                                      const double *pc, float *grad_out, hipStream_t s) {
+  if (!pinn_unroll_nx_ok(nx) || B < 1) return hipErrorInvalidValue;
+  AdjArgs a{};
+  a.p = pred, a.t = target;
+  a.f = phys_of(state, phys, dt, dx, nu, pc);
+  a.pnext = phys ? pred_next : nullptr;
+  a.carry = grad_state_next;
+  a.nx = nx;
+  a.gd0 = 2.0 * (double)w[0] * (double)scale;
+  a.gd1 = 2.0 * (double)w[1] * (double)scale;
+  a.gd2 = 2.0 * (double)w[2] * (double)scale;
+  if (phys) {
+    a.qc = 2.0 * (double)phys_scale * (double)phys[0];
+    a.qm = 2.0 * (double)phys_scale * (double)phys[1];
+    a.gc = a.qc / dt;
+    a.gm = a.qm / dt;
+    a.gp = 2.0 * (double)phys_scale * (double)phys[2];
+  }
+  a.g = grad_out;
+  hipLaunchKernelGGL(pinn_unroll_adjoint_kernel, dim3((unsigned)B), dim3(kPuThreads), lds_bytes(a.f, nx), s, a);
+  return hipGetLastError();
+}
+
+}  // namespace hf

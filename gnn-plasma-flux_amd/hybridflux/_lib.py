@@ -77,6 +77,12 @@ SIGNATURES = {
                                  c_void_p, c_void_p, c_int64, c_void_p]),
     "hf_pinn_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_double, c_void_p,
                              c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "hf_pinn_unroll_workspace_bytes": (c_int64, [c_int, c_int]),
+    "hf_pinn_unroll_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_void_p, c_float,
+                                    c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "hf_pinn_unroll_adjoint": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                       c_float, c_void_p, c_float, c_double, c_double, c_double, c_void_p, c_void_p,
+                                       c_void_p]),
     "hf_poisson_plan_len": (c_int, [c_int]),
     "hf_poisson_coeffs": (c_int, [c_int, c_double, c_void_p]),
     "hf_poisson": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),

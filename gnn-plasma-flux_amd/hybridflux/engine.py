@@ -428,10 +428,11 @@ def _pinn_dims(dims, B):
     return dim, hidden, layers, nb
 
 
-def pinn_forward_train(params, dims, state):
+def pinn_forward_train(params, dims, state, out=None):
     """PINN's training forward (hf_pinn_forward_train): params is the flat
     float32 device buffer in state-dict order, state [B, dim] float32 on its
-    device.  Returns (out [B, dim] = state + net(state), tape)."""
+    device.  Returns (out [B, dim] = state + net(state), tape).  out: a
+    preallocated contiguous float32 [B, dim] on the state's device to write."""
     require_device(state, "state")
     if state.dtype != torch.float32 or state.dim() != 2 or state.shape[1] != dims[0] or not state.is_contiguous():
         raise ValueError(f"pinn_forward_train: state must be contiguous float32 [B,{dims[0]}], got "
@@ -440,7 +441,10 @@ def pinn_forward_train(params, dims, state):
         raise RuntimeError(f"PINN parameters on {params.device} but the state on {state.device}")
     B = state.shape[0]
     dim, hidden, layers, nb = _pinn_dims(dims, B)
-    out = torch.empty_like(state)
+    if out is None:
+        out = torch.empty_like(state)
+    elif out.dtype != torch.float32 or out.shape != state.shape or out.device != state.device or not out.is_contiguous():
+        raise ValueError(f"pinn_forward_train: out must be contiguous float32 {tuple(state.shape)} on {state.device}")
     tape = torch.empty(nb, dtype=torch.uint8, device=state.device)
     with torch.cuda.device(state.device):
         check(lib().hf_pinn_forward_train(ptr(params), dim, hidden, layers, ptr(state), B, ptr(out), ptr(tape),
@@ -802,6 +806,83 @@ def pure_unroll_adjoint(state_next, target, weights, scale, grad_delta_next=None
         check(lib().hf_pure_unroll_adjoint(ptr(sn), ptr(tg), ptr(w), float(scale), ptr(grad_delta_next),
                                            ptr(gnf_next), B, nx, ptr(gd), stream_of(dev)))
     return gd
+
+
+def pinn_unroll_workspace(B, nx, dev):
+    """hf_pinn_unroll_workspace_bytes of scratch for pinn_unroll_loss on `dev` (a uint8 tensor)."""
+    nb = int(lib().hf_pinn_unroll_workspace_bytes(B, nx))
+    if nb < 0:
+        raise ValueError(f"pinn unroll workspace: need B >= 1, nx >= 1 (B = {B}, nx = {nx})")
+    return torch.empty(nb, dtype=torch.uint8, device=dev)
+
+
+def _pinn_unroll_args(what, pred, target, weights, state, phys, phys_scale, dx, dt, nu, length):
+    """The arguments hf_pinn_unroll_loss and hf_pinn_unroll_adjoint share:
+    (pred, target, state or None, B, nx, dev, w, lam or None, phys_scale, dt,
+    dx, nu, plan or None).  phys = (l_c, l_m, l_p) needs state, dx, dt, nu."""
+    require_device(pred, "pred")
+    if pred.dim() != 3:
+        raise ValueError(f"{what}: pred must be [B,3,nx], got {tuple(pred.shape)}")
+    B, _, nx = pred.shape
+    dev = pred.device
+    p = _unroll_state(pred, B, nx, dev, "pred")
+    tg = _unroll_state(target, B, nx, dev, "target")
+    w = _weights3(weights)
+    if phys is None:
+        return p, tg, None, B, nx, dev, w, None, 0.0, 1.0, 1.0, 0.0, None
+    lam = np.ascontiguousarray(np.asarray(phys, dtype=np.float32).reshape(-1))
+    if lam.size != 3:
+        raise ValueError(f"{what}: phys must be (l_continuity, l_momentum, l_poisson)")
+    if state is None or dx is None or dt is None or nu is None:
+        raise ValueError(f"{what}: phys needs state, dx, dt and nu")
+    st = _unroll_state(state, B, nx, dev, "state")
+    pc = pinn_loss_plan(nx, nx * float(dx) if length is None else length, dev)
+    return p, tg, st, B, nx, dev, w, lam, float(phys_scale), float(dt), float(dx), float(nu), pc
+
+
+def pinn_unroll_loss(pred, target, weights, scale, state=None, phys=None, phys_scale=0.0, dx=None, dt=None, nu=None,
+                     length=None, losses=None, ws=None):
+    """hf_pinn_unroll_loss: one step's term of PINN's K-step loss, losses [5] =
+    (total, data, cont, mom, pois) with data = scale sum w_ch (pred - target)^2
+    and, with phys = (l_c, l_m, l_p), phys_scale l sum r^2 of hf_pinn_loss's
+    residuals at p = pred, (n, u, E) = state; all states contiguous float32
+    [B,3,nx] on pred's device.  phys None: entries 2..4 are 0 and state is not
+    read.  length: the domain length of the Poisson operator (default nx dx).
+    losses / ws: a preallocated float32 [5] and workspace (pinn_unroll_workspace)."""
+    p, tg, st, B, nx, dev, w, lam, phys_scale, dt, dx, nu, pc = _pinn_unroll_args(
+        "pinn_unroll_loss", pred, target, weights, state, phys, phys_scale, dx, dt, nu, length)
+    losses = torch.empty(5, device=dev) if losses is None else losses
+    if losses.dtype != torch.float32 or losses.numel() != 5 or losses.device != dev or not losses.is_contiguous():
+        raise ValueError("pinn_unroll_loss: losses must be five contiguous float32 elements on pred's device")
+    ws = pinn_unroll_workspace(B, nx, dev) if ws is None else ws
+    if ws.device != dev or not ws.is_contiguous():
+        raise ValueError(f"pinn_unroll_loss: the workspace must be contiguous on {dev}")
+    with torch.cuda.device(dev):
+        check(lib().hf_pinn_unroll_loss(ptr(p), ptr(st), ptr(tg), B, nx, ptr(w), float(scale), ptr(lam), phys_scale, dt,
+                                        dx, nu, ptr(pc), ptr(losses), ptr(ws), ws.numel() * ws.element_size(),
+                                        stream_of(dev)))
+    return losses
+
+
+def pinn_unroll_adjoint(pred, target, weights, scale, state=None, phys=None, phys_scale=0.0, dx=None, dt=None, nu=None,
+                        length=None, pred_next=None, grad_state_next=None):
+    """hf_pinn_unroll_adjoint: step k's incoming gradient [B,3,nx] for
+    pinn_backward = d term_k / d pred (pinn_unroll_loss's arguments), + with
+    phys and pred_next (s^_{k+1}) d term_{k+1} / d (state slot), +
+    grad_state_next (pinn_backward's d state of step k+1); pred_next and
+    grad_state_next None at the last step, or to cut the state gradient."""
+    p, tg, st, B, nx, dev, w, lam, phys_scale, dt, dx, nu, pc = _pinn_unroll_args(
+        "pinn_unroll_adjoint", pred, target, weights, state, phys, phys_scale, dx, dt, nu, length)
+    if pred_next is not None:
+        pred_next = _unroll_state(pred_next, B, nx, dev, "pred_next")
+    if grad_state_next is not None:
+        grad_state_next = _unroll_state(grad_state_next, B, nx, dev, "grad_state_next")
+    g = torch.empty(B, 3, nx, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().hf_pinn_unroll_adjoint(ptr(p), ptr(st), ptr(tg), ptr(pred_next), ptr(grad_state_next), B, nx, ptr(w),
+                                           float(scale), ptr(lam), phys_scale, dt, dx, nu, ptr(pc), ptr(g),
+                                           stream_of(dev)))
+    return g
 
 
 def ablation_loss_terms(grid, flux_edge, st, ft, sn, lam, rollout_steps=0, dt=None):

@@ -37,7 +37,11 @@ gradient back as one (flat.py).
 
 PINN (scripts/training/train_pinn.py:64-201) trains at the end of this module:
 pinn_forward (PINN.forward itself stays inference only), pinn_physics_loss
-(hf_pinn_loss), pinn_step and train_pinn, over pinn_train.hip.
+(hf_pinn_loss), pinn_step and train_pinn, over pinn_train.hip; and through K
+steps of its own rollout, as the two graph models and on their driver:
+pinn_unrolled_loss / pinn_unrolled_step / train_pinn_unrolled (pinn_unroll.hip),
+with the state loss of the other two and, on request, the physics residuals
+evaluated on the model's own previous state.
 """
 import json
 import os
@@ -631,6 +635,11 @@ class _Rollout(NamedTuple):
     log_label: str
     checkpoint: str      # <checkpoint>_K<K>.pt
     history: str         # <history>_K<K>.json
+    graph: bool = True   # False (PINN): no edge index and no x, the model maps the flattened state to the next
+    #                      state itself (forward(..., out=pred[k])), `grid` carries the loss's own constants
+    terms: int = 1       # values of a step's loss row, the first one the step's term of L
+    direct_ok: Optional[Callable] = None  # (model, opt) -> the direct step applies (default: FlatAdam on exactly
+    #                                       the model's parameters, grad enabled)
 
 
 _FLUX = _Rollout(FluxGNN, "unrolled_loss", None, lambda st, x: build_chain_graph_batch(st, x)[0],
@@ -648,24 +657,27 @@ def _rollout_forward(m, flat, dims, traj, x, grid, weights):
     K = K1 - 1
     dev = traj.device
     tr = traj.detach().to(torch.float32).transpose(0, 1).contiguous()  # [K+1,B,3,nx]: a step's rows contiguous
-    ei = shared_chain_edge_index(nx, B, dev)
+    ei = shared_chain_edge_index(nx, B, dev) if m.graph else None
     scale = 1.0 / (K * 3 * B * nx)
     pred = torch.empty(K, B, 3, nx, device=dev)
-    terms = torch.empty(K, device=dev)
+    terms = torch.empty(K, device=dev) if m.terms == 1 else torch.empty(K, m.terms, device=dev)
     ws = m.workspace(B, nx, dev)
     st = tr[0]
     nf = m.features(st, x)
     forward, update = m.forward, m.update
     tapes, nfs, chain_nx = [], [], 0
     for k in range(K):
-        y, tape, nf_d, ei_d, chain_nx = forward(flat, dims, nf, ei)
+        if m.graph:
+            y, tape, nf_d, ei_d, chain_nx = forward(flat, dims, nf, ei)
+        else:
+            y, tape, nf_d, ei_d, chain_nx = forward(flat, dims, nf, ei, out=pred[k])
         _, nf, _ = update(grid, y, st, x, tr[k + 1], weights, scale, want_nf=k + 1 < K, out=pred[k],
-                          loss=terms[k:k + 1], ws=ws)
+                          loss=terms[k:k + 1] if m.terms == 1 else terms[k], ws=ws)
         tapes.append(tape)
         nfs.append(nf_d)
         st = pred[k]
-    rec = dict(tr=tr, pred=pred, tapes=tapes, nfs=nfs, ei=ei_d, chain_nx=chain_nx, scale=scale, K=K)
-    return terms.sum(), rec
+    rec = dict(tr=tr, pred=pred, tapes=tapes, nfs=nfs, ei=ei_d, chain_nx=chain_nx, scale=scale, K=K, terms=terms)
+    return (terms.sum() if m.terms == 1 else terms[:, 0].sum()), rec
 
 
 def _rollout_backward(m, flat, dims, rec, grid, weights, through_state):
@@ -692,6 +704,12 @@ def _rollout_check(m, model, traj, x, grid):
     if m.input_dim is not None and model.input_dim != m.input_dim:
         raise ValueError(f"the rollout builds [n,u,E,x] node features: input_dim must be {m.input_dim}")
     engine.require_device(traj, "traj")
+    if not m.graph:  # PINN: no x, nx the model's
+        if traj.dim() != 4 or traj.shape[0] < 1 or traj.shape[1] < 2 or traj.shape[2] != 3 \
+                or 3 * traj.shape[3] != model.input_dim:
+            raise ValueError(f"traj must be [B,K+1,3,nx] with B >= 1, K >= 1, 3 nx = {model.input_dim}, got "
+                             f"{tuple(traj.shape)}")
+        return None
     want = f"[B,K+1,3,{grid.nx}] with B >= 1, K >= 1" if grid is not None else \
         "[B,K+1,3,nx] with B >= 1, K >= 1, nx >= 1"
     if traj.dim() != 4 or traj.shape[1] < 2 or traj.shape[2] != 3 or traj.shape[0] < 1 \
@@ -715,12 +733,12 @@ class _RolloutLoss(torch.autograd.Function):
             m, rec, flat, grid, weights, through_state, dims
         ctx.shapes = [q.shape for q in params]
         ctx.param_devices = [q.device for q in params]
-        ctx.mark_non_differentiable(rec["pred"])
-        return loss, rec["pred"]
+        ctx.mark_non_differentiable(rec["pred"], rec["terms"])
+        return loss, rec["pred"], rec["terms"]
 
     @staticmethod
     @torch.autograd.function.once_differentiable
-    def backward(ctx, g_loss, g_pred):
+    def backward(ctx, g_loss, g_pred, g_terms):
         gp = _rollout_backward(ctx.m, ctx.flat, ctx.dims, ctx.rec, ctx.grid, ctx.weights, ctx.through)
         ctx.rec = None  # the tapes are consumed
         gp = gp.mul_(g_loss)  # (exact for autograd's seed 1)
@@ -731,12 +749,17 @@ def _rollout_loss(m, model, traj, x, grid, channel_weights, through_state, retur
     x = _rollout_check(m, model, traj, x, grid)
     dims = (model.input_dim, model.hidden_dim, model.num_layers)
     w = tuple(float(v) for v in channel_weights)
-    loss, pred = _RolloutLoss.apply(m, traj, x, grid, w, bool(through_state), dims, *model.parameters())
-    return (loss, pred) if return_states else loss
+    loss, pred, terms = _RolloutLoss.apply(m, traj, x, grid, w, bool(through_state), dims, *model.parameters())
+    if not return_states:
+        return loss
+    return (loss, pred) if m.terms == 1 else (loss, pred, terms)
 
 
 def _rollout_step(m, model, opt, traj, x, grid, channel_weights, through_state):
-    if type(model) is not m.model_cls or not isinstance(opt, FlatAdam) or not torch.is_grad_enabled():
+    if m.direct_ok is not None:
+        if not m.direct_ok(model, opt):
+            return None
+    elif type(model) is not m.model_cls or not isinstance(opt, FlatAdam) or not torch.is_grad_enabled():
         return None
     params = list(model.parameters())
     if not drives_exactly(opt, params):
@@ -761,7 +784,7 @@ def _train_windows(m, model, data, x, grid, init, epochs, lr, batch_size, seed, 
     where that does not apply), one host sync per epoch.  model: the freshly
     initialised host model; init: a state dict to load into it first."""
     K = data.K
-    x_dev = torch.as_tensor(np.asarray(x, dtype=np.float32), device=device)
+    x_dev = torch.as_tensor(np.asarray(x, dtype=np.float32), device=device) if x is not None else None
     if init is not None:
         model.load_state_dict({k: torch.as_tensor(np.asarray(v)) if not isinstance(v, torch.Tensor) else v
                                for k, v in init.items()})
@@ -1160,3 +1183,139 @@ def train_pinn(state_t, state_next, dx, dt, nu, epochs=50, lr=1e-3, batch_size=3
             log(f"Epoch {epoch + 1}/{epochs}, Loss: {mean[0]:.6f} (data={mean[1]:.6f}, cont={mean[2]:.6f}, "
                 f"mom={mean[3]:.6f}, pois={mean[4]:.6f})")
     return model, history
+
+
+# ------------------------------------------------------- PINN, unrolled training
+# PINN differentiated through K steps of its own rollout s^_k = s^_{k-1} +
+# net(s^_{k-1}) (evaluate_multi_ic.py:70-83; hf_pinn_unroll_loss /
+# hf_pinn_unroll_adjoint, pinn_unroll.hip), on the driver of the two graph
+# models: the third _Rollout.  The `grid` slot carries the loss's constants.
+class _PinnPhys(NamedTuple):
+    """The residual terms of PINN's K-step loss: lam = (l_c, l_m, l_p) or None (state loss only)."""
+    lam: Optional[tuple]
+    dx: Optional[float]
+    dt: Optional[float]
+    nu: Optional[float]
+    length: Optional[float]
+
+    def kw(self, scale):
+        # phys_scale = 1 / (K B nx) = 3 loss_scale
+        return dict(phys=self.lam, phys_scale=3.0 * scale, dx=self.dx, dt=self.dt, nu=self.nu, length=self.length)
+
+
+def _pinn_roll_forward(flat, dims, state, ei, out):
+    B = state.shape[0]
+    s2 = state.reshape(B, dims[0])
+    y, tape = engine.pinn_forward_train(flat, dims, s2, out=out.view(B, dims[0]))
+    return y, tape, s2, None, 0
+
+
+def _pinn_roll_update(phys, y, st, x, target, weights, scale, want_nf, out, loss, ws):
+    # the forward wrote s^_k into `out` itself; the next model input is that state
+    engine.pinn_unroll_loss(out, target, weights, scale, state=st if phys.lam is not None else None, losses=loss,
+                            ws=ws, **phys.kw(scale))
+    return out, out, None
+
+
+def _pinn_roll_adjoint(phys, tr, pred, k, weights, scale, carry, gstate, keep):
+    # gstate: hf_pinn_backward's dL/dstate of step k+1, there exactly when the state gradient passes (k < K-1)
+    B, _, nx = pred[k].shape
+    on = phys.lam is not None
+    g = engine.pinn_unroll_adjoint(pred[k], tr[k + 1], weights, scale, state=(tr[0] if k == 0 else pred[k - 1]) if on
+                                   else None, pred_next=pred[k + 1] if on and gstate is not None else None,
+                                   grad_state_next=None if gstate is None else gstate.view(B, 3, nx), **phys.kw(scale))
+    return g.view(B, 3 * nx), None
+
+
+def _pinn_roll_backward(flat, dims, state, ei, chain_nx, tape, g, keep):
+    return engine.pinn_backward(flat, dims, state, tape, g, keep)
+
+
+_PINN = _Rollout(PINN, "pinn_unrolled_loss", None, lambda st, x: st, _pinn_roll_forward, _pinn_roll_backward,
+                 engine.pinn_unroll_workspace, _pinn_roll_update, _pinn_roll_adjoint, "PINN unrolled loss",
+                 "pinn_unrolled", "history_pinn_unrolled", graph=False, terms=5, direct_ok=_pinn_direct_ok)
+
+
+def _pinn_phys(physics_weights, dx, dt, nu, length):
+    """dx, dt and nu are required exactly when physics_weights is given."""
+    given = [v is not None for v in (dx, dt, nu)]
+    if physics_weights is None:
+        if any(given) or length is not None:
+            raise ValueError("dx, dt, nu and length belong to the residual terms: pass physics_weights with them")
+        return _PinnPhys(None, None, None, None, None)
+    lam = tuple(float(v) for v in physics_weights)
+    if len(lam) != 3:
+        raise ValueError("physics_weights must be (l_continuity, l_momentum, l_poisson)")
+    if not all(given):
+        raise ValueError("physics_weights needs dx, dt and nu")
+    return _PinnPhys(lam, float(dx), float(dt), float(nu), None if length is None else float(length))
+
+
+def pinn_unrolled_loss(model, traj, dx=None, dt=None, nu=None, channel_weights=(1.0, 1.0, 1.0), physics_weights=None,
+                       through_state=True, return_states=False, length=None):
+    """L = (1/K) sum_{k=1..K} [ mean_{b,ch,i} w_ch (s^_k - s*_k)^2 + l_c mean r_c^2 +
+    l_m mean r_m^2 + l_p mean r_p^2 ] of PINN's own rollout s^_k = s^_{k-1} +
+    net(s^_{k-1}) (evaluate_multi_ic.py:70-83) unrolled K steps from traj[:, 0]
+    against the targets traj[:, 1:]: traj [B,K+1,3,nx] on the device, 3 nx the
+    model's input_dim, nx <= 6144.  physics_weights None (the default): the state
+    loss of unrolled_loss / pure_unrolled_loss alone.  physics_weights = (l_c,
+    l_m, l_p) adds pinn_physics_loss's residuals (train_pinn.py:64-111) at p =
+    s^_k and (n, u, E) = s^_{k-1}, the model's own previous state, and needs dx,
+    dt, nu (length: the Poisson operator's domain length, default nx dx); at K =
+    1 with (0.1, 0.1, 0.01) this is pinn_physics_loss with PINN_LOSS_WEIGHTS.  A
+    scalar with autograd into the model's parameters, through every step's
+    network call and, with through_state, through the state the steps hand on
+    (the network's input and the residuals' state slot).  through_state=False
+    cuts both between steps (the pushforward form).  Per unrolled step the
+    forward is hf_pinn_forward_train + one hf_pinn_unroll_loss launch, the
+    backward one hf_pinn_unroll_adjoint launch + hf_pinn_backward.
+    return_states: also the predicted states [K,B,3,nx] and the steps' terms
+    [K,5] = (total, data, cont, mom, pois), both without gradient."""
+    return _rollout_loss(_PINN, model, traj, None, _pinn_phys(physics_weights, dx, dt, nu, length), channel_weights,
+                         through_state, return_states)
+
+
+def pinn_unrolled_step(model, opt, traj, dx=None, dt=None, nu=None, channel_weights=(1.0, 1.0, 1.0),
+                       physics_weights=None, through_state=True, length=None):
+    """pinn_unrolled_loss -> backward -> opt.step() without autograd, after
+    pure_unrolled_step: where pinn_step's direct path applies (the optimizer
+    drives exactly the model's parameters, no parameter hooks, no anomaly mode)
+    and the parameters share one buffer (flatten_parameters_).  The same
+    forwards, adjoints, backwards and gradient sum as the autograd step, in the
+    same order, so the same parameters bit for bit.  Returns the detached loss,
+    or None when the case does not apply (the caller then takes the autograd
+    step)."""
+    return _rollout_step(_PINN, model, opt, traj, None, _pinn_phys(physics_weights, dx, dt, nu, length),
+                         channel_weights, through_state)
+
+
+def pinn_unrolled_train_flop_per_sample(K=4, D=192, H=256, L=4):
+    """Algorithmic FLOPs of one sample (one K-step window) of PINN's unrolled
+    training step: K times pinn_train_flop_per_sample, plus the first layer's
+    data gradient 2DH for the K - 1 steps that hand a state gradient back.  The
+    loss terms and their adjoints are not counted."""
+    return K * pinn_train_flop_per_sample(D, H, L) + (K - 1) * 2 * D * H
+
+
+def train_pinn_unrolled(trajectories, dx, dt, nu, K=4, epochs=10, lr=1e-3, batch_size=32, hidden_dim=256, num_layers=4,
+                        physics_weights=None, seed=None, init=None, channel_weights=(1.0, 1.0, 1.0),
+                        through_state=True, device="cuda", save_dir="checkpoints", log=print):
+    """Train (or fine-tune) PINN(3 nx, hidden_dim, num_layers) on K-step windows
+    of classical trajectories [N,T+1,3,nx] with pinn_unrolled_loss:
+    train_unrolled's loop -- Adam(lr) over shuffled batches of batch_size windows
+    (WindowDataset), one pinn_unrolled_step each, one host sync per epoch.
+    physics_weights None: the state loss alone (dx, dt, nu are then not used);
+    (l_c, l_m, l_p): with the residual terms.  seed also seeds the initial
+    weights; init: a reference state dict to start from (e.g. train_pinn's).
+    Returns (model, history) with history keys epoch, loss, seconds, and writes
+    checkpoints/pinn_unrolled_K<K>.pt (the reference PINN's keys) and
+    history_pinn_unrolled_K<K>.json (save_dir=None skips)."""
+    engine.require_device(torch.empty(0, device=device), "device")
+    if seed is not None:
+        torch.manual_seed(seed)
+    data = WindowDataset(trajectories, K, device)
+    phys = _pinn_phys(physics_weights, dx, dt, nu, None) if physics_weights is not None else \
+        _PinnPhys(None, None, None, None, None)
+    model = PINN(3 * data.nx, hidden_dim, num_layers)
+    return _train_windows(_PINN, model, data, None, phys, init, epochs, lr, batch_size, seed, channel_weights,
+                          through_state, device, save_dir, log)

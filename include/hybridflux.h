@@ -532,6 +532,75 @@ int hf_pinn_loss(const float *dev_pred, const float *dev_state_t, const float *d
                  void *dev_workspace, int64_t workspace_bytes, void *stream);
 
 /*
+ * Unrolled training of PINN: the network differentiated through K steps of its
+ * own rollout s^_k = s^_{k-1} + net(s^_{k-1}), s^_0 = s*_0
+ * (scripts/evaluation/evaluate_multi_ic.py:70-83), around
+ * hf_pinn_forward_train / hf_pinn_backward.  For a window of targets s*_0..s*_K
+ *   L = (1/K) sum_{k=1..K} [ mean_{b,ch,i} w_ch (s^_k - s*_k)^2
+ *         + l_c mean_{b,i} r_c^2 + l_m mean_{b,i} r_m^2 + l_p mean_{b,i} r_p^2 ]
+ * with r_c, r_m, r_p hf_pinn_loss's residuals at p = s^_k, (n, u, E) = s^_{k-1}
+ * (the model's own previous state, so the residuals carry a gradient into it,
+ * which hf_pinn_loss does not have).  l = (0, 0, 0) is hf_unroll_update's and
+ * hf_pure_unroll_update's L; K = 1, w = (1, 1, 1), l = (0.1, 0.1, 0.01) is
+ * hf_pinn_loss with the reference's weights.
+ *
+ * hf_pinn_unroll_loss, step k's term: p = dev_pred = s^_k, dev_state =
+ * s^_{k-1}, dev_target = s*_k, all [B][3][nx].  dev_losses[0..4] = (total,
+ * data, cont, mom, pois): data = loss_scale sum w_ch (p - s*)^2, cont =
+ * phys_scale l_c sum r_c^2, mom = phys_scale l_m sum r_m^2, pois = phys_scale
+ * l_p sum r_p^2, total their sum; loss_scale = 1/(K 3 B nx) and phys_scale =
+ * 1/(K B nx) give the step's term of L.  weights = w, 3 HOST floats; phys = (l_c,
+ * l_m, l_p), 3 HOST floats, or NULL: entries 2..4 are 0, dev_state and dev_plan
+ * are not read and no O(nx^2) Poisson work is done (nor is it with l_p = 0).
+ * The data term is hf_pure_unroll_update's sum term for term (the float32
+ * difference squared in float64): with phys NULL and nx <= 1024 the total equals
+ * that call's loss bit for bit; beyond 1024 cells that kernel cuts its partials
+ * per tile, this one per IC.
+ *
+ * hf_pinn_unroll_adjoint, step k's incoming gradient for hf_pinn_backward, three
+ * parts, a NULL term left out of the sum, not added as zero:
+ *   dev_grad_out = d term_k / d p              (p = dev_pred, state slot dev_state)
+ *                + d term_{k+1} / d (state slot) (with phys and dev_pred_next =
+ *                    s^_{k+1}: the residuals of step k+1 at p' = dev_pred_next,
+ *                    (n, u, E) = dev_pred)
+ *                + dev_grad_state_next         (hf_pinn_backward's dL/dstate of step k+1)
+ * Part 1 is hf_pinn_loss's dL/dp with 2 w_ch loss_scale (p - s*) per channel
+ * and the factors 2 phys_scale l (the -(P r~) term on the n row included).
+ * Part 2, with q_c = 2 phys_scale l_c r_c and q_m = 2 phys_scale l_m r_m of step
+ * k+1, periodic indices, (n, u, E) = dev_pred:
+ *   d/dn[j] = -q_c[j]/dt + u[j](q_c[j-1] - q_c[j+1])/(2dx)
+ *   d/du[j] = n[j](q_c[j-1] - q_c[j+1])/(2dx)
+ *           + q_m[j](-1/dt + (u[j+1] - u[j-1])/(2dx) + 2nu/dx^2)
+ *           + q_m[j-1](u[j-1]/(2dx) - nu/dx^2) + q_m[j+1](-u[j+1]/(2dx) - nu/dx^2)
+ *   d/dE[j] = q_m[j]
+ * (r_p does not depend on the state slot; the neighbour terms stay separate
+ * terms where indices coincide, nx = 1, 2).  The last step passes NULL for
+ * dev_pred_next and dev_grad_state_next, the pushforward form at every step.
+ *
+ * Kernels: one 256-thread workgroup per IC; the circulant column, p_n - 1, r~
+ * and q_c, q_m in LDS (16 nx bytes; nx <= 6144, larger: HF_EUNSUPPORTED);
+ * spectral operator only (dev_plan[0..nx) of hf_poisson_coeffs(nx, nx dx));
+ * residuals and sums in float64; per-IC float64 partials through dev_workspace
+ * (hf_pinn_unroll_workspace_bytes(B, nx); the call zeroes its arrival counter
+ * itself), summed in IC order by the last workgroup to arrive; no float atomics;
+ * every output value is written by one thread in a fixed order: two calls give
+ * the same bits.  Before any device call a NULL required pointer, B < 1, nx < 1,
+ * phys without dev_plan or dev_state (or with dt <= 0 or dx <= 0), a
+ * workspace_bytes too small, or dev_grad_out equal to an input return HF_EINVAL
+ * (the size query: -1).
+ */
+int64_t hf_pinn_unroll_workspace_bytes(int B, int nx);
+int hf_pinn_unroll_loss(const float *dev_pred, const float *dev_state, const float *dev_target, int B, int nx,
+                        const float *weights /* 3 host */, float loss_scale,
+                        const float *phys /* 3 host: l_c, l_m, l_p; or NULL */, float phys_scale, double dt, double dx,
+                        double nu, const double *dev_plan /* required iff phys */, float *dev_losses /* [5] */,
+                        void *dev_workspace, int64_t workspace_bytes, void *stream);
+int hf_pinn_unroll_adjoint(const float *dev_pred, const float *dev_state, const float *dev_target,
+                           const float *dev_pred_next /* or NULL */, const float *dev_grad_state_next /* or NULL */,
+                           int B, int nx, const float *weights, float loss_scale, const float *phys, float phys_scale,
+                           double dt, double dx, double nu, const double *dev_plan, float *dev_grad_out, void *stream);
+
+/*
  * Host helper (no device work): the Poisson "plan" for nx cells, length
  * hf_poisson_plan_len(nx) doubles.  plan[0..nx) is the first column c of the
  * real circulant matrix equal to the reference's spectral Poisson operator
