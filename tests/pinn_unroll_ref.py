@@ -18,18 +18,35 @@ import torch
 REF_LAMBDA = (0.1, 0.1, 0.01)  # PINN_LOSS_WEIGHTS[1:], train_pinn.py:142-145
 
 
+_COLUMNS = {}
+
+
 def poisson_column(nx, length):
-    """First column of the engine's spectral Poisson operator (hf_poisson_coeffs)."""
+    """First column of the engine's spectral Poisson operator (hf_poisson_coeffs; the
+    host forms it in O(nx^2), so each (nx, length) is asked for once).  A fresh copy."""
     from hybridflux._lib import check, lib
-    pc = np.empty(lib().hf_poisson_plan_len(nx), dtype=np.float64)
-    check(lib().hf_poisson_coeffs(nx, float(length), pc.ctypes.data_as(c_void_p)))
-    return pc[:nx].copy()
+    key = (int(nx), float(length))
+    if key not in _COLUMNS:
+        pc = np.empty(lib().hf_poisson_plan_len(nx), dtype=np.float64)
+        check(lib().hf_poisson_coeffs(nx, float(length), pc.ctypes.data_as(c_void_p)))
+        _COLUMNS[key] = pc[:nx].copy()
+    return _COLUMNS[key].copy()
+
+
+_LAST_MATRIX = {}
 
 
 def poisson_matrix(nx, length, dtype=torch.float64):
-    """The dense circulant: (P f)[i] = sum_j col[(i - j) mod nx] f[j]."""
-    i = torch.arange(nx)
-    return torch.as_tensor(poisson_column(nx, length), dtype=dtype)[(i[:, None] - i[None, :]) % nx]
+    """The dense circulant: (P f)[i] = sum_j col[(i - j) mod nx] f[j].  The last one
+    built is kept (one entry: 6144^2 float64 values are 302 MB and seconds to index)
+    and shared by the calls that follow for the same operator; callers leave it
+    unchanged."""
+    key = (int(nx), float(length), dtype)
+    if key not in _LAST_MATRIX:
+        i = torch.arange(nx)
+        _LAST_MATRIX.clear()
+        _LAST_MATRIX[key] = torch.as_tensor(poisson_column(nx, length), dtype=dtype)[(i[:, None] - i[None, :]) % nx]
+    return _LAST_MATRIX[key]
 
 
 def _up(f):

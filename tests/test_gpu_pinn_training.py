@@ -18,6 +18,9 @@ no element left out.  The reference alone, float32 against float64 (f64_* in
 the fixture): first-batch losses rel 9.4e-8, gradients 4.5e-7 * max|ref|, six
 steps' losses rel 3.0e-7, final weights max abs 1.6e-7, so every gate leaves
 at least 30x over the reference's own rounding.
+
+hf_pinn_loss alone runs here up to nx = 1024; 2048, 4097 and the LDS limit 6144 are
+in test_gpu_nx_regimes.py (through check_loss below).
 """
 import math
 
@@ -66,7 +69,8 @@ def poisson_column(nx, length):
 def restated_loss(pred, st, sn, dx, dt, nu, w, col):
     """The loss of the issue's formulas in torch (any dtype; differentiable in
     pred): returns (loss, data, cont, mom, pois).  P is the circulant with
-    first column col: (P f)[i] = sum_j col[(i - j) mod nx] f[j]."""
+    first column col: (P f)[i] = sum_j col[(i - j) mod nx] f[j]; col may also be that
+    matrix itself, already built in pred's dtype (the wide sizes build it once)."""
     nx = pred.shape[-1]
     n, u, E = st[:, 0], st[:, 1], st[:, 2]
     pn, pu, pE = pred[:, 0], pred[:, 1], pred[:, 2]
@@ -74,7 +78,7 @@ def restated_loss(pred, st, sn, dx, dt, nu, w, col):
     r_c = (pn - n) / dt + (up(n * u) - dn(n * u)) / (2 * dx)
     r_m = (pu - u) / dt + u * (up(u) - dn(u)) / (2 * dx) + E - nu * (up(u) - 2 * u + dn(u)) / dx ** 2
     i = torch.arange(nx)
-    Pm = torch.as_tensor(col, dtype=pred.dtype)[(i[:, None] - i[None, :]) % nx]
+    Pm = col if np.ndim(col) == 2 else torch.as_tensor(col, dtype=pred.dtype)[(i[:, None] - i[None, :]) % nx]
     keep = torch.ones(nx, dtype=pred.dtype)
     keep[0] = 0.0
     X = -(pn @ Pm.T) * keep  # X[0] = 0
@@ -199,13 +203,14 @@ def loss_case(nx, B=3, seed=11):
     return pred, st, sn
 
 
-def check_loss(pred, st, sn, dx, w, tag=""):
+def check_loss(pred, st, sn, dx, w, tag="", dt=DT, col=None):
     from hybridflux import engine
     nx = pred.shape[-1]
     p64 = pred.double().requires_grad_(True)
-    vals = restated_loss(p64, st.double(), sn.double(), dx, DT, NU, w, poisson_column(nx, nx * dx))
+    col = poisson_column(nx, nx * dx) if col is None else col
+    vals = restated_loss(p64, st.double(), sn.double(), dx, dt, NU, w, col)
     vals[0].backward()
-    losses, gp = engine.pinn_loss(pred.to(DEV), st.to(DEV), sn.to(DEV), dx, DT, NU, w)
+    losses, gp = engine.pinn_loss(pred.to(DEV), st.to(DEV), sn.to(DEV), dx, dt, NU, w)
     close(losses, np.array([float(v.detach()) for v in vals]), 0.0, 1e-5, what=f"losses{tag}")
     grad_close(gp, p64.grad.numpy(), f"grad_pred{tag}")
     return losses, gp

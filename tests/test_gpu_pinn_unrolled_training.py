@@ -23,7 +23,9 @@ Gates, those of the sibling file test_gpu_pure_unrolled_training.py unless named
   exact case ............................ zero tolerance
   K = 1 against the one-step trainer .... loss row rtol 1e-6; six Adam steps: loss rtol
       1e-4, weights atol 2e-5, every element (test_gpu_pinn_training's gate)
-Every measured error is recorded (conftest `record` / close)."""
+Every measured error is recorded (conftest `record` / close).
+The shapes here stop at nx = 300; the loss and adjoint kernels at 2048, 4097 and the
+LDS limit 6144 are in test_gpu_nx_regimes.py (through this file's helpers)."""
 import math
 
 import numpy as np
@@ -32,6 +34,7 @@ import torch
 
 import pinn_unroll_ref as R
 from conftest import close, golden
+from nx_regimes import long_wave
 from oracle import hybrid_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -67,10 +70,14 @@ def phys_kw(lam, nx):
 
 
 def states(nx, B, n, seed):
-    """n random states [n,B,3,nx] float32 around (1, 0, 0), each 0.02 from the one before."""
+    """n random states [n,B,3,nx] float32 around (1, 0, 0), each 0.02 from the one before;
+    beyond 1024 cells (test_gpu_nx_regimes.py's sizes) the densities carry
+    nx_regimes.long_wave, without which P p_n is lost next to p_E."""
     g = torch.Generator().manual_seed(seed)
     s = torch.stack([1 + 0.1 * torch.randn(B, nx, generator=g), 0.1 * torch.randn(B, nx, generator=g),
                      0.1 * torch.randn(B, nx, generator=g)], dim=1)
+    if nx > 1024:
+        s[:, 0] += torch.as_tensor(long_wave(nx, B), dtype=torch.float32)
     out = [s]
     for _ in range(n - 1):
         out.append(out[-1] + 0.02 * torch.randn(B, 3, nx, generator=g))

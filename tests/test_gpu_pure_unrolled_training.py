@@ -29,14 +29,17 @@ import pytest
 import torch
 
 from conftest import close, golden
+from nx_regimes import PURE_WIDE
 from oracle import hybrid_oracle as O
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 REL = 2e-5
 # (nx, B): one cell, two cells, a quarter of a wave, part of a wave, more than a
-# wave, several workgroups of one tile each, and a chain of two tiles (1024 + 6 cells)
-SHAPES = [(1, 2), (2, 3), (16, 3), (48, 3), (100, 3), (64, 9), (1030, 2)]
+# wave, several workgroups of one tile each, and a chain of two tiles (1024 + 6 cells);
+# then nx_regimes.PURE_WIDE: exactly one tile (1024), a one-cell tail tile (2049) and
+# six whole tiles (6144, the other training kernels' limit)
+SHAPES = [(1, 2), (2, 3), (16, 3), (48, 3), (100, 3), (64, 9), (1030, 2)] + PURE_WIDE
 
 
 @pytest.fixture(scope="module")

@@ -535,7 +535,10 @@ def test_loss_terms_any_nx(hf, nx):
     """hf_ablation_loss at chain lengths other than the trainer's 64: the
     one-launch terms (circulant sizes: nx = 1, 16, 100) and the three-launch
     form around the FFT Poisson (nx = 256) against the torch expressions of
-    the same loss ('physics' weights; loss, flux loss and d loss / d flux_edge)."""
+    the same loss ('physics' weights; loss, flux loss and d loss / d flux_edge).
+    The torch form takes its E' from the engine's own Poisson kernel; the sizes past
+    256 (every Poisson path of the three-launch form, the one-launch kernel's largest
+    size) are in test_gpu_nx_regimes.py against an independent float64 reference."""
     from hybridflux.training import ablation_loss
     g = torch.Generator().manual_seed(nx)
     B = 37

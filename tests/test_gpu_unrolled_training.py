@@ -18,7 +18,18 @@ Tolerances:
       split-K partials are summed in another order than the CPU BLAS's, factor 4)
   predicted states, K = 4 ............... atol 2e-6 + rtol 2e-6 (test_gpu_parity's gate
       on hybrid rollouts)
-Every measured error is recorded (conftest `record` / close)."""
+Every measured error is recorded (conftest `record` / close).
+
+Sizes: the update, its loss term and the adjoint run over SHAPES (nx <= 256) and
+nx_regimes.UNROLL_WIDE: every FFT instantiation (256, 512, 1024, 2048; a lone IC,
+odd IC counts, one IC past a workgroup, two workgroups of the 2048 kernel) and the
+circulant kernels at 257, 1000, 4096 and their LDS limit 6144; the bit-for-bit
+comparison with hf_step at 100, 256, 257, 512, 1024, 2048, 6144; the K-step
+gradients up to 100 with the trained model and at 512, 2048, 6144 with
+FluxGNN(4, 64, 2).  Beyond 256 cells dt shrinks with dx (dt_for), which keeps the
+values O(1) and the gates unchanged.  E of one update is float32 on both sides and
+reaches [0.5, 1), where one ulp is 5.96e-8: a last-bit difference from the oracle's
+own rounding is 0.596 of the 1e-7 gate, at nx = 48 as at 6144 (n and u: equal bits)."""
 import ctypes
 
 import numpy as np
@@ -26,6 +37,7 @@ import pytest
 import torch
 
 from conftest import close, golden
+from nx_regimes import UNROLL_WIDE, UNROLLED_GRAD_WIDE, UPDATE_BITWISE_WIDE, dt_of
 from oracle import hybrid_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -73,8 +85,26 @@ def load(hf, sd, dims=(4, 128, 4)):
     return m.to(DEV)
 
 
+def dt_for(nx):
+    """The reference's 5e-3 at the sizes up to 256 (the cases first written here, kept
+    as they were); beyond, nx_regimes.dt_of: the same dt / dx as at nx = 64, so that
+    the values, and with them what an absolute gate means, keep their size."""
+    return 5e-3 if nx <= 256 else dt_of(nx)
+
+
+_GRIDS = {}
+
+
+def grid_of(hf, nx):
+    """The engine grid of nx at dt_for(nx), built once (the host builds the circulant
+    column in O(nx^2): seconds at 6144) and shared; nothing here changes a grid."""
+    if nx not in _GRIDS:
+        _GRIDS[nx] = hf.BaselineSolver(nx, dt=dt_for(nx), device=DEV).grid
+    return _GRIDS[nx]
+
+
 def ics(nx, B, seed0=0):
-    G = O.Grid(nx)
+    G = O.Grid(nx, dt=dt_for(nx))
     return G, np.stack([O.initial_condition(G, seed0 + s) for s in range(B)])
 
 
@@ -130,12 +160,12 @@ def unrolled_loss_cpu(sd, G, traj, w, dtype, through=True):
 
 
 # ------------------------------------------------------------------ 1. update forward
-@pytest.mark.parametrize("nx,B", SHAPES)
+@pytest.mark.parametrize("nx,B", SHAPES + UNROLL_WIDE)
 def test_update_vs_oracle(hf, nx, B):
     from hybridflux import engine
     G, st = ics(nx, B)
     fe = np.random.default_rng(nx * 100 + B).normal(0, 0.3, (B, 2 * nx)).astype(np.float32)
-    grid = hf.BaselineSolver(nx, device=DEV).grid
+    grid = grid_of(hf, nx)
     out, nf, loss = engine.unroll_update(grid, dev(fe).reshape(-1), dev(st))
     assert loss is None
     want, _ = O.hybrid_update(G, st, fe)
@@ -149,15 +179,17 @@ def test_update_vs_oracle(hf, nx, B):
     assert nf2 is None and torch.equal(out2, out)
 
 
-@pytest.mark.parametrize("nx,B", [(100, 3), (256, 3), (256, 9)])
+@pytest.mark.parametrize("nx,B", [(100, 3), (256, 3), (256, 9)] + UPDATE_BITWISE_WIDE)
 def test_update_bitwise_equals_step(hf, nx, B):
     """At the chain lengths where hf_step is the flux kernel followed by the
     finite-volume kernel on its face flux, the update on the same model's edge
-    fluxes gives hf_step's state bit for bit (shared device functions)."""
+    fluxes gives hf_step's state bit for bit (shared device functions):
+    fv_step_kernel<true> up to the LDS limit 6144, fv_step_fft_kernel<true> at
+    each of the FFT sizes 256, 512, 1024 and 2048."""
     from hybridflux import engine
     _, st = ics(nx, B, seed0=5)
     m = load(hf, w1r2()).eval()
-    grid = hf.BaselineSolver(nx, device=DEV).grid
+    grid = grid_of(hf, nx)
     std = dev(st)
     x, _ = grid.on(std.device)
     nf, _ = hf.build_chain_graph_batch(std, x)
@@ -169,7 +201,7 @@ def test_update_bitwise_equals_step(hf, nx, B):
 
 
 # ---------------------------------------------------------------------- 2. loss term
-@pytest.mark.parametrize("nx,B", [(16, 3), (100, 3), (256, 9), (64, 300)])
+@pytest.mark.parametrize("nx,B", [(16, 3), (100, 3), (256, 9), (64, 300)] + UNROLL_WIDE)
 def test_step_loss(hf, nx, B):
     from hybridflux import engine
     G, st = ics(nx, min(B, 4))
@@ -179,7 +211,7 @@ def test_step_loss(hf, nx, B):
     fe = g.normal(0, 0.3, (B, 2 * nx)).astype(np.float32)
     tgt = (st + g.normal(0, 0.05, st.shape)).astype(np.float32)
     w, K = (1.0, 0.5, 2.0), 4
-    grid = hf.BaselineSolver(nx, device=DEV).grid
+    grid = grid_of(hf, nx)
     scale = 1.0 / (K * 3 * B * nx)
     runs = []
     for _ in range(2):
@@ -210,7 +242,7 @@ def adjoint_case(hf, nx, B, mode):
         din_d = gnf_d = None
     else:
         din_d, gnf_d = dev(din), dev(gnf)
-    grid = hf.BaselineSolver(nx, device=DEV).grid
+    grid = grid_of(hf, nx)
     g_fe, direct = engine.unroll_adjoint(grid, dev(st), dev(sn), dev(tg), w, scale, din_d, gnf_d)
     # reference: float64 autograd of sum(g * step(st, fe)) with fe a free tensor
     gt = 2.0 * np.asarray(w)[None, :, None] * scale * (sn.astype(np.float64) - tg)
@@ -224,7 +256,7 @@ def adjoint_case(hf, nx, B, mode):
 
 
 @pytest.mark.parametrize("mode", ["full", "last", "e_only"])
-@pytest.mark.parametrize("nx,B", SHAPES)
+@pytest.mark.parametrize("nx,B", SHAPES + UNROLL_WIDE)
 def test_adjoint_vs_autograd(hf, record, nx, B, mode):
     g_fe, direct, want_fe, want_d, gmax = adjoint_case(hf, nx, B, mode)
     name = f"test_adjoint_vs_autograd[{nx}-{B}-{mode}]"
@@ -246,6 +278,7 @@ def classical_windows(G, B, K):
 
 
 _GRAD_CASES = [(64, 3, 1, 128), (64, 3, 4, 128), (16, 3, 4, 128), (48, 2, 2, 128), (100, 2, 2, 64)]
+_GRAD_CASES += [(nx, B, 2, 64) for nx, B in UNROLLED_GRAD_WIDE]  # FluxGNN(4, 64, 2), K = 2
 _REF = {}
 
 
@@ -253,7 +286,7 @@ def grad_reference(nx, B, K, hidden, through):
     """(sd, dims, traj, g64, g32), computed once per case and left unchanged."""
     key = (nx, B, K, hidden, through)
     if key not in _REF:
-        G = O.Grid(nx)
+        G = O.Grid(nx, dt=dt_for(nx))
         sd, dims = (w1r2(), (4, 128, 4)) if hidden == 128 else (rand_sd64(2, 11), (4, 64, 2))
         traj = classical_windows(G, B, K)
         w = (1.0, 1.0, 1.0)
@@ -266,7 +299,7 @@ def grad_reference(nx, B, K, hidden, through):
 def gpu_grads(hf, sd, dims, traj, nx, through):
     from hybridflux import training
     m = load(hf, sd, dims)
-    grid = hf.BaselineSolver(nx, device=DEV).grid
+    grid = grid_of(hf, nx)
     x, _ = grid.on(torch.device(DEV))
     loss = training.unrolled_loss(m, dev(traj), x, grid, through_state=through)
     loss.backward()
@@ -315,7 +348,7 @@ def test_predicted_states_vs_oracle(hf):
     sd = w1r2()
     traj = classical_windows(G, B, K)
     m = load(hf, sd)
-    grid = hf.BaselineSolver(nx, device=DEV).grid
+    grid = grid_of(hf, nx)
     x, _ = grid.on(torch.device(DEV))
     _, pred = training.unrolled_loss(m, dev(traj), x, grid, return_states=True)
     assert not pred.requires_grad and tuple(pred.shape) == (K, B, 3, nx)
@@ -332,7 +365,7 @@ def test_direct_step_equals_autograd_step(hf, through):
     from hybridflux import training
     nx, B, K = 64, 3, 4
     traj = dev(classical_windows(O.Grid(nx), B, K))
-    grid = hf.BaselineSolver(nx, device=DEV).grid
+    grid = grid_of(hf, nx)
     x, _ = grid.on(torch.device(DEV))
 
     def fresh():
