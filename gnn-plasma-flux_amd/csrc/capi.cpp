@@ -947,6 +947,27 @@ int hf_poisson(const float *n, int ld_n, float *E, int ld_E, const double *pc, i
   return hf_poisson_ex(n, ld_n, E, ld_E, pc, HF_POISSON_SPECTRAL, B, nx, stream);
 }
 
+int hf_initial_conditions(const int64_t *seeds, int B, int nx, const double *x, float *state, double *table,
+                          void *stream) {
+  if (B < 0 || nx < 1) return fail(HF_EINVAL, "hf_initial_conditions: bad shape");
+  if (nx > hf::kIcMaxNx) return fail(HF_EUNSUPPORTED, "hf_initial_conditions: nx > 2^24");
+  if (B == 0) return HF_OK;
+  if (!seeds || !x || !state) return fail(HF_EINVAL, "hf_initial_conditions: NULL pointer");
+  HF_CHECK_HIP(hf::launch_initial_conditions(seeds, B, nx, x, state, table, as_stream(stream)),
+               "hf_initial_conditions");
+  return HF_OK;
+}
+
+int hf_ic_draws_host(int64_t seed, int nx, double *table, double *gauss) {
+  if (seed < 0 || seed > 0xffffffffLL)
+    return fail(HF_EINVAL, "hf_ic_draws_host: Seed must be between 0 and 2**32 - 1");
+  if (nx < 1) return fail(HF_EINVAL, "hf_ic_draws_host: bad shape");
+  if (nx > hf::kIcMaxNx) return fail(HF_EUNSUPPORTED, "hf_ic_draws_host: nx > 2^24");
+  if (!table || !gauss) return fail(HF_EINVAL, "hf_ic_draws_host: NULL pointer");
+  if (!hf::ic_draws_host(seed, nx, table, gauss)) return fail(HF_EINVAL, "hf_ic_draws_host: bad argument");
+  return HF_OK;
+}
+
 int64_t hf_run_workspace_bytes(int op, int B, int nx, int T) {
   if (B < 0 || nx < 1 || T < 0 || op < HF_OP_STEP || op > HF_OP_COMPARE) return -1;
   const int64_t S = 4LL * 3 * nx, F = 4LL * nx, al = 256;

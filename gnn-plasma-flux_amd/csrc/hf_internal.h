@@ -344,6 +344,15 @@ hipError_t launch_state_metrics(const float *st, int64_t ld, int B, int nx, floa
 hipError_t launch_poisson(const float *n, int ld_n, float *E, int ld_E, const double *pc, int B,
                           int nx, int pm, hipStream_t s);
 
+// Initial conditions from numpy's MT19937 draws (initial_conditions.hip): rows
+// n and u of state [B][3][nx] for int64 seeds in [0, 2^32), one wave per seed;
+// table [B][HF_IC_TABLE_LEN] or NULL.  ic_draws_host: the same draws for one
+// seed on the host (table, gauss [nx]); false: out-of-range seed or nx.
+constexpr int kIcMaxNx = 1 << 24;
+hipError_t launch_initial_conditions(const int64_t *seeds, int B, int nx, const double *x, float *state, double *table,
+                                     hipStream_t s);
+bool ic_draws_host(int64_t seed, int nx, double *table, double *gauss);
+
 int64_t graph_workspace_bytes(const GraphW &w, int64_t N, int64_t E);
 // Training forward (activation tape) and backward, graph_train section of graph.hip.
 int64_t graph_tape_bytes(const GraphW &w, int64_t N, int64_t E);

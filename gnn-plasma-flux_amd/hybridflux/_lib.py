@@ -29,6 +29,7 @@ HF_WS_TRAJ = 1
 HF_WS_FLUX_FACE = 2
 HF_POISSON_SPECTRAL = 0
 HF_POISSON_TRIDIAG = 1
+HF_IC_TABLE_LEN = 23
 
 # name -> (restype, argtypes); mirrors include/hybridflux.h exactly.
 SIGNATURES = {
@@ -89,6 +90,8 @@ SIGNATURES = {
     "hf_poisson_plan_size": (c_int, [c_int, c_int]),
     "hf_poisson_plan": (c_int, [c_int, c_int, c_double, c_void_p]),
     "hf_poisson_ex": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "hf_initial_conditions": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "hf_ic_draws_host": (c_int, [c_int64, c_int, c_void_p, c_void_p]),
     "hf_run_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
     "hf_workspace_need": (c_int64, [c_void_p, c_int, c_int, c_int, c_int, c_int]),
     "hf_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,

@@ -39,7 +39,7 @@ class BaselineSolver:
         if self.dt / self.dx > 0.5:  # src/baseline_solver.py:23-24
             print("Warning: dt/dx may be large; consider reducing dt for stability.")
 
-    # -- initial conditions (host RNG, device Poisson) ---------------------------
+    # -- initial conditions (host RNG by default, device_rng=True: device RNG; device Poisson) --
     def _modes(self, seed):
         """n, u of src/baseline_solver.py:35-51 — MT19937 RandomState, same draws."""
         rs = np.random.RandomState(seed)
@@ -58,11 +58,19 @@ class BaselineSolver:
         u += 0.05 * rs.randn(self.nx).astype(np.float32)
         return n, u
 
-    def initial_condition(self, seed=None):
-        return self.initial_conditions([seed])[0]
+    def initial_condition(self, seed=None, device_rng=False):
+        return self.initial_conditions([seed], device_rng=device_rng)[0]
 
-    def initial_conditions(self, seeds, as_tensor=False):
-        """Batched ICs for a list of seeds -> [B,3,nx] (numpy, or a device tensor)."""
+    def initial_conditions(self, seeds, as_tensor=False, device_rng=False):
+        """Batched ICs for a list of seeds -> [B,3,nx] (numpy, or a device tensor).
+
+        device_rng=True draws them on the device (engine.initial_conditions: the
+        same MT19937 words, one launch over the batch) instead of one
+        RandomState per seed on the host; seeds are then integers in [0, 2^32)
+        (a range, list, numpy array or CPU tensor; None is refused)."""
+        if device_rng:
+            st = engine.initial_conditions(self.grid, seeds, device=self.device)
+            return st if as_tensor else st.cpu().numpy()
         nu = [self._modes(s) for s in seeds]
         if not nu:  # an empty shard (an IC-sharded job with more ranks than ICs)
             st = torch.zeros(0, 3, self.nx, dtype=torch.float32, device=self.device)

@@ -22,12 +22,13 @@ from .baseline_solver import BaselineSolver
 
 
 def generate_dataset(nx=64, num_initial_conditions=20, steps_per_ic=30, dt=5e-3, t_end=1.0, nu=1e-3,
-                     out_path="data/dataset.npz", device="cuda", seeds=None):
+                     out_path="data/dataset.npz", device="cuda", seeds=None, device_rng=False):
     """Returns (state_t, flux_t, state_next, x, dt, dx, nu) like the reference and
-    writes them to `out_path` (skipped when out_path is None)."""
+    writes them to `out_path` (skipped when out_path is None).  device_rng=True
+    draws the ICs on the device too (BaselineSolver.initial_conditions)."""
     solver = BaselineSolver(nx=nx, dt=dt, t_end=t_end, nu=nu, device=device)
     seeds = list(range(num_initial_conditions)) if seeds is None else list(seeds)
-    ics = solver.initial_conditions(seeds, as_tensor=True)
+    ics = solver.initial_conditions(seeds, as_tensor=True, device_rng=device_rng)
     r = solver.run_batch(ics, steps_per_ic, traj=True, flux=True)
     traj = r["traj"].cpu().numpy()                     # [N, steps+1, 3, nx]
     N = traj.shape[0]
@@ -44,12 +45,13 @@ def generate_dataset(nx=64, num_initial_conditions=20, steps_per_ic=30, dt=5e-3,
 
 
 def generate_trajectories(nx=64, num_initial_conditions=20, steps_per_ic=30, dt=5e-3, t_end=1.0, nu=1e-3,
-                          device="cuda", seeds=None):
+                          device="cuda", seeds=None, device_rng=False):
     """The classical trajectories themselves, [N, steps+1, 3, nx] float32 (numpy):
     the array generate_dataset computes and flattens into (state_t, state_next)
     pairs, kept whole for multi-step windows (training.WindowDataset).  Same
-    ICs, same batched rollout; x, dx are BaselineSolver(nx=nx).x / .dx."""
+    ICs, same batched rollout; x, dx are BaselineSolver(nx=nx).x / .dx.
+    device_rng=True draws the ICs on the device too."""
     solver = BaselineSolver(nx=nx, dt=dt, t_end=t_end, nu=nu, device=device)
     seeds = list(range(num_initial_conditions)) if seeds is None else list(seeds)
-    ics = solver.initial_conditions(seeds, as_tensor=True)
+    ics = solver.initial_conditions(seeds, as_tensor=True, device_rng=device_rng)
     return solver.run_batch(ics, steps_per_ic, traj=True)["traj"].cpu().numpy()

@@ -527,6 +527,59 @@ def poisson(grid, n):
     return E
 
 
+def ic_seeds(seeds):
+    """Seeds (a range, list, numpy array or CPU tensor of integers) -> int64
+    numpy array, validated on the host as np.random.RandomState validates an
+    integer seed.  None (numpy: seed from the OS) has no device counterpart."""
+    if seeds is None:
+        raise ValueError("device_rng needs integer seeds; seed=None draws from the OS and cannot be reproduced")
+    if isinstance(seeds, torch.Tensor):
+        if seeds.is_cuda:
+            raise ValueError("seeds must be on the host (they are validated there and uploaded once)")
+        seeds = seeds.numpy()
+    if not isinstance(seeds, np.ndarray):
+        seeds = list(seeds)
+        if any(s is None for s in seeds):
+            raise ValueError("device_rng needs integer seeds; seed=None draws from the OS and cannot be reproduced")
+        seeds = np.asarray(seeds) if seeds else np.zeros(0, dtype=np.int64)
+    if seeds.dtype.kind not in "iu":
+        if seeds.dtype.kind != "O":
+            raise TypeError(f"seeds must be integers, got dtype {seeds.dtype}")
+        import operator
+        seeds = np.asarray([operator.index(s) for s in seeds.reshape(-1)], dtype=object)  # (ints beyond int64)
+    seeds = seeds.reshape(-1)
+    if seeds.size and (seeds.min() < 0 or seeds.max() > 0xFFFFFFFF):
+        raise ValueError("Seed must be between 0 and 2**32 - 1")
+    return np.ascontiguousarray(seeds.astype(np.int64))
+
+
+def initial_conditions(grid, seeds, debug=False, device=None):
+    """ICs of src/baseline_solver.py:29-57 for integer seeds, drawn on the device
+    (hf_initial_conditions: numpy's MT19937 words, one wave per seed) -> state
+    [B,3,nx] with E = poisson(grid, n).  debug: also the draw table [B,
+    HF_IC_TABLE_LEN] float64 (mode count, (km, amp, ph) x 7, words consumed;
+    include/hybridflux.h), which equals numpy's draws exactly."""
+    s = ic_seeds(seeds)
+    if device is None:
+        if not torch.cuda.is_available():
+            raise RuntimeError("hybridflux: no HIP device is visible; this engine has no CPU path")
+        device = torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    B, nx = int(s.size), grid.nx
+    st = torch.empty(B, 3, nx, dtype=torch.float32, device=device)
+    table = torch.empty(B, _lib.HF_IC_TABLE_LEN, dtype=torch.float64, device=device) if debug else None
+    if B:
+        key = ("x64", str(device))
+        if key not in grid._dev:
+            grid._dev[key] = torch.as_tensor(grid.x, dtype=torch.float64, device=device)
+        sd = torch.as_tensor(s, device=device)
+        with torch.cuda.device(device):
+            check(lib().hf_initial_conditions(ptr(sd), B, nx, ptr(grid._dev[key]), ptr(st), ptr(table),
+                                              stream_of(device)))
+        st[:, 2] = poisson(grid, st[:, 0])
+    return (st, table) if debug else st
+
+
 def _series(t, shape_tail, what):
     require_device(t, what)
     if t.dtype != torch.float32 or tuple(t.shape[2:]) != shape_tail or not t.is_contiguous():

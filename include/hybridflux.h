@@ -652,6 +652,42 @@ int hf_poisson_ex(const float *dev_n, int ld_n, float *dev_E, int ld_E, const do
                   int poisson_mode, int B, int nx, void *stream);
 
 /*
+ * Initial conditions on the device.
+ * Replaces: the per-seed host loop over BaselineSolver.initial_condition
+ * (src/baseline_solver.py:29-51): np.random.RandomState(seed), 3-5 sine modes
+ * on n, two cosine modes and 0.05 * randn(nx) on u.  The kernel consumes the
+ * 32-bit words of MT19937 exactly as numpy's legacy RandomState does
+ * (init_genrand seeding; randint by masked rejection, one word per try; rand
+ * from two words; the polar gauss, four words per attempt) and evaluates
+ *   n[i] = 1 + sum_m f32(amp_m) * f32(sin(km_m x[i] + ph_m))
+ *   u[i] = sum_m f32(amp_m) * f32(cos(km_m x[i] + ph_m)) + f32(0.05) * f32(gauss[i])
+ * with the argument and sin / cos in float64 and every product and sum in
+ * float32, in the reference's order.  One wave per seed.  Rows n and u of
+ * dev_state [B][3][nx] are written; row E is left alone (hf_poisson fills it).
+ *
+ * dev_seeds: [B] int64, each in [0, 2^32) (numpy's integer-seed path); dev_x:
+ * [nx] float64 cell centres.  numpy's rejection loops have no bound; here each
+ * randint gives up after 64 tries and the gauss after 2 nx + 256 attempts
+ * (probability < 4^-64 with a correct generator), and an IC whose draws gave
+ * up, or whose seed is out of range, gets NaN in every cell of n and u.
+ *
+ * dev_table (or NULL): [B][HF_IC_TABLE_LEN] float64, per IC
+ *   [0]          number of n modes (3..5; -1: the draws gave up)
+ *   [1 + 3 s..]  (km, amp, ph) of slot s: s = 0..4 the n modes (unused: 0),
+ *                s = 5, 6 the two u modes
+ *   [22]         32-bit words consumed
+ * None of it passes through sin, cos or log, so it equals numpy's exactly.
+ *
+ * hf_ic_draws_host: host only (no device work), the same draw code for one
+ * seed: host_table [HF_IC_TABLE_LEN] as above and host_gauss [nx] float64, the
+ * values of randn(nx) after the mode draws.
+ */
+#define HF_IC_TABLE_LEN 23
+int hf_initial_conditions(const int64_t *dev_seeds, int B, int nx, const double *dev_x, float *dev_state,
+                          double *dev_table /* or NULL */, void *stream);
+int hf_ic_draws_host(int64_t seed, int nx, double *host_table, double *host_gauss);
+
+/*
  * Scratch of the generic (non-fused) sequencing.  hf_step, hf_run and
  * hf_run_compare take (dev_workspace, workspace_bytes): a device buffer of at
  * least hf_workspace_need(model, op, B, nx, T, flags) bytes (or the upper
