@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -502,6 +503,29 @@ int hf_adam_flat(float *params, const float *grads, float *exp_avg, float *exp_a
   HF_CHECK_HIP(hf::launch_adam_flat(params, grads, exp_avg, exp_avg_sq, n, step, done, lr, beta1, beta2, eps,
                                     as_stream(stream)),
                "hf_adam_flat");
+  return HF_OK;
+}
+
+int64_t hf_adam_flat_workspace_bytes(int64_t n) {
+  if (n < 0) return -1;
+  return hf::adam_flat_ws_bytes(n);
+}
+
+int hf_adam_flat_ex(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, int64_t n, float *step,
+                    unsigned *done, const float *dev_lr, float lr, float beta1, float beta2, float eps,
+                    float weight_decay, float max_norm, int skip_nonfinite, void *ws, float *stats, void *stream) {
+  if (n < 0) return fail(HF_EINVAL, "hf_adam_flat_ex: n < 0");
+  if (!(max_norm > 0.f)) return fail(HF_EINVAL, "hf_adam_flat_ex: max_norm must be > 0 (INFINITY: no clipping)");
+  if (!(weight_decay >= 0.f)) return fail(HF_EINVAL, "hf_adam_flat_ex: weight_decay must be >= 0");
+  if (n > 0 && (!params || !grads || !exp_avg || !exp_avg_sq || !step || !done))
+    return fail(HF_EINVAL, "hf_adam_flat_ex: NULL pointer");
+  if (n > 0 && !ws && (max_norm <= std::numeric_limits<float>::max() || skip_nonfinite || stats))
+    return fail(HF_EINVAL, "hf_adam_flat_ex: clipping, skip_nonfinite and dev_stats need the workspace");
+  if (n == 0) return HF_OK;
+  HF_CHECK_HIP(hf::launch_adam_flat_ex(params, grads, exp_avg, exp_avg_sq, n, step, done, dev_lr, lr, beta1, beta2,
+                                       eps, weight_decay, max_norm, skip_nonfinite ? 1 : 0, ws, stats,
+                                       as_stream(stream)),
+               "hf_adam_flat_ex");
   return HF_OK;
 }
 

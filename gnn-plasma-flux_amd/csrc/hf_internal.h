@@ -401,9 +401,15 @@ constexpr int kLossMaxRollout = 3;  // rollout energy term in the loss kernels: 
 hipError_t launch_chain_batch_gather(const int64_t *idx, int B, const float *st_all, const float *ft_all,
                                      const float *sn_all, int64_t N, int nx, const float *x, float *st, float *ft,
                                      float *sn, float *nf, hipStream_t s);
-// Adam over one flat parameter buffer, step count on the device (train_chain.hip).
+// Adam over one flat parameter buffer, step count on the device (optim.hip); _ex: the
+// guarded step (clip by the global norm, weight decay, device lr, non-finite skip), with
+// the norm's launch when ws (adam_flat_ws_bytes of float64 partials) is given.
 hipError_t launch_adam_flat(float *p, const float *g, float *m, float *v, int64_t n, float *step, unsigned *done,
                             float lr, float b1, float b2, float eps, hipStream_t s);
+int64_t adam_flat_ws_bytes(int64_t n);
+hipError_t launch_adam_flat_ex(float *p, const float *g, float *m, float *v, int64_t n, float *step, unsigned *done,
+                               const float *dev_lr, float lr, float b1, float b2, float eps, float wd, float max_norm,
+                               int skip, void *ws, float *stats, hipStream_t s);
 hipError_t launch_graph_flux(const GraphW &w, const float *nf, int64_t N, const int64_t *ei,
                              int64_t E, float *flux, void *ws, hipStream_t s);
 

@@ -30,6 +30,7 @@ HF_WS_FLUX_FACE = 2
 HF_POISSON_SPECTRAL = 0
 HF_POISSON_TRIDIAG = 1
 HF_IC_TABLE_LEN = 23
+HF_OPT_NUM_STATS = 4
 
 # name -> (restype, argtypes); mirrors include/hybridflux.h exactly.
 SIGNATURES = {
@@ -131,6 +132,9 @@ SIGNATURES = {
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hf_adam_flat": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_float, c_float,
                              c_float, c_float, c_void_p]),
+    "hf_adam_flat_workspace_bytes": (c_int64, [c_int64]),
+    "hf_adam_flat_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_float,
+                                c_float, c_float, c_float, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p]),
     "hf_unroll_workspace_bytes": (c_int64, [c_int, c_int]),
     "hf_unroll_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int64,

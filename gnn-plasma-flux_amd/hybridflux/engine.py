@@ -685,6 +685,55 @@ def adam_flat(params, grads, exp_avg, exp_avg_sq, step, done, lr, beta1, beta2, 
                                  float(lr), float(beta1), float(beta2), float(eps), stream_of(dev)))
 
 
+OPT_NUM_STATS = _lib.HF_OPT_NUM_STATS
+
+
+def adam_flat_workspace(n, dev):
+    """hf_adam_flat_workspace_bytes of scratch (the norm's float64 partials) for
+    adam_flat_ex on `dev`, as a float64 tensor."""
+    nb = int(lib().hf_adam_flat_workspace_bytes(n))
+    if nb < 0:
+        raise ValueError(f"adam_flat workspace: need n >= 0 (n = {n})")
+    return torch.empty(nb // 8, dtype=torch.float64, device=dev)
+
+
+def adam_flat_ex(params, grads, exp_avg, exp_avg_sq, step, done, lr, beta1, beta2, eps, weight_decay=0.0,
+                 max_norm=float("inf"), skip_nonfinite=False, ws=None, stats=None):
+    """hf_adam_flat_ex: the guarded step on one flat float32 parameter buffer --
+    clip_grad_norm_(max_norm) + torch.optim.AdamW(weight_decay) + the skip of a
+    step whose gradient norm is not finite, in two launches without a host
+    sync.  lr: a float, or a one-element float32 device tensor the kernel reads
+    at launch time (so a captured step follows a scheduler).  ws:
+    adam_flat_workspace(n) (needed for clipping, skipping and stats); stats:
+    float32 [4] = (norm, coef, skipped, skipped so far), zeroed before the
+    first step; the other arguments as adam_flat."""
+    tensors = [(params, "params"), (grads, "grads"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq"),
+               (step, "step"), (done, "done")]
+    dev_lr = lr if isinstance(lr, torch.Tensor) else None
+    tensors += [(t, what) for t, what in ((dev_lr, "lr"), (ws, "ws"), (stats, "stats")) if t is not None]
+    dev = params.device
+    for t, what in tensors:
+        require_device(t, what)
+        if not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"adam_flat_ex: {what} must be contiguous and on the parameters' device")
+    n = params.numel()
+    if any(t.numel() != n or t.dtype != torch.float32 for t in (grads, exp_avg, exp_avg_sq)) or \
+            params.dtype != torch.float32 or step.dtype != torch.float32 or step.numel() < 1 or done.numel() * \
+            done.element_size() < 4:
+        raise ValueError("adam_flat_ex: float32 buffers of one size, a float32 step and a 4-byte done counter")
+    if dev_lr is not None and (dev_lr.dtype != torch.float32 or dev_lr.numel() != 1):
+        raise ValueError("adam_flat_ex: a tensor lr must hold one float32")
+    if stats is not None and (stats.dtype != torch.float32 or stats.numel() < OPT_NUM_STATS):
+        raise ValueError(f"adam_flat_ex: stats must hold {OPT_NUM_STATS} float32")
+    if ws is not None and ws.numel() * ws.element_size() < int(lib().hf_adam_flat_workspace_bytes(n)):
+        raise ValueError("adam_flat_ex: the workspace is smaller than hf_adam_flat_workspace_bytes(n)")
+    with torch.cuda.device(dev):
+        check(lib().hf_adam_flat_ex(ptr(params), ptr(grads), ptr(exp_avg), ptr(exp_avg_sq), n, ptr(step), ptr(done),
+                                    ptr(dev_lr), 0.0 if dev_lr is not None else float(lr), float(beta1), float(beta2),
+                                    float(eps), float(weight_decay), float(max_norm), int(bool(skip_nonfinite)),
+                                    ptr(ws), ptr(stats), stream_of(dev)))
+
+
 def unroll_workspace(B, nx, dev):
     """hf_unroll_workspace_bytes of scratch for unroll_update on `dev` (a uint8 tensor)."""
     nb = int(lib().hf_unroll_workspace_bytes(B, nx))

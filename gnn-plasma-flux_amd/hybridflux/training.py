@@ -270,10 +270,34 @@ class FlatAdam(torch.optim.Optimizer):
     parameter in one HIP launch (hf_adam_flat) with the step count on the
     device, so it is capturable (GraphedStep) and needs no host sync.  The
     gradients are read as one buffer when they are (the chain training
-    backward returns them as pieces of one), otherwise concatenated first."""
+    backward returns them as pieces of one), otherwise concatenated first.
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
+    The keyword options guard the step on the device (hf_adam_flat_ex; two
+    launches, still no host sync, still capturable): max_grad_norm clips the
+    gradient by its global L2 norm (torch.nn.utils.clip_grad_norm_'s
+    arithmetic), weight_decay is torch.optim.AdamW's decoupled decay, and
+    skip_nonfinite leaves parameters, moments and step count untouched when
+    the gradient norm is inf or NaN.  lr may be a one-element float32 tensor:
+    it is moved to the parameters' device once and the kernel reads it there,
+    so a torch.optim.lr_scheduler (which fills a tensor lr in place) also
+    drives a captured step.  With clipping or skipping on, last_stats is the
+    device tensor [4] = (norm before clipping, coefficient applied, skipped
+    0/1, skipped steps so far) of the most recent step (state["stats"], saved
+    and loaded with the rest); otherwise it is None.  With the three options
+    at their defaults and a float lr the step is the one hf_adam_flat launch."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, *, weight_decay=0.0, max_grad_norm=None,
+                 skip_nonfinite=False):
+        if not float(weight_decay) >= 0.0:
+            raise ValueError(f"FlatAdam: weight_decay must be >= 0, got {weight_decay}")
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError(f"FlatAdam: max_grad_norm must be > 0 (None: no clipping), got {max_grad_norm}")
+        if isinstance(lr, torch.Tensor) and lr.numel() != 1:
+            raise ValueError("FlatAdam: a tensor lr must hold one value")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=float(weight_decay),
+                                      max_grad_norm=None if max_grad_norm is None else float(max_grad_norm),
+                                      skip_nonfinite=bool(skip_nonfinite)))
+        self._ws = {}
         for group in self.param_groups:
             ps = group["params"]
             flat = flat_view(ps, ps[0].device)
@@ -286,6 +310,47 @@ class FlatAdam(torch.optim.Optimizer):
             st["step"] = torch.zeros(1, dtype=torch.float32, device=flat.device)
             # the kernel's done-counter: 4 zero bytes (float32 so that load_state_dict's cast keeps them 0)
             st["done"] = torch.zeros(1, dtype=torch.float32, device=flat.device)
+            if self._needs_norm(group):
+                st["stats"] = torch.zeros(engine.OPT_NUM_STATS, dtype=torch.float32, device=flat.device)
+            if isinstance(group["lr"], torch.Tensor):
+                group["lr"] = self._device_lr(group["lr"], flat.device)
+
+    @staticmethod
+    def _needs_norm(group):
+        return group.get("max_grad_norm") is not None or bool(group.get("skip_nonfinite"))
+
+    @staticmethod
+    def _device_lr(lr, dev):
+        """A tensor lr as float32 on dev: the tensor itself when it already is."""
+        if lr.device == dev and lr.dtype == torch.float32 and lr.is_contiguous() and not lr.requires_grad:
+            return lr
+        return lr.detach().to(device=dev, dtype=torch.float32).contiguous()
+
+    @property
+    def guarded(self):
+        """Some group clips or skips: its steps write last_stats."""
+        return any(self._needs_norm(g) for g in self.param_groups)
+
+    @property
+    def last_stats(self):
+        """The most recent step's statistics [4] on the device (of the first
+        group that keeps them; it is overwritten by the next step), or None."""
+        for group in self.param_groups:
+            st = self.state[group["params"][0]]
+            if "stats" in st:
+                return st["stats"]
+        return None
+
+    def load_state_dict(self, state_dict):
+        """torch's, except that a tensor lr keeps its address (a captured step
+        reads it there): the loaded value is copied into it."""
+        held = [g["lr"] for g in self.param_groups]
+        super().load_state_dict(state_dict)
+        for group, lr in zip(self.param_groups, held):
+            if isinstance(lr, torch.Tensor):
+                new = group["lr"]
+                lr.copy_(new.reshape(lr.shape) if isinstance(new, torch.Tensor) else torch.as_tensor(float(new)))
+                group["lr"] = lr
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -293,7 +358,7 @@ class FlatAdam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        for group in self.param_groups:
+        for gi, group in enumerate(self.param_groups):
             ps = group["params"]
             st = self.state[ps[0]]
             flat = flat_view(ps, ps[0].device)
@@ -301,20 +366,84 @@ class FlatAdam(torch.optim.Optimizer):
                 raise RuntimeError("FlatAdam: the parameters no longer share one buffer (moved or re-created?)")
             if any(p.grad is None for p in ps):
                 raise RuntimeError("FlatAdam: every parameter needs a gradient")
-            for k in ("exp_avg", "exp_avg_sq", "step", "done"):  # (a state_dict loaded elsewhere)
+            norm = self._needs_norm(group)
+            if norm and "stats" not in st:  # (options switched on later, or a plain optimizer's state loaded)
+                st["stats"] = torch.zeros(engine.OPT_NUM_STATS, dtype=torch.float32, device=flat.device)
+            for k in ("exp_avg", "exp_avg_sq", "step", "done") + (("stats",) if "stats" in st else ()):
                 if st[k].device != flat.device or st[k].dtype != torch.float32 or not st[k].is_contiguous():
+                    # (a state_dict loaded elsewhere)
                     st[k] = st[k].to(device=flat.device, dtype=torch.float32).contiguous()
             g = flat_view([p.grad for p in ps], ps[0].device)
             if g is None:
                 g = torch.cat([p.grad.reshape(-1) for p in ps])
             b1, b2 = group["betas"]
-            engine.adam_flat(flat, g, st["exp_avg"], st["exp_avg_sq"], st["step"], st["done"], group["lr"],
-                             b1, b2, group["eps"])
+            lr, wd = group["lr"], group.get("weight_decay", 0.0)
+            if isinstance(lr, torch.Tensor):
+                lr = group["lr"] = self._device_lr(lr, flat.device)
+            if not norm and wd == 0.0 and not isinstance(lr, torch.Tensor):
+                engine.adam_flat(flat, g, st["exp_avg"], st["exp_avg_sq"], st["step"], st["done"], lr, b1, b2,
+                                 group["eps"])
+            else:
+                ws = None
+                if norm:
+                    ws = self._ws.get(gi)
+                    if ws is None or ws.device != flat.device:
+                        ws = self._ws[gi] = engine.adam_flat_workspace(flat.numel(), flat.device)
+                max_norm = group.get("max_grad_norm")
+                engine.adam_flat_ex(flat, g, st["exp_avg"], st["exp_avg_sq"], st["step"], st["done"], lr, b1, b2,
+                                    group["eps"], wd, float("inf") if max_norm is None else max_norm,
+                                    bool(group.get("skip_nonfinite")), ws, st["stats"] if norm else None)
             # the kernel wrote the parameters behind autograd's back: bump their
             # version counters as an in-place torch update would, so that a packed
             # inference copy (FluxGNN.device_model keys on _version) is rebuilt
             torch.autograd.graph.increment_version(ps)
         return loss
+
+
+class _StepStats:
+    """The statistics of a guarded optimizer's steps over one epoch: each step's
+    last_stats is copied on the device (note) and all are read in the epoch's one
+    host sync (read), which appends the epoch's grad_norm_max and skipped_steps to
+    the trainer's history.  Off -- no key, nothing copied or read -- for any other
+    optimizer."""
+
+    def __init__(self, opt, history):
+        self.opt = opt if isinstance(opt, FlatAdam) and opt.guarded else None
+        self.history, self.rows, self.weights, self.weight = history, [], [], 0
+        if self.opt is not None:
+            history.update(grad_norm_max=[], skipped_steps=[])
+
+    def __bool__(self):
+        return self.opt is not None
+
+    def note(self, weight=1):
+        """After a step over `weight` samples."""
+        if self.opt is not None:
+            self.rows.append(self.opt.last_stats.clone())
+            self.weights.append(weight)
+
+    def read(self):
+        """Per step of the epoch whether it was applied; `weight` becomes the
+        samples of those steps.  grad_norm_max is taken over the applied steps."""
+        rows = torch.stack(self.rows).tolist() if self.rows else []
+        applied = [r[2] == 0.0 for r in rows]
+        norms = [r[0] for r, a in zip(rows, applied) if a]
+        self.history["grad_norm_max"].append(max(norms, key=lambda v: (v != v, v)) if norms else 0.0)  # (a NaN wins)
+        self.history["skipped_steps"].append(len(rows) - sum(applied))
+        self.weight = sum(w for w, a in zip(self.weights, applied) if a)
+        self.rows, self.weights = [], []
+        return applied
+
+
+def _guarded_optimizer(params, lr, weight_decay, max_grad_norm, skip_nonfinite, scheduler, device):
+    """The trainers' FlatAdam and its scheduler (None without one): with a
+    scheduler -- a callable opt -> torch.optim.lr_scheduler.LRScheduler -- lr is a
+    device tensor, which the scheduler's steps rewrite in place."""
+    if scheduler is not None:
+        lr = torch.full((), float(lr), dtype=torch.float32, device=device)
+    opt = FlatAdam(params, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
+                   skip_nonfinite=skip_nonfinite)
+    return opt, (scheduler(opt) if scheduler is not None else None)
 
 
 def direct_step(model, opt, st, ft, sn, nf, x, dt, dx, cfg, grid):
@@ -406,14 +535,17 @@ class GraphedStep:
         return self.out[0].clone(), self.out[1].clone()
 
 
-def train_steps(model, opt, data, order, batch_size, x, dt, dx, cfg, grid, graphed=None, warmup=3, direct=True):
+def train_steps(model, opt, data, order, batch_size, x, dt, dx, cfg, grid, graphed=None, warmup=3, direct=True,
+                stats=None):
     """One pass over `order` (sample indices) in batches; returns (sum of
     losses, sum of flux losses) weighted by batch size, and the step count.
     graphed: a GraphedStep of this batch size (created by the caller and kept
     across passes); its first `warmup` steps run eagerly on a side stream, then
     it is captured and every further full batch replays the graph.  direct:
     eager steps take direct_step where it applies (the same parameters bit for
-    bit as the autograd step)."""
+    bit as the autograd step).  stats: the trainer's _StepStats; with a guarded
+    FlatAdam the sums then run over the steps that were applied (stats.weight
+    samples)."""
     tot, tot_flux, steps = 0.0, 0.0, 0
     losses = []
     data.check_indices(order)  # once per pass; the steps gather with check=False
@@ -444,7 +576,11 @@ def train_steps(model, opt, data, order, batch_size, x, dt, dx, cfg, grid, graph
                 opt.step()
                 loss, flux_loss = loss.detach(), flux_loss.detach()
         losses.append((loss, flux_loss, len(idx)))
+        if stats is not None:
+            stats.note(len(idx))
         steps += 1
+    if stats:
+        losses = [row for row, a in zip(losses, stats.read()) if a]
     for l, f, n in losses:  # one host sync per pass, not per step
         tot += float(l) * n
         tot_flux += float(f) * n
@@ -452,10 +588,16 @@ def train_steps(model, opt, data, order, batch_size, x, dt, dx, cfg, grid, graph
 
 
 def train_model(state_t, flux_t, state_next, x, dt, dx, nu, config_name, stencil_radius, epochs=20, lr=1e-3,
-                device="cuda", batch_size=1, seed=None, save_dir="checkpoints", log=print):
+                device="cuda", batch_size=1, seed=None, save_dir="checkpoints", log=print, weight_decay=0.0,
+                max_grad_norm=None, skip_nonfinite=False, scheduler=None):
     """scripts/training/train_ablation.py:64-237 on the MI355X.  Returns
     (model, history) and writes checkpoints/hybrid_<config>_r<radius>.pt and
-    history_<config>_r<radius>.json like the reference (save_dir=None skips)."""
+    history_<config>_r<radius>.json like the reference (save_dir=None skips).
+    weight_decay, max_grad_norm, skip_nonfinite: FlatAdam's guard options;
+    scheduler: a callable opt -> torch.optim.lr_scheduler.LRScheduler, stepped
+    once per epoch.  With max_grad_norm or skip_nonfinite the history gains
+    grad_norm_max and skipped_steps per epoch, and the epoch's losses are means
+    over the samples of the steps that were applied."""
     cfg = ABLATION_CONFIGS[config_name]
     engine.require_device(torch.empty(0, device=device), "device")
     if seed is not None:
@@ -465,18 +607,24 @@ def train_model(state_t, flux_t, state_next, x, dt, dx, nu, config_name, stencil
     x_dev = torch.as_tensor(np.asarray(x, dtype=np.float32), device=device)
     model = FluxGNN(MODEL_CONFIG["input_dim"], MODEL_CONFIG["hidden_dim"], MODEL_CONFIG["num_layers"]).to(device)
     model.flatten_parameters_()  # one parameter buffer: no per-step concat in the training forward
-    opt = FlatAdam(model.parameters(), lr=lr)  # torch.optim.Adam's update (:82), one launch per step
+    # torch.optim.Adam's update (:82), one launch per step
+    opt, sched = _guarded_optimizer(model.parameters(), lr, weight_decay, max_grad_norm, skip_nonfinite, scheduler,
+                                    device)
     gen = torch.Generator().manual_seed(0 if seed is None else seed)
     history = {"epoch": [], "loss": [], "flux_loss": [], "seconds": []}
+    stats = _StepStats(opt, history)
     model.train()
     for epoch in range(1, epochs + 1):
         order = torch.randperm(len(data), generator=gen).to(device)
         t0 = time.perf_counter()
-        tot, tot_flux, _ = train_steps(model, opt, data, order, batch_size, x_dev, dt, dx, cfg, grid)
+        tot, tot_flux, _ = train_steps(model, opt, data, order, batch_size, x_dev, dt, dx, cfg, grid, stats=stats)
+        count = stats.weight if stats else len(data)
         torch.cuda.synchronize(device)
+        if sched is not None:
+            sched.step()
         history["epoch"].append(epoch)
-        history["loss"].append(tot / len(data))
-        history["flux_loss"].append(tot_flux / len(data))
+        history["loss"].append(tot / count if count else float("nan"))
+        history["flux_loss"].append(tot_flux / count if count else float("nan"))
         history["seconds"].append(time.perf_counter() - t0)
         if log:
             log(f"[Epoch {epoch}/{epochs}] Loss: {history['loss'][-1]:.6e}, Flux: {history['flux_loss'][-1]:.6e}")
@@ -557,14 +705,17 @@ def _stage_states(state_t, state_next, device):
 
 
 def train_pure_gnn(state_t, state_next, x, epochs=50, lr=1e-3, batch_size=32, hidden_dim=None, num_layers=None,
-                   device="cuda", order=None, seed=None, log=None):
+                   device="cuda", order=None, seed=None, log=None, weight_decay=0.0, max_grad_norm=None,
+                   skip_nonfinite=False, scheduler=None):
     """scripts/training/train_pure_gnn.py:79-151 on the MI355X: PureGNN(4,
     hidden_dim, num_layers) (default MODEL_CONFIG's, :94-98), Adam(lr), batches
     of batch_size samples in a shuffled order (the last one may be partial),
     the epoch's history entry the mean of its batch losses (:147-150).  Each
     batch is one batched step (pure_gnn_step).  order: per epoch an explicit
     sample order (a sequence of `epochs` index sequences) instead of the
-    shuffle.  Returns (model, {'loss': [...]})."""
+    shuffle.  Returns (model, {'loss': [...]}).  weight_decay, max_grad_norm,
+    skip_nonfinite, scheduler: as train_model's (the mean then runs over the
+    batches whose step was applied)."""
     engine.require_device(torch.empty(0, device=device), "device")
     if seed is not None:
         torch.manual_seed(seed)
@@ -574,24 +725,48 @@ def train_pure_gnn(state_t, state_next, x, epochs=50, lr=1e-3, batch_size=32, hi
     model = PureGNN(MODEL_CONFIG["input_dim"], hidden_dim or MODEL_CONFIG["hidden_dim"],
                     MODEL_CONFIG["num_layers"] if num_layers is None else num_layers).to(device)
     model.flatten_parameters_()
-    opt = FlatAdam(model.parameters(), lr=lr)
+    opt, sched = _guarded_optimizer(model.parameters(), lr, weight_decay, max_grad_norm, skip_nonfinite, scheduler,
+                                    device)
     gen = torch.Generator().manual_seed(0 if seed is None else seed)
     history = {"loss": []}
+    stats = _StepStats(opt, history)
     model.train()
     for epoch in range(epochs):
         perm = torch.randperm(n, generator=gen) if order is None else torch.as_tensor(order[epoch], dtype=torch.int64)
         if perm.numel() and (int(perm.min()) < -n or int(perm.max()) >= n):
             raise IndexError(f"sample index out of range for a dataset of {n} samples")
         perm = perm.to(device)
-        total, nb = torch.zeros((), device=device), 0
+        total, nb, each = torch.zeros((), device=device), 0, []
         for k in range(0, perm.numel(), batch_size):
             idx = perm[k:k + batch_size]
-            total += pure_gnn_step(model, opt, st_all[idx], sn_all[idx], x_dev)
+            loss = pure_gnn_step(model, opt, st_all[idx], sn_all[idx], x_dev)
+            if stats:
+                each.append(loss)
+                stats.note()
+            else:
+                total += loss
             nb += 1
-        history["loss"].append(float(total) / max(nb, 1))
+        if stats:
+            history["loss"].append(_applied_mean(each, stats.read()))
+        else:
+            history["loss"].append(float(total) / max(nb, 1))
+        if sched is not None:
+            sched.step()
         if log:
             log(f"Epoch {epoch + 1}/{epochs}, Loss: {history['loss'][-1]:.6f}")
     return model, history
+
+
+def _applied_mean(values, applied):
+    """The mean of the device values (scalars or vectors of one size) of the
+    steps that were applied, read in one transfer; NaN when none was."""
+    rows = torch.stack(values).tolist() if values else []
+    rows = [r for r, a in zip(rows, applied) if a]
+    if not rows:
+        return float("nan")
+    if isinstance(rows[0], list):
+        return [sum(col) / len(rows) for col in zip(*rows)]
+    return sum(rows) / len(rows)
 
 
 # -------------------------------------------------------- unrolled training
@@ -778,11 +953,15 @@ def _rollout_step(m, model, opt, traj, x, grid, channel_weights, through_state):
 
 
 def _train_windows(m, model, data, x, grid, init, epochs, lr, batch_size, seed, channel_weights, through_state,
-                   device, save_dir, log):
+                   device, save_dir, log, guard=(0.0, None, False, None)):
     """The K-step trainers' loop: Adam(lr) over shuffled batches of batch_size
     windows of data (a WindowDataset), one direct step each (the autograd step
     where that does not apply), one host sync per epoch.  model: the freshly
-    initialised host model; init: a state dict to load into it first."""
+    initialised host model; init: a state dict to load into it first.  guard:
+    (weight_decay, max_grad_norm, skip_nonfinite, scheduler) as train_model's;
+    with clipping or skipping on the epoch's loss is the mean over the windows
+    of the steps that were applied, and the history gains grad_norm_max and
+    skipped_steps."""
     K = data.K
     x_dev = torch.as_tensor(np.asarray(x, dtype=np.float32), device=device) if x is not None else None
     if init is not None:
@@ -790,9 +969,10 @@ def _train_windows(m, model, data, x, grid, init, epochs, lr, batch_size, seed, 
                                for k, v in init.items()})
     model = model.to(device)
     model.flatten_parameters_()
-    opt = FlatAdam(model.parameters(), lr=lr)
+    opt, sched = _guarded_optimizer(model.parameters(), lr, *guard, device)
     gen = torch.Generator().manual_seed(0 if seed is None else seed)
     history = {"epoch": [], "loss": [], "seconds": []}
+    stats = _StepStats(opt, history)
     model.train()
     for epoch in range(1, epochs + 1):
         order = torch.randperm(len(data), generator=gen).to(device)
@@ -808,10 +988,17 @@ def _train_windows(m, model, data, x, grid, init, epochs, lr, batch_size, seed, 
                 opt.step()
                 loss = loss.detach()
             losses.append((loss, win.shape[0]))
+            stats.note(win.shape[0])
+        count = len(data)
+        if stats:
+            losses = [row for row, a in zip(losses, stats.read()) if a]
+            count = stats.weight
         tot = sum(float(l) * n for l, n in losses)  # one host sync per epoch
         torch.cuda.synchronize(device)
+        if sched is not None:
+            sched.step()
         history["epoch"].append(epoch)
-        history["loss"].append(tot / len(data))
+        history["loss"].append(tot / count if count else float("nan"))
         history["seconds"].append(time.perf_counter() - t0)
         if log:
             log(f"[Epoch {epoch}/{epochs}] {m.log_label} (K = {K}): {history['loss'][-1]:.6e}")
@@ -896,7 +1083,7 @@ class WindowDataset:
 
 def train_unrolled(trajectories, x, dt, dx, nu, K=4, epochs=10, lr=1e-3, batch_size=32, seed=None, init=None,
                    channel_weights=(1.0, 1.0, 1.0), through_state=True, device="cuda", save_dir="checkpoints",
-                   log=print):
+                   log=print, weight_decay=0.0, max_grad_norm=None, skip_nonfinite=False, scheduler=None):
     """Train (or fine-tune) FluxGNN on K-step windows of classical trajectories
     [N,T+1,3,nx] (datagen.generate_trajectories) with the unrolled loss: Adam(lr)
     over shuffled batches of batch_size windows, one unrolled_step each.  init:
@@ -904,7 +1091,9 @@ def train_unrolled(trajectories, x, dt, dx, nu, K=4, epochs=10, lr=1e-3, batch_s
     Returns (model, history) with history keys epoch, loss (the mean over the
     epoch's windows), seconds, and writes checkpoints/hybrid_unrolled_K<K>.pt
     and history_unrolled_K<K>.json as train_model writes its files (save_dir=None
-    skips)."""
+    skips).  weight_decay, max_grad_norm, skip_nonfinite, scheduler: as
+    train_model's -- the guard that keeps one window whose rollout blows up from
+    turning every parameter into NaN."""
     engine.require_device(torch.empty(0, device=device), "device")
     if seed is not None:
         torch.manual_seed(seed)
@@ -914,7 +1103,8 @@ def train_unrolled(trajectories, x, dt, dx, nu, K=4, epochs=10, lr=1e-3, batch_s
         raise ValueError(f"dx = {dx} is not the periodic grid's {grid.dx} for nx = {data.nx}")
     model = FluxGNN(MODEL_CONFIG["input_dim"], MODEL_CONFIG["hidden_dim"], MODEL_CONFIG["num_layers"])
     return _train_windows(_FLUX, model, data, x, grid, init, epochs, lr, batch_size, seed, channel_weights,
-                          through_state, device, save_dir, log)
+                          through_state, device, save_dir, log,
+                          (weight_decay, max_grad_norm, skip_nonfinite, scheduler))
 
 
 def pure_unrolled_loss(model, traj, x, channel_weights=(1.0, 1.0, 1.0), through_state=True, return_states=False):
@@ -957,7 +1147,8 @@ def pure_unrolled_train_flop_per_sample(K=4, nx=64, H=128, L=4, F=4):
 
 def train_pure_gnn_unrolled(trajectories, x, K=4, epochs=10, lr=1e-3, batch_size=32, hidden_dim=None, num_layers=None,
                             seed=None, init=None, channel_weights=(1.0, 1.0, 1.0), through_state=True, device="cuda",
-                            save_dir="checkpoints", log=print):
+                            save_dir="checkpoints", log=print, weight_decay=0.0, max_grad_norm=None,
+                            skip_nonfinite=False, scheduler=None):
     """Train (or fine-tune) PureGNN on K-step windows of classical trajectories
     [N,T+1,3,nx] (datagen.generate_trajectories) with the unrolled loss:
     train_unrolled's loop -- Adam(lr) over shuffled batches of batch_size windows
@@ -968,7 +1159,8 @@ def train_pure_gnn_unrolled(trajectories, x, K=4, epochs=10, lr=1e-3, batch_size
     (model, history) with history keys epoch, loss (the mean over the epoch's
     windows), seconds, and writes checkpoints/pure_gnn_unrolled_K<K>.pt (a state
     dict the reference's PureGNN loads) and history_pure_gnn_unrolled_K<K>.json
-    (save_dir=None skips)."""
+    (save_dir=None skips).  weight_decay, max_grad_norm, skip_nonfinite,
+    scheduler: as train_unrolled's."""
     engine.require_device(torch.empty(0, device=device), "device")
     if seed is not None:
         torch.manual_seed(seed)
@@ -976,7 +1168,8 @@ def train_pure_gnn_unrolled(trajectories, x, K=4, epochs=10, lr=1e-3, batch_size
     model = PureGNN(MODEL_CONFIG["input_dim"], hidden_dim or MODEL_CONFIG["hidden_dim"],
                     MODEL_CONFIG["num_layers"] if num_layers is None else num_layers)
     return _train_windows(_PURE, model, data, x, None, init, epochs, lr, batch_size, seed, channel_weights,
-                          through_state, device, save_dir, log)
+                          through_state, device, save_dir, log,
+                          (weight_decay, max_grad_norm, skip_nonfinite, scheduler))
 
 
 # --------------------------------------------------------------------- PINN
@@ -1145,7 +1338,8 @@ def pinn_train_flop_per_sample(D=192, H=256, L=4):
 
 
 def train_pinn(state_t, state_next, dx, dt, nu, epochs=50, lr=1e-3, batch_size=32, hidden_dim=256, num_layers=4,
-               weights=PINN_LOSS_WEIGHTS, seed=None, init=None, device=None, log=None):
+               weights=PINN_LOSS_WEIGHTS, seed=None, init=None, device=None, log=None, weight_decay=0.0,
+               max_grad_norm=None, skip_nonfinite=False, scheduler=None):
     """scripts/training/train_pinn.py:114-201 on the MI355X: PINN(3 nx,
     hidden_dim, num_layers), Adam(lr), batches of batch_size samples in a
     shuffled order (the last one may be partial), one pinn_step per batch.
@@ -1153,7 +1347,8 @@ def train_pinn(state_t, state_next, dx, dt, nu, epochs=50, lr=1e-3, batch_size=3
     Returns (model, history) with the reference's history keys, each the
     per-epoch mean of its batch values (:187-197), accumulated on the device
     and read once per epoch.  model.state_dict() has the reference PINN's keys
-    and shapes."""
+    and shapes.  weight_decay, max_grad_norm, skip_nonfinite, scheduler: as
+    train_model's (the means then run over the batches whose step was applied)."""
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     engine.require_device(torch.empty(0, device=device), "device")
     if seed is not None:
@@ -1164,19 +1359,32 @@ def train_pinn(state_t, state_next, dx, dt, nu, epochs=50, lr=1e-3, batch_size=3
     if init is not None:
         model.load_state_dict({k: torch.as_tensor(v) for k, v in init.items()})
     model = model.to(device).flatten_parameters_()
-    opt = FlatAdam(model.parameters(), lr=lr)
+    opt, sched = _guarded_optimizer(model.parameters(), lr, weight_decay, max_grad_norm, skip_nonfinite, scheduler,
+                                    device)
     gen = torch.Generator().manual_seed(0 if seed is None else seed)
     keys = ("loss", "loss_data", "loss_continuity", "loss_momentum", "loss_poisson")
     history = {k: [] for k in keys}
+    stats = _StepStats(opt, history)
     model.train()
     for epoch in range(epochs):
         perm = torch.randperm(n, generator=gen).to(device)
-        total, nb = torch.zeros(5, device=device), 0
+        total, nb, each = torch.zeros(5, device=device), 0, []
         for k in range(0, n, batch_size):
             idx = perm[k:k + batch_size]
-            total += pinn_step(model, opt, st_all[idx], sn_all[idx], dx, dt, nu, weights)
+            losses = pinn_step(model, opt, st_all[idx], sn_all[idx], dx, dt, nu, weights)
+            if stats:
+                each.append(losses)
+                stats.note()
+            else:
+                total += losses
             nb += 1
-        mean = (total / max(nb, 1)).tolist()  # the epoch's one host read
+        if stats:
+            mean = _applied_mean(each, stats.read())
+            mean = mean if isinstance(mean, list) else [mean] * 5
+        else:
+            mean = (total / max(nb, 1)).tolist()  # the epoch's one host read
+        if sched is not None:
+            sched.step()
         for k, v in zip(keys, mean):
             history[k].append(v)
         if log:
@@ -1299,7 +1507,8 @@ def pinn_unrolled_train_flop_per_sample(K=4, D=192, H=256, L=4):
 
 def train_pinn_unrolled(trajectories, dx, dt, nu, K=4, epochs=10, lr=1e-3, batch_size=32, hidden_dim=256, num_layers=4,
                         physics_weights=None, seed=None, init=None, channel_weights=(1.0, 1.0, 1.0),
-                        through_state=True, device="cuda", save_dir="checkpoints", log=print):
+                        through_state=True, device="cuda", save_dir="checkpoints", log=print, weight_decay=0.0,
+                        max_grad_norm=None, skip_nonfinite=False, scheduler=None):
     """Train (or fine-tune) PINN(3 nx, hidden_dim, num_layers) on K-step windows
     of classical trajectories [N,T+1,3,nx] with pinn_unrolled_loss:
     train_unrolled's loop -- Adam(lr) over shuffled batches of batch_size windows
@@ -1309,7 +1518,8 @@ def train_pinn_unrolled(trajectories, dx, dt, nu, K=4, epochs=10, lr=1e-3, batch
     weights; init: a reference state dict to start from (e.g. train_pinn's).
     Returns (model, history) with history keys epoch, loss, seconds, and writes
     checkpoints/pinn_unrolled_K<K>.pt (the reference PINN's keys) and
-    history_pinn_unrolled_K<K>.json (save_dir=None skips)."""
+    history_pinn_unrolled_K<K>.json (save_dir=None skips).  weight_decay,
+    max_grad_norm, skip_nonfinite, scheduler: as train_unrolled's."""
     engine.require_device(torch.empty(0, device=device), "device")
     if seed is not None:
         torch.manual_seed(seed)
@@ -1318,4 +1528,5 @@ def train_pinn_unrolled(trajectories, dx, dt, nu, K=4, epochs=10, lr=1e-3, batch
         _PinnPhys(None, None, None, None, None)
     model = PINN(3 * data.nx, hidden_dim, num_layers)
     return _train_windows(_PINN, model, data, None, phys, init, epochs, lr, batch_size, seed, channel_weights,
-                          through_state, device, save_dir, log)
+                          through_state, device, save_dir, log,
+                          (weight_decay, max_grad_norm, skip_nonfinite, scheduler))

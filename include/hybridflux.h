@@ -237,6 +237,53 @@ int hf_adam_flat(float *dev_params, const float *dev_grads, float *dev_exp_avg, 
                  float *dev_step, unsigned *dev_done, float lr, float beta1, float beta2, float eps, void *stream);
 
 /*
+ * The guarded optimizer step.  Replaces: torch.nn.utils.clip_grad_norm_ +
+ * torch.optim.AdamW + a GradScaler-style skip of a step whose gradient is not
+ * finite (a multi-tensor norm, a multi-tensor scale, the update and a host
+ * read of the norm per step) around hf_adam_flat, by at most two launches and
+ * no host synchronisation, so a captured training step keeps all of it.
+ *
+ * Launch 1 (made only with a workspace): the sum of g[i]^2 in float64, one
+ * partial per workgroup into dev_ws.  The partition is hf_adam_flat's (256
+ * threads; ceil(n / 1024) workgroups, 2048 at most): workgroup b's thread t
+ * adds the squares of g[(b + k W) 256 + t], k = 0, 1, ... (W workgroups) in
+ * ascending k, and the 256 thread sums are added by a halving tree (sum[t] +=
+ * sum[t + 128], then t + 64, ..., t + 1).  Launch 2: every workgroup adds the W partials --
+ * thread t those at t, t + 256, ... in ascending order, then the same tree --
+ * so every workgroup holds the same bits, and two calls on the same gradient
+ * give the same norm.  Then, in float32 unless stated:
+ *   norm = (float)sqrt(sum),  coef = min(max_norm / (norm + 1e-6f), 1)
+ *   skipped = skip_nonfinite and norm is inf or NaN: nothing is written to
+ *     dev_params, dev_exp_avg, dev_exp_avg_sq or dev_step
+ *   otherwise per value: g' = g coef (g itself when coef == 1: an unclipped
+ *     step is bit-equal to one without clipping), p = p (1 - lr wd) when wd !=
+ *     0, then hf_adam_flat's update with g' and that p, bit for bit (c1 = 1.0f
+ *     - beta1, c2 = 1.0f - beta2, the bias corrections from float64 pow).
+ * lr is dev_lr[0] when dev_lr is not NULL (a device float a scheduler rewrites
+ * between replays of a captured step), the by-value lr otherwise.  max_norm:
+ * INFINITY = no clipping.  dev_step advances except on a skipped step;
+ * dev_done as for hf_adam_flat (left 0, skipped or not).  dev_stats
+ * [HF_OPT_NUM_STATS] or NULL, written by the last workgroup to finish: (norm
+ * before clipping, coef applied (0 on a skipped step), skipped 0/1, skipped
+ * steps so far); the last one is read and incremented, so zero the buffer
+ * before the first step and hand the same one to every step.
+ *
+ * dev_ws: hf_adam_flat_workspace_bytes(n) bytes (a multiple of 8, monotone in
+ * n; -1 for n < 0), 8-byte aligned.  It may be NULL only when max_norm is
+ * INFINITY, skip_nonfinite is 0 and dev_stats is NULL: then no norm launch is
+ * made and the call is hf_adam_flat with weight decay and the device lr.
+ * HF_EINVAL: n < 0, a NULL pointer with n > 0 (dev_lr, dev_stats and, as said,
+ * dev_ws may be NULL), max_norm <= 0 or NaN, weight_decay < 0 or NaN, a missing
+ * workspace.  n == 0 is HF_OK without a launch.
+ */
+#define HF_OPT_NUM_STATS 4
+int64_t hf_adam_flat_workspace_bytes(int64_t n);
+int hf_adam_flat_ex(float *dev_params, const float *dev_grads, float *dev_exp_avg, float *dev_exp_avg_sq, int64_t n,
+                    float *dev_step, unsigned *dev_done, const float *dev_lr, float lr, float beta1, float beta2,
+                    float eps, float weight_decay, float max_norm, int skip_nonfinite, void *dev_ws,
+                    float *dev_stats, void *stream);
+
+/*
  * Unrolled training: FluxGNN differentiated through K hybrid solver steps.
  * Replaces: the torch ops a user would put around FluxGNN's autograd Function
  * to train through the solver's feedback loop n -> E -> u -> node features
