@@ -42,6 +42,14 @@ struct hf_model {
   hf::GraphW graph{};
 };
 
+// M models of one wdtype and the device table of their ChainW (hf_run_set's
+// workgroups index it by model).  The models are borrowed, not owned.
+struct hf_model_set {
+  std::vector<hf_model *> models;
+  hf::ChainW *table = nullptr;  // [M] on the device
+  int wdtype = 0;
+};
+
 namespace {
 
 // Offsets of each parameter inside the reference-ordered flat array.
@@ -1467,6 +1475,151 @@ int hf_run_compare(hf_model_t m, const float *state0, float *state_final, const 
                    float *metrics_cl, void *ws, int64_t ws_bytes, void *stream) {
   return hf_run_compare_ex(m, state0, state_final, x, pc, HF_POISSON_SPECTRAL, B, nx, T, c, dt, nu, dx2, mse,
                            metrics, metrics_cl, ws, ws_bytes, stream);
+}
+
+int hf_model_set_create(const hf_model_t *models, int M, hf_model_set_t *out) {
+  if (!out) return fail(HF_EINVAL, "hf_model_set_create: out is NULL");
+  *out = nullptr;
+  if (!models) return fail(HF_EINVAL, "hf_model_set_create: models is NULL");
+  if (M <= 0) return fail(HF_EINVAL, "hf_model_set_create: need M >= 1");
+  for (int i = 0; i < M; ++i) {
+    if (!models[i]) return fail(HF_EINVAL, "hf_model_set_create: NULL model in the set");
+    if (models[i]->wdtype != models[0]->wdtype)
+      return fail(HF_EINVAL, "hf_model_set_create: the models of a set share one wdtype");
+    if (!models[i]->chain_ok)
+      return fail(HF_EUNSUPPORTED,
+                  "hf_model_set_create: a set takes chain-capable models only (FluxGNN input_dim 4, hidden_dim 128)");
+  }
+  if (int rc = check_device()) return rc;
+  hf_model_set *set = new hf_model_set();
+  set->models.assign(models, models + M);
+  set->wdtype = models[0]->wdtype;
+  std::vector<hf::ChainW> host((size_t)M);
+  for (int i = 0; i < M; ++i) host[i] = models[i]->chain;
+  hipError_t e = hipMalloc(&set->table, sizeof(hf::ChainW) * (size_t)M);
+  if (e != hipSuccess) {
+    delete set;
+    return fail(HF_ENOMEM, std::string("hf_model_set_create: hipMalloc: ") + hipGetErrorString(e));
+  }
+  e = hipMemcpy(set->table, host.data(), sizeof(hf::ChainW) * (size_t)M, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(set->table);
+    delete set;
+    return fail_hip(e, "hf_model_set_create: upload");
+  }
+  *out = set;
+  return HF_OK;
+}
+
+void hf_model_set_destroy(hf_model_set_t set) {
+  if (!set) return;
+  if (set->table) (void)hipFree(set->table);
+  delete set;
+}
+
+int hf_model_set_size(hf_model_set_t set) { return set ? (int)set->models.size() : 0; }
+
+int64_t hf_set_workspace_need(hf_model_set_t set, int op, int B, int nx, int T, int flags) {
+  if (!set || (op != HF_OP_RUN && op != HF_OP_COMPARE)) return -1;
+  int64_t need = 0;  // the models run one after another off the fused sizes: the largest single need
+  for (hf_model *m : set->models) {
+    const int64_t n = hf_workspace_need(m, op, B, nx, T, flags);
+    if (n < 0) return -1;
+    need = n > need ? n : need;
+  }
+  return need;
+}
+
+namespace {
+
+// The checks hf_run_set and hf_run_compare_set share, all before any device
+// call; *done: nothing to run (B == 0).
+int check_set_call(const char *fn, hf_model_set_t set, const float *state0, int64_t model_stride,
+                   const float *state_final, const float *x, const double *pc, int pm, int B, int nx, int T,
+                   bool *done) {
+  const std::string f(fn);
+  *done = false;
+  if (B < 0 || nx < 1 || T < 0) return fail(HF_EINVAL, f + ": need B >= 0, nx >= 1, T >= 0");
+  const int64_t cells = (int64_t)B * nx;  // < 2^62
+  if (model_stride != 0 && (cells > std::numeric_limits<int64_t>::max() / 3 || model_stride != 3 * cells))
+    return fail(HF_EINVAL, f + ": model_stride is 0 (shared ICs) or B*3*nx floats (ICs per model)");
+  if (model_stride == 0 && state0 && state0 == state_final)
+    return fail(HF_EINVAL, f + ": state_final may alias state0 only with ICs per model (model_stride != 0)");
+  if (!set) return fail(HF_EINVAL, f + ": NULL model set");
+  if (int rc = check_mode(pm, nx, fn)) return rc;
+  if ((int64_t)set->models.size() * B > std::numeric_limits<int>::max())
+    return fail(HF_EINVAL, f + ": M*B exceeds the int range");
+  if (B == 0) {
+    *done = true;
+    return HF_OK;
+  }
+  if (!state0 || !state_final || !pc || !x) return fail(HF_EINVAL, f + ": NULL state, x or Poisson plan");
+  return HF_OK;
+}
+
+hf::ChainSet chain_set(const hf_model_set *set, int64_t model_stride) {
+  return hf::ChainSet{set->table, (int)set->models.size(), set->wdtype, model_stride};
+}
+
+}  // namespace
+
+int hf_run_set(hf_model_set_t set, const float *state0, int64_t model_stride, float *state_final, const float *x,
+               const double *pc, int pm, int B, int nx, int T, float c, float dt, float nu, float dx2, float *traj,
+               float *flux_traj, float *metrics, void *ws, int64_t ws_bytes, void *stream) {
+  bool done = false;
+  if (int rc = check_set_call("hf_run_set", set, state0, model_stride, state_final, x, pc, pm, B, nx, T, &done))
+    return rc;
+  if (done) return HF_OK;
+  if (fused_nx(nx)) {  // one launch: the workgroups pick their model
+    hf::RolloutExtras ex;
+    ex.poisson = pm;
+    HF_CHECK_HIP(hf::launch_chain_rollout_set(chain_set(set, model_stride), state0, state_final, x, pc, B, nx, T, c,
+                                              dt, traj, flux_traj, metrics, as_stream(stream), ex),
+                 "hf_run_set(fused)");
+    return HF_OK;
+  }
+  const int64_t S = 3LL * B * nx, R = (int64_t)B * (T + 1);  // per model: state floats, [T+1] rows
+  for (size_t m = 0; m < set->models.size(); ++m) {
+    const int64_t i = (int64_t)m;
+    if (int rc = hf_run_ex(set->models[m], state0 + i * model_stride, state_final + i * S, x, pc, pm, B, nx, T, c, dt,
+                           nu, dx2, traj ? traj + i * R * 3 * nx : nullptr,
+                           flux_traj ? flux_traj + i * B * T * nx : nullptr,
+                           metrics ? metrics + i * R * HF_NUM_METRICS : nullptr, ws, ws_bytes, stream))
+      return fail(rc, "hf_run_set: model " + std::to_string(m) + ": " + g_err);
+  }
+  return HF_OK;
+}
+
+int hf_run_compare_set(hf_model_set_t set, const float *state0, int64_t model_stride, float *state_final,
+                       const float *x, const double *pc, int pm, int B, int nx, int T, float c, float dt, float nu,
+                       float dx2, float *mse, float *metrics, float *metrics_cl, void *ws, int64_t ws_bytes,
+                       void *stream) {
+  bool done = false;
+  if (int rc = check_set_call("hf_run_compare_set", set, state0, model_stride, state_final, x, pc, pm, B, nx, T, &done))
+    return rc;
+  if (done) return HF_OK;
+  if (!mse) return fail(HF_EINVAL, "hf_run_compare_set: NULL mse");
+  if (fused_nx(nx)) {
+    hf::RolloutExtras ex;
+    ex.nu = nu;
+    ex.dx2 = dx2;
+    ex.mse = mse;
+    ex.metrics_cl = metrics_cl;
+    ex.poisson = pm;
+    HF_CHECK_HIP(hf::launch_chain_rollout_set(chain_set(set, model_stride), state0, state_final, x, pc, B, nx, T, c,
+                                              dt, nullptr, nullptr, metrics, as_stream(stream), ex),
+                 "hf_run_compare_set(fused)");
+    return HF_OK;
+  }
+  const int64_t S = 3LL * B * nx, R = (int64_t)B * (T + 1);
+  for (size_t m = 0; m < set->models.size(); ++m) {
+    const int64_t i = (int64_t)m;
+    if (int rc = hf_run_compare_ex(set->models[m], state0 + i * model_stride, state_final + i * S, x, pc, pm, B, nx, T,
+                                   c, dt, nu, dx2, mse + i * R * 3, metrics ? metrics + i * R * HF_NUM_METRICS : nullptr,
+                                   metrics_cl ? metrics_cl + i * R * HF_NUM_METRICS : nullptr, ws, ws_bytes, stream))
+      return fail(rc, "hf_run_compare_set: model " + std::to_string(m) + ": " + g_err);
+  }
+  return HF_OK;
 }
 
 int hf_traj_metrics(const float *traj, int B, int T1, int nx, float *metrics, void *stream) {

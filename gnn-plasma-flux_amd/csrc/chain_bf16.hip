@@ -1009,4 +1009,14 @@ hipError_t launch_chain_rollout_bf16(const ChainW &w, const float *state0, float
                                                              flux_traj, metrics, ex, s);
 }
 
+hipError_t launch_chain_rollout_set_bf16(const ChainSet &set, const float *state0, float *state_final, const float *x,
+                                         const double *pc, int B, int nx, int T, float c, float dt, float *traj,
+                                         float *flux_traj, float *metrics, const RolloutExtras &ex, hipStream_t s) {
+  if (chain::set_prefers_cells(set, B, nx, ex))
+    return chain::launch_cells_set<CellBF16Ld>(set, state0, state_final, x, pc, B, nx, T, c, dt, traj, flux_traj,
+                                               metrics, ex.poisson, s);
+  return chain::launch_rollout_core_set<CoreBF16<4, 2, 4, true, 4, 1, -1>>(set, state0, state_final, x, pc, B, nx, T,
+                                                                           c, dt, traj, flux_traj, metrics, ex, s);
+}
+
 }  // namespace hf

@@ -22,6 +22,8 @@
 // wave's own DMA, one s_barrier, issue p+2, ds_read_b128 the fragments.
 #pragma once
 
+#include <type_traits>
+
 #include "hf_device.h"
 #include "hf_internal.h"
 
@@ -838,12 +840,49 @@ __global__ __launch_bounds__(64 * Core::kNW, Core::kWGPerCU) void chain_train_bw
 // T steps of GNN -> symmetrise -> continuity -> Burgers -> spectral Poisson
 // with the IC's state in LDS (src/hybrid_solver.py:34-73).  The weight stream
 // runs continuously across steps.
-template <class Core, int MT>
+//
+// One body, two entries.  SET = false is the single-model launch: the model's
+// ChainW arrives by value in the kernarg segment, ceil(B/4) workgroups.
+// SET = true is a model set's launch (hf_run_set): M x G workgroups, G =
+// ceil(B/4) per model; workgroup blockIdx.x serves model m = blockIdx.x / G
+// with the ChainW it reads from table[m].  The index is workgroup-uniform and
+// the table read-only, so the entry comes in by scalar loads and stays in
+// SGPRs, as the kernarg copy does.  Every pointer then moves to the model's
+// own [B] block and the rest of the body runs on blk, the workgroup's index
+// within its model: the clamp of a ragged last workgroup (b = live ? b_raw :
+// B - 1) therefore stays inside the model's ICs.
+struct ModelTable {
+  const ChainW *table;  // [M], device memory
+  int G;                // workgroups per model
+  int64_t stride0;      // floats between two models' state0 blocks (0: shared ICs)
+};
+template <bool SET>
+using ModelArg = std::conditional_t<SET, ModelTable, ChainW>;
+__device__ __forceinline__ const ChainW &model_of(const ChainW &arg, const ChainW &) { return arg; }
+__device__ __forceinline__ const ChainW &model_of(const ModelTable &, const ChainW &mine) { return mine; }
+
+template <class Core, int MT, bool SET = false>
 __global__ __launch_bounds__(256, 1) void chain_rollout_kernel(
-    ChainW W, const float *state0, float *state_final,  // may alias (read whole before written)
+    ModelArg<SET> Wa, const float *state0, float *state_final,  // may alias (read whole before written; SET: stride0 != 0)
     const float *__restrict__ x, const double *__restrict__ pc, int B, int T, float c, float dt,
     float *__restrict__ traj, float *__restrict__ flux_traj, float *__restrict__ metrics, RolloutExtras ex) {
   constexpr int NX = 16 * MT;
+  ChainW Wm{};
+  unsigned blk = blockIdx.x;
+  if constexpr (SET) {
+    const unsigned m = blockIdx.x / (unsigned)Wa.G;
+    Wm = Wa.table[m];
+    blk -= m * (unsigned)Wa.G;
+    const int64_t ic0 = (int64_t)m * B, rows = ic0 * (T + 1);  // ICs and [T+1] rows before this model's
+    state0 += m * Wa.stride0;
+    state_final += ic0 * 3 * NX;
+    if (traj) traj += rows * 3 * NX;
+    if (flux_traj) flux_traj += ic0 * T * NX;
+    if (metrics) metrics += rows * HF_NUM_METRICS;
+    if (ex.mse) ex.mse += rows * 3;
+    if (ex.metrics_cl) ex.metrics_cl += rows * HF_NUM_METRICS;
+  }
+  const ChainW &W = model_of(Wa, Wm);
   constexpr int kRingFloats = Core::kSlots * Core::kChunkFloats;
   __shared__ f4 lds4[lds_floats<Core>() / 4];
   float *lds = reinterpret_cast<float *>(lds4);
@@ -861,7 +900,7 @@ __global__ __launch_bounds__(256, 1) void chain_rollout_kernel(
   float *park = park_of<Core>(lds, R.wave);
   const bool twin = ex.mse != nullptr;
   static_assert(Core::kNW == kWaves, "rollout: 4 waves, one IC each");
-  const int b_raw = blockIdx.x * kWaves + R.wave;
+  const int b_raw = blk * kWaves + R.wave;
   const bool live = b_raw < B;
   const int64_t b = live ? b_raw : B - 1;
   const float *st0 = state0 + b * 3 * NX;
@@ -1002,13 +1041,28 @@ constexpr int cells_threads() {
   return 64 * (kWaves + (CC::R_t::kLoader ? 1 : 0));
 }
 
-template <class CC, int WPI>
+// SET: the model-set entry, as chain_rollout_kernel's (G = ceil(B/IPW) per model).
+template <class CC, int WPI, bool SET = false>
 __global__ __launch_bounds__(cells_threads<CC>(), 1) void chain_rollout_cells_kernel(
-    ChainW W, const float *state0, float *state_final,  // may alias (read whole before written)
+    ModelArg<SET> Wa, const float *state0, float *state_final,  // may alias (read whole before written; SET: stride0 != 0)
     const float *__restrict__ x,
     const double *__restrict__ pc, int B, int T, float c, float dt, float *__restrict__ traj,
     float *__restrict__ flux_traj, float *__restrict__ metrics, int pm) {
   constexpr int NX = 16 * WPI;
+  ChainW Wm{};
+  unsigned blk = blockIdx.x;
+  if constexpr (SET) {
+    const unsigned m = blockIdx.x / (unsigned)Wa.G;
+    Wm = Wa.table[m];
+    blk -= m * (unsigned)Wa.G;
+    const int64_t ic0 = (int64_t)m * B, rows = ic0 * (T + 1);
+    state0 += m * Wa.stride0;
+    state_final += ic0 * 3 * NX;
+    if (traj) traj += rows * 3 * NX;
+    if (flux_traj) flux_traj += ic0 * T * NX;
+    if (metrics) metrics += rows * HF_NUM_METRICS;
+  }
+  const ChainW &W = model_of(Wa, Wm);
   const bool tri = pm == HF_POISSON_TRIDIAG;  // plan = {h}: no circulant column
   const double h = tri ? pc[0] : 0.0;
   constexpr int IPW = kWaves / WPI;  // ICs per workgroup
@@ -1038,7 +1092,7 @@ __global__ __launch_bounds__(cells_threads<CC>(), 1) void chain_rollout_cells_ke
   float *s_F = scratch + kScrF;
   double *s_rho = reinterpret_cast<double *>(scratch + kScrRho);
   double *s_c2 = reinterpret_cast<double *>(scratch + kScrC2);
-  const int b_raw = blockIdx.x * IPW + slot;
+  const int b_raw = blk * IPW + slot;
   const bool live = b_raw < B;
   const int64_t b = live ? b_raw : B - 1;  // a missing IC mirrors the last one and writes nothing
   if (lead) {
@@ -1052,7 +1106,7 @@ __global__ __launch_bounds__(cells_threads<CC>(), 1) void chain_rollout_cells_ke
   __syncthreads();  // small weights + IC state visible (no DMA in flight yet)
   // outputs of state t of IC slot sl: trajectory row and metrics
   auto emit = [&](int sl, int t) {
-    const int64_t bs = (int64_t)blockIdx.x * IPW + sl;
+    const int64_t bs = (int64_t)blk * IPW + sl;
     if (bs >= B) return;
     const float *st = lds + kRingFloats + kSmallFloats + sl * kWaveScratchFloats;
     if (traj) {
@@ -1215,6 +1269,18 @@ hipError_t cells_launch(const ChainW &w, const float *state0, float *state_final
 }
 
 
+template <class CC, int WPI>
+hipError_t cells_launch_set(const ChainSet &set, const float *state0, float *state_final, const float *x,
+                            const double *pc, int B, int T, float c, float dt, float *traj, float *flux_traj,
+                            float *metrics, int pm, hipStream_t s) {
+  constexpr int IPW = kWaves / WPI;
+  const int G = (B + IPW - 1) / IPW;
+  hipLaunchKernelGGL((chain_rollout_cells_kernel<CC, WPI, true>), dim3((unsigned)(set.M * G)), dim3(cells_threads<CC>()), 0,
+                     s, ModelTable{set.table, G, set.stride0}, state0, state_final, x, pc, B, T, c, dt, traj, flux_traj, metrics, pm);
+  return hipGetLastError();
+}
+
+
 // ------------------------------------------------------------------ launchers
 // Workgroups resident at once: one per CU (the chain kernels hold ~500
 // registers per lane, so 4 waves = one per SIMD fill a CU).
@@ -1286,6 +1352,51 @@ hipError_t launch_rollout_core(const ChainW &w, const float *state0, float *stat
     case 64: return rollout_launch<Core, 4>(w, state0, state_final, x, pc, B, T, c, dt, traj, flux_traj, metrics, ex, s);
     default: return hipErrorInvalidValue;
   }
+}
+
+template <class Core, int MT>
+hipError_t rollout_launch_set(const ChainSet &set, const float *state0, float *state_final, const float *x,
+                              const double *pc, int B, int T, float c, float dt, float *traj, float *flux_traj,
+                              float *metrics, const RolloutExtras &ex, hipStream_t s) {
+  const int G = (B + kWaves - 1) / kWaves;
+  hipLaunchKernelGGL((chain_rollout_kernel<Core, MT, true>), dim3((unsigned)(set.M * G)), dim3(64 * kWaves), 0, s,
+                     ModelTable{set.table, G, set.stride0}, state0, state_final, x, pc, B, T, c, dt, traj, flux_traj, metrics, ex);
+  return hipGetLastError();
+}
+
+template <class Core>
+hipError_t launch_rollout_core_set(const ChainSet &set, const float *state0, float *state_final, const float *x,
+                                   const double *pc, int B, int nx, int T, float c, float dt, float *traj,
+                                   float *flux_traj, float *metrics, const RolloutExtras &ex, hipStream_t s) {
+  if (B <= 0 || set.M <= 0) return hipSuccess;
+  switch (nx) {
+    case 16: return rollout_launch_set<Core, 1>(set, state0, state_final, x, pc, B, T, c, dt, traj, flux_traj, metrics, ex, s);
+    case 32: return rollout_launch_set<Core, 2>(set, state0, state_final, x, pc, B, T, c, dt, traj, flux_traj, metrics, ex, s);
+    case 48: return rollout_launch_set<Core, 3>(set, state0, state_final, x, pc, B, T, c, dt, traj, flux_traj, metrics, ex, s);
+    case 64: return rollout_launch_set<Core, 4>(set, state0, state_final, x, pc, B, T, c, dt, traj, flux_traj, metrics, ex, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// The cell-split set launch of core CC for nx in {32, 48, 64}.
+template <class CC>
+hipError_t launch_cells_set(const ChainSet &set, const float *state0, float *state_final, const float *x,
+                            const double *pc, int B, int nx, int T, float c, float dt, float *traj, float *flux_traj,
+                            float *metrics, int pm, hipStream_t s) {
+  if (B <= 0 || set.M <= 0) return hipSuccess;
+  switch (nx) {
+    case 32: return cells_launch_set<CC, 2>(set, state0, state_final, x, pc, B, T, c, dt, traj, flux_traj, metrics, pm, s);
+    case 48: return cells_launch_set<CC, 3>(set, state0, state_final, x, pc, B, T, c, dt, traj, flux_traj, metrics, pm, s);
+    case 64: return cells_launch_set<CC, 4>(set, state0, state_final, x, pc, B, T, c, dt, traj, flux_traj, metrics, pm, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// Whether a set launch of M x B ICs takes the cell-split kernel: the single
+// launch's rule on the launch's total (both families give the same bits).
+inline bool set_prefers_cells(const ChainSet &set, int B, int nx, const RolloutExtras &ex) {
+  ChainW any{};
+  return ex.mse == nullptr && ex.metrics_cl == nullptr && chain_rollout_prefers_cells(any, set.M * B, nx);
 }
 
 }  // namespace chain

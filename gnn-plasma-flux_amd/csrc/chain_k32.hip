@@ -579,4 +579,17 @@ hipError_t launch_chain_rollout_k32(const ChainW &w, const float *state0, float 
                                    s);
 }
 
+hipError_t launch_chain_rollout_set_k32(const ChainSet &set, const float *state0, float *state_final, const float *x,
+                                        const double *pc, int B, int nx, int T, float c, float dt, float *traj,
+                                        float *flux_traj, float *metrics, const RolloutExtras &ex, hipStream_t s) {
+  if (set.prec != kPrecF16x3)
+    return launch_chain_rollout_set_bf16(set, state0, state_final, x, pc, B, nx, T, c, dt, traj, flux_traj, metrics,
+                                         ex, s);
+  if (chain::set_prefers_cells(set, B, nx, ex))
+    return chain::launch_cells_set<CellF16x3Ld>(set, state0, state_final, x, pc, B, nx, T, c, dt, traj, flux_traj,
+                                                metrics, ex.poisson, s);
+  return chain::launch_rollout_core_set<CoreF16x3T<1, false, kK32Defer>>(set, state0, state_final, x, pc, B, nx, T, c,
+                                                                         dt, traj, flux_traj, metrics, ex, s);
+}
+
 }  // namespace hf

@@ -221,6 +221,37 @@ hipError_t launch_chain_rollout_bf16(const ChainW &, const float *, float *, con
                                      int, float, float, float *, float *, float *, const RolloutExtras &,
                                      hipStream_t);
 
+// A model set's fused rollout (hf_run_set): one launch of M x G workgroups,
+// G the workgroup count of one model's B ICs; each workgroup reads its model's
+// ChainW from table[blockIdx.x / G] (device memory, M entries of one prec).
+// Model m starts from state0 + m*stride0 (stride0 = 0: shared ICs) and every
+// output carries a leading [M] axis.  Needs M*B and M*G within int.
+struct ChainSet {
+  const ChainW *table;
+  int M;
+  int prec;
+  int64_t stride0;
+};
+hipError_t launch_chain_rollout_set_f32(const ChainSet &, const float *, float *, const float *, const double *, int,
+                                        int, int, float, float, float *, float *, float *, const RolloutExtras &,
+                                        hipStream_t);
+hipError_t launch_chain_rollout_set_k32(const ChainSet &, const float *, float *, const float *, const double *, int,
+                                        int, int, float, float, float *, float *, float *, const RolloutExtras &,
+                                        hipStream_t);
+hipError_t launch_chain_rollout_set_bf16(const ChainSet &, const float *, float *, const float *, const double *, int,
+                                         int, int, float, float, float *, float *, float *, const RolloutExtras &,
+                                         hipStream_t);
+inline hipError_t launch_chain_rollout_set(const ChainSet &set, const float *state0, float *state_final,
+                                           const float *x, const double *pc, int B, int nx, int T, float c, float dt,
+                                           float *traj, float *flux_traj, float *metrics, hipStream_t s,
+                                           const RolloutExtras &ex) {
+  return set.prec == kPrecF32
+             ? launch_chain_rollout_set_f32(set, state0, state_final, x, pc, B, nx, T, c, dt, traj, flux_traj,
+                                            metrics, ex, s)
+             : launch_chain_rollout_set_k32(set, state0, state_final, x, pc, B, nx, T, c, dt, traj, flux_traj,
+                                            metrics, ex, s);
+}
+
 // Chain flux.  Feature source: AoS node features [B*nx][4] (nf != nullptr)
 // or SoA state [B][3][nx] with IC stride ld_state floats + x[nx].
 inline hipError_t launch_chain_flux(const ChainW &w, const float *nf, const float *state, int64_t ld_state,

@@ -111,6 +111,16 @@ SIGNATURES = {
     "hf_run_compare": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                c_void_p]),
+    "hf_model_set_create": (c_int, [c_void_p, c_int, POINTER(c_void_p)]),
+    "hf_model_set_destroy": (None, [c_void_p]),
+    "hf_model_set_size": (c_int, [c_void_p]),
+    "hf_run_set": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                           c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                           c_void_p]),
+    "hf_run_compare_set": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                   c_int, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_int64, c_void_p]),
+    "hf_set_workspace_need": (c_int64, [c_void_p, c_int, c_int, c_int, c_int, c_int]),
     "hf_traj_metrics": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "hf_traj_mse": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "hf_pure_gnn_score_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),

@@ -121,6 +121,46 @@ class DeviceModel:
             pass
 
 
+class DeviceModelSet:
+    """M DeviceModels of one precision on one device behind one handle
+    (hf_model_set_t): the table the model-set rollouts index per workgroup.
+    Keeps the DeviceModels alive for as long as the set lives; their layer
+    counts may differ."""
+
+    def __init__(self, models):
+        models = list(models)
+        if not models:
+            raise ValueError("DeviceModelSet needs at least one model")
+        for i, m in enumerate(models):
+            if m.precision != models[0].precision:
+                raise ValueError(f"DeviceModelSet: model {i} is {m.precision}, model 0 is {models[0].precision}; a set "
+                                 "shares one precision")
+            if m.device != models[0].device:
+                raise ValueError(f"DeviceModelSet: model {i} is on {m.device}, model 0 on {models[0].device}")
+            if not m.chain_ok:
+                raise ValueError(f"DeviceModelSet: model {i} is not FluxGNN(input_dim=4, hidden_dim=128)")
+        self.models = models
+        self.device, self.precision = models[0].device, models[0].precision
+        self.handle = c_void_p()
+        arr = (c_void_p * len(models))(*[m.handle.value for m in models])
+        with torch.cuda.device(self.device):
+            check(lib().hf_model_set_create(arr, len(models), self.handle))
+
+    def __len__(self):
+        return len(self.models)
+
+    def close(self):
+        if getattr(self, "handle", None) is not None and self.handle.value:
+            lib().hf_model_set_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown
+            pass
+
+
 POISSON_MODES = {"spectral": _lib.HF_POISSON_SPECTRAL, "tridiagonal": _lib.HF_POISSON_TRIDIAG}
 
 
@@ -274,6 +314,89 @@ def run_compare(model, grid, state0, T, metrics=True, out=None, ws=None):
                                       grid.nx, T,
                                    grid.c32, grid.dt32, grid.nu32, grid.dx2_32, ptr(mse), ptr(me), ptr(mc),
                                    ptr(w), wb, stream_of(dev)))
+    return {"final": final, "mse": mse, "metrics": me, "metrics_classical": mc}
+
+
+def set_states(state0, M, nx):
+    """The ICs of a model-set rollout: float32 [B,3,nx] shared by the M models,
+    or [M,B,3,nx] with each model's own.  Returns (contiguous tensor, B,
+    model stride in floats: 0 when shared)."""
+    require_device(state0, "state")
+    shared = state0.dim() == 3
+    if state0.dtype != torch.float32 or state0.dim() not in (3, 4) or tuple(state0.shape[-2:]) != (3, nx) \
+            or (not shared and state0.shape[0] != M):
+        raise ValueError(f"state must be float32 [B,3,{nx}] (shared ICs) or [{M},B,3,{nx}] (ICs per model), got "
+                         f"{tuple(state0.shape)} {state0.dtype}")
+    B = state0.shape[-3]
+    return state0.contiguous(), B, 0 if shared else B * 3 * nx
+
+
+def _set_final(state0, stride, out, M, B, nx):
+    """state_final [M,B,3,nx] of a set rollout: the caller's `out` (which may be
+    state0 itself only when every model has its own ICs) or a new tensor."""
+    if out is None:
+        return torch.empty(M, B, 3, nx, device=state0.device)
+    final = _buf(True, out, (M, B, 3, nx), state0.device)
+    if stride == 0 and B > 0 and final.untyped_storage().data_ptr() == state0.untyped_storage().data_ptr():
+        raise ValueError("out must not share memory with state0 when the models share their ICs (every model "
+                         "reads all of state0); give each model its own ICs [M,B,3,nx] to roll out in place")
+    return final
+
+
+def set_workspace(op, mset, B, nx, T, dev, given=None, traj=False):
+    """workspace() for a model set: the largest single-model need (none at the fused nx)."""
+    nbytes = int(lib().hf_set_workspace_need(mset.handle, op, B, nx, T, _lib.HF_WS_TRAJ if traj is not None else 0))
+    if nbytes < 0:
+        raise ValueError(f"bad workspace query (op={op}, B={B}, nx={nx}, T={T})")
+    if given is not None:
+        if not (given.is_cuda and given.device == dev and given.numel() * given.element_size() >= nbytes):
+            raise ValueError(f"workspace must be a device tensor of >= {nbytes} bytes on {dev}")
+        return given, given.numel() * given.element_size()
+    if nbytes == 0:
+        return None, 0
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
+
+
+def run_set(mset, grid, state0, T, traj=True, flux=False, metrics=False, out=None, ws=None):
+    """run() for every model of a DeviceModelSet, one launch at nx in
+    {16,32,48,64}: state0 [B,3,nx] (shared) or [M,B,3,nx]; returns run()'s dict
+    with a leading model axis (final [M,B,3,nx], traj [M,B,T+1,3,nx], flux
+    [M,B,T,nx], metrics [M,B,T+1,4]), model m's block bit-identical to
+    run(mset.models[m], ...)."""
+    M = len(mset)
+    state0, B, stride = set_states(state0, M, grid.nx)
+    dev = state0.device
+    T = int(T)
+    final = _set_final(state0, stride, out, M, B, grid.nx)
+    tr = _buf(traj, traj, (M, B, T + 1, 3, grid.nx), dev)
+    fl = _buf(flux, flux, (M, B, T, grid.nx), dev)
+    me = _buf(metrics, metrics, (M, B, T + 1, HF_NUM_METRICS), dev)
+    x, pc = grid.on(dev)
+    w, wb = set_workspace(HF_OP_RUN, mset, B, grid.nx, T, dev, ws, traj=tr)
+    with torch.cuda.device(dev):
+        check(lib().hf_run_set(mset.handle, ptr(state0), stride, ptr(final), ptr(x), ptr(pc), grid.pmode, B, grid.nx, T,
+                               grid.c32, grid.dt32, grid.nu32, grid.dx2_32, ptr(tr), ptr(fl), ptr(me), ptr(w), wb,
+                               stream_of(dev)))
+    return {"final": final, "traj": tr, "flux": fl, "metrics": me}
+
+
+def run_compare_set(mset, grid, state0, T, metrics=True, out=None, ws=None):
+    """run_compare() for every model of a DeviceModelSet (one launch at the fused
+    nx): run_compare's dict with a leading model axis."""
+    M = len(mset)
+    state0, B, stride = set_states(state0, M, grid.nx)
+    dev = state0.device
+    T = int(T)
+    final = _set_final(state0, stride, out, M, B, grid.nx)
+    mse = torch.empty(M, B, T + 1, 3, device=dev)
+    me = torch.empty(M, B, T + 1, HF_NUM_METRICS, device=dev) if metrics else None
+    mc = torch.empty(M, B, T + 1, HF_NUM_METRICS, device=dev) if metrics else None
+    x, pc = grid.on(dev)
+    w, wb = set_workspace(HF_OP_COMPARE, mset, B, grid.nx, T, dev, ws)
+    with torch.cuda.device(dev):
+        check(lib().hf_run_compare_set(mset.handle, ptr(state0), stride, ptr(final), ptr(x), ptr(pc), grid.pmode, B,
+                                       grid.nx, T, grid.c32, grid.dt32, grid.nu32, grid.dx2_32, ptr(mse), ptr(me),
+                                       ptr(mc), ptr(w), wb, stream_of(dev)))
     return {"final": final, "mse": mse, "metrics": me, "metrics_classical": mc}
 
 
@@ -582,6 +705,8 @@ def initial_conditions(grid, seeds, debug=False, device=None):
 
 def _series(t, shape_tail, what):
     require_device(t, what)
+    if t.dim() == 4:  # [M,B,T+1,.] of a model set: the rows are independent, so M*B of them
+        t = t.reshape(-1, *t.shape[2:]) if t.is_contiguous() else t
     if t.dtype != torch.float32 or tuple(t.shape[2:]) != shape_tail or not t.is_contiguous():
         raise ValueError(f"{what} must be contiguous float32 [B,T+1,{','.join(map(str, shape_tail))}], "
                          f"got {tuple(t.shape)} {t.dtype}")
@@ -615,7 +740,10 @@ def traj_mse(a, b):
 
 def rollout_summary(metrics, mse=None, metrics_ref=None, drift=False):
     """hf_rollout_summary: (summary [B,8], drift [B,T+1,4] or None); fields in
-    include/hybridflux.h (HF_NUM_SUMMARY)."""
+    include/hybridflux.h (HF_NUM_SUMMARY).  Series with a leading model axis
+    ([M,B,T+1,.], a model set's) give summary [M,B,8] and drift [M,B,T+1,4]:
+    the kernel works per row."""
+    lead = tuple(metrics.shape[:2]) if isinstance(metrics, torch.Tensor) and metrics.dim() == 4 else None
     metrics = _series(metrics, (HF_NUM_METRICS,), "metrics")
     B, T1 = metrics.shape[:2]
     dev = metrics.device
@@ -631,6 +759,9 @@ def rollout_summary(metrics, mse=None, metrics_ref=None, drift=False):
     with torch.cuda.device(dev):
         check(lib().hf_rollout_summary(ptr(metrics), ptr(mse), ptr(metrics_ref), B, T1 - 1, ptr(summ), ptr(dr),
                                        stream_of(dev)))
+    if lead is not None:
+        summ = summ.reshape(*lead, _lib.HF_NUM_SUMMARY)
+        dr = dr.reshape(*lead, T1, 4) if dr is not None else None
     return summ, dr
 
 

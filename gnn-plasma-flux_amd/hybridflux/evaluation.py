@@ -9,7 +9,8 @@ hf_rollout_summary), so a sharded multi-GPU job can gather them.
   long_rollout(solver, states0, n_steps)      scripts/evaluation/evaluate_long_rollout.py:18-81
   compare_models(models, states0, n_steps)    scripts/evaluation/evaluate_multi_ic.py:97-136
 
-`solver` is a HybridSolver or a ModelRollout, the adapter that gives the
+`solver` is a HybridSolver, a HybridEnsemble (every result then carries a
+leading model axis) or a ModelRollout, the adapter that gives the
 comparison models (PureGNN, PINN: evaluate_multi_ic.py:45-83) the same
 compare_batch / run_batch, scored inside their one-launch rollouts.
 """
@@ -17,14 +18,16 @@ import torch
 
 from . import engine
 from .baselines import PureGNN
+from .hybrid_solver import HybridEnsemble, HybridSolver
 
 SUMMARY_FIELDS = ("exploded_at", "actual_steps", "final_energy_drift", "final_charge_drift", "final_mse",
                   "mean_mse", "final_energy_drift_true", "final_charge_drift_true")
 
 
 def summary_dict(summary):
-    """[B, HF_NUM_SUMMARY] -> {field: [B] tensor}; exploded_at is -1 where nothing exploded."""
-    return {k: summary[:, i] for i, k in enumerate(SUMMARY_FIELDS)}
+    """[B, HF_NUM_SUMMARY] -> {field: [B] tensor} (or [M, B, .] -> [M, B], a model
+    set's); exploded_at is -1 where nothing exploded."""
+    return {k: summary[..., i] for i, k in enumerate(SUMMARY_FIELDS)}
 
 
 def compute_metrics(states_pred, states_true):
@@ -84,16 +87,39 @@ class ModelRollout:
         return {"final": r["final"], "traj": r["traj"], "flux": None, "metrics": r.get("metrics")}
 
 
-def compare_models(models, states0, n_steps):
+def ensemble_groups(models):
+    """Which entries of `models` (name -> solver) compare_models rolls out
+    together: lists of names, in `models`' order, of HybridSolvers that agree
+    on HybridEnsemble.SIGNATURE (nx, grid constants, Poisson mode, precision,
+    device).  Groups of one, ModelRollouts and anything else are left out: they
+    run on their own."""
+    groups = {}
+    for k, m in models.items():
+        if isinstance(m, HybridSolver):
+            groups.setdefault(HybridEnsemble.signature(m), []).append(k)
+    return [g for g in groups.values() if len(g) > 1]
+
+
+def compare_models(models, states0, n_steps, grouped=True):
     """evaluate_multi_ic.py:97-136 on the device: every model of `models` (name
     -> HybridSolver or ModelRollout) rolled out from the same ICs and scored
     against the classical solver.  Returns {name: {mean_mse, std_mse (python
     floats, np.mean / np.std over the ICs as :128-136), mse_per_ic (list)}};
-    the one host synchronisation is the copy of all per-IC numbers at the end."""
+    the one host synchronisation is the copy of all per-IC numbers at the end.
+    grouped: the HybridSolvers that can share a launch (ensemble_groups) run as
+    one HybridEnsemble each, everything else one by one; grouped=False runs
+    every model on its own.  The numbers are the same, bit for bit."""
     names = list(models)
     if not names:
         return {}
-    per_ic = torch.stack([multi_ic_mse(models[k], states0, n_steps)[0] for k in names])  # [M, B], device
+    rows = {}
+    for g in ensemble_groups(models) if grouped else []:
+        per_model = multi_ic_mse(HybridEnsemble([models[k] for k in g]), states0, n_steps)[0]  # [len(g), B]
+        rows.update(zip(g, per_model))
+    for k in names:
+        if k not in rows:
+            rows[k] = multi_ic_mse(models[k], states0, n_steps)[0]
+    per_ic = torch.stack([rows[k] for k in names])  # [M, B], device
     host = per_ic.to(torch.float64).cpu().numpy()
     return {k: {"mean_mse": float(host[i].mean()) if host.shape[1] else float("nan"),
                 "std_mse": float(host[i].std()) if host.shape[1] else float("nan"),
@@ -105,7 +131,8 @@ def multi_ic_mse(solver, states0, n_steps):
     """evaluate_model_on_ic('hybrid', ...) for B ICs in one launch: the hybrid
     rollout and the classical BaselineSolver twin from the same states, scored
     per step.  Returns (mean MSE per IC [B] (the reference's return value),
-    the compare_batch result, summary dict)."""
+    the compare_batch result, summary dict); with a HybridEnsemble every
+    tensor has a leading model axis ([M,B] mean MSE)."""
     r = solver.compare_batch(states0, n_steps, metrics=True)
     summ, _ = engine.rollout_summary(r["metrics"], r["mse"], r["metrics_classical"])
     d = summary_dict(summ)

@@ -855,6 +855,49 @@ int hf_run_compare_ex(hf_model_t model, const float *dev_state0, float *dev_stat
                       void *dev_workspace, int64_t workspace_bytes, void *stream);
 
 /*
+ * Model sets: M FluxGNN checkpoints rolled out in one launch (an ablation
+ * sweep's models, or an ensemble's members, from the same or their own ICs).
+ * hf_model_set_create: M >= 1 models of one wdtype, on the current device; all
+ * chain-capable (in_dim 4, hidden 128) or the call is HF_EUNSUPPORTED.  Uploads
+ * the table of their weights' addresses once; the models must outlive the set.
+ * Their `layers` may differ.
+ */
+typedef struct hf_model_set *hf_model_set_t;
+int hf_model_set_create(const hf_model_t *models, int M, hf_model_set_t *out);
+void hf_model_set_destroy(hf_model_set_t set);
+int hf_model_set_size(hf_model_set_t set); /* M; 0 for NULL */
+/*
+ * hf_run_ex / hf_run_compare_ex for every model of the set.  model_stride, in
+ * floats, says where model m's ICs start (dev_state0 + m*model_stride): 0 =
+ * all M models start from the same [B][3][nx] states, B*3*nx = dev_state0 is
+ * [M][B][3][nx]; any other value is HF_EINVAL.  Every output is model-major:
+ * dev_state_final [M][B][3][nx], dev_traj [M][B][T+1][3][nx], dev_flux_traj
+ * [M][B][T][nx], dev_metrics / dev_metrics_classical [M][B][T+1][HF_NUM_METRICS],
+ * dev_mse [M][B][T+1][3]; each model's block holds exactly what the
+ * single-model call writes for it, bit for bit.  dev_state_final may alias
+ * dev_state0 only when model_stride != 0 (with shared ICs: HF_EINVAL).
+ * For nx in {16,32,48,64} the call is ONE persistent launch of M x G
+ * workgroups (G = one model's workgroup count), each workgroup serving the
+ * model blockIdx.x / G: no allocation, no host synchronisation, capturable.
+ * For any other nx the M models run one after another on `stream` through the
+ * single-model sequencing; dev_workspace is then sized by
+ * hf_set_workspace_need (the largest single-model need; op HF_OP_RUN or
+ * HF_OP_COMPARE, flags as hf_workspace_need; -1 on bad arguments), and M*B
+ * must fit an int.
+ */
+int hf_run_set(hf_model_set_t set, const float *dev_state0, int64_t model_stride,
+               float *dev_state_final, const float *dev_x, const double *dev_plan,
+               int poisson_mode, int B, int nx, int T, float c, float dt, float nu, float dx2,
+               float *dev_traj, float *dev_flux_traj, float *dev_metrics,
+               void *dev_workspace, int64_t workspace_bytes, void *stream);
+int hf_run_compare_set(hf_model_set_t set, const float *dev_state0, int64_t model_stride,
+                       float *dev_state_final, const float *dev_x, const double *dev_plan,
+                       int poisson_mode, int B, int nx, int T, float c, float dt, float nu, float dx2,
+                       float *dev_mse, float *dev_metrics, float *dev_metrics_classical,
+                       void *dev_workspace, int64_t workspace_bytes, void *stream);
+int64_t hf_set_workspace_need(hf_model_set_t set, int op, int B, int nx, int T, int flags);
+
+/*
  * Metric series of recorded trajectories (the host-side scoring of
  * scripts/evaluation/evaluate_all.py:118-159 and evaluate_multi_ic.py:88-94,
  * on the device):
