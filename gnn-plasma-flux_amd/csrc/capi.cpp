@@ -583,6 +583,77 @@ int hf_unroll_adjoint(const float *st, const float *st_next, const float *target
   return HF_OK;
 }
 
+// The _ex calls' conservation arguments, checked alike (before any device call).  cons NULL: the
+// reference and coefficient buffers must be NULL too, and *out stays NULL (the plain call's work).
+static int cons_args(const char *name, const float *cons, float cons_scale, const double *ref, float *coef,
+                     const float *target, const void *ws, int64_t ws_bytes, int64_t need_ex, hf::ConsTerms *store,
+                     const hf::ConsTerms **out) {
+  const std::string fn = name;
+  *out = nullptr;
+  if (!cons) {
+    if (ref || coef) return fail(HF_EINVAL, fn + ": dev_cons_ref / dev_cons_coef given without cons");
+    return HF_OK;
+  }
+  if (!(cons[0] >= 0.f) || !(cons[1] >= 0.f)) return fail(HF_EINVAL, fn + ": cons (lam_e, lam_q) must be >= 0");
+  if (!ref || !coef || !ws || !target)
+    return fail(HF_EINVAL, fn + ": cons needs dev_target, dev_cons_ref, dev_cons_coef and a workspace (NULL pointer)");
+  if (ws_bytes < need_ex) return fail(HF_EINVAL, fn + ": workspace smaller than the _ex workspace query");
+  store->lam_e = cons[0], store->lam_q = cons[1], store->scale = cons_scale;
+  store->ref = ref, store->coef = coef;
+  *out = store;
+  return HF_OK;
+}
+
+int hf_state_moments(const float *states, int64_t rows, int nx, double *moments, void *stream) {
+  if (rows < 1 || nx < 1) return fail(HF_EINVAL, "hf_state_moments: need rows >= 1, nx >= 1");
+  if (!states || !moments) return fail(HF_EINVAL, "hf_state_moments: NULL pointer");
+  if ((rows - 1) / 4 + 1 > 0x7fffffffLL) return fail(HF_EINVAL, "hf_state_moments: rows / 4 >= 2^31");
+  HF_CHECK_HIP(hf::launch_state_moments(states, rows, nx, moments, as_stream(stream)), "hf_state_moments");
+  return HF_OK;
+}
+
+int64_t hf_unroll_workspace_bytes_ex(int B, int nx) {
+  if (B < 1 || nx < 1) return -1;
+  return hf::unroll_ws_bytes_ex(B, nx);
+}
+
+int hf_unroll_update_ex(const float *fe, const float *st, const float *x, const double *pc, int pm, int B, int nx,
+                        float c, float dt, float *st_next, float *nf_next, const float *target, const float *weights,
+                        float scale, float *losses, void *ws, int64_t ws_bytes, const float *cons, float cons_scale,
+                        const double *cons_ref, float *cons_coef, void *stream) {
+  const char *fn = "hf_unroll_update_ex";
+  if (B < 1 || nx < 1) return fail(HF_EINVAL, "hf_unroll_update_ex: need B >= 1, nx >= 1");
+  if (!fe || !st || !x || !pc || !st_next || !ws) return fail(HF_EINVAL, "hf_unroll_update_ex: NULL pointer");
+  if (target && (!weights || !losses))
+    return fail(HF_EINVAL, "hf_unroll_update_ex: NULL weights or losses with a target");
+  if (st == st_next) return fail(HF_EINVAL, "hf_unroll_update_ex: state and state_next must not alias");
+  if (ws_bytes < hf::unroll_ws_bytes(B, nx))
+    return fail(HF_EINVAL, "hf_unroll_update_ex: workspace smaller than hf_unroll_workspace_bytes");
+  hf::ConsTerms ct{};
+  const hf::ConsTerms *cp = nullptr;
+  if (int rc = cons_args(fn, cons, cons_scale, cons_ref, cons_coef, target, ws, ws_bytes, hf::unroll_ws_bytes_ex(B, nx),
+                         &ct, &cp))
+    return rc;
+  if (int rc = unroll_mode_args(fn, pm, nx)) return rc;
+  HF_CHECK_HIP(hf::launch_unroll_update_ex(fe, st, x, pc, B, nx, c, dt, st_next, nf_next, target, weights, scale, losses,
+                                           ws, cp, as_stream(stream)),
+               fn);
+  return HF_OK;
+}
+
+int hf_unroll_adjoint_ex(const float *st, const float *st_next, const float *target, const float *weights, float scale,
+                         const float *direct_next, const float *gnf_next, const double *pc, int pm, int B, int nx,
+                         float c, float dt, float *g_fe, float *direct, const float *cons_coef, void *stream) {
+  if (B < 1 || nx < 1) return fail(HF_EINVAL, "hf_unroll_adjoint_ex: need B >= 1, nx >= 1");
+  if (!st || !st_next || !target || !weights || !pc || !g_fe)
+    return fail(HF_EINVAL, "hf_unroll_adjoint_ex: NULL pointer");
+  if (int rc = unroll_mode_args("hf_unroll_adjoint_ex", pm, nx)) return rc;
+  HF_CHECK_HIP(hf::launch_unroll_adjoint_ex(st, st_next, target, weights, scale, direct_next, gnf_next, pc, B, nx, c, dt,
+                                            g_fe, direct, cons_coef, as_stream(stream)),
+               "hf_unroll_adjoint_ex");
+  return HF_OK;
+}
+
 // ------------------------------------------------------- unrolled training, PureGNN
 int64_t hf_pure_unroll_workspace_bytes(int B, int nx) {
   if (!hf::pure_unroll_shape_ok(B, nx)) return -1;
@@ -616,6 +687,51 @@ int hf_pure_unroll_adjoint(const float *st_next, const float *target, const floa
   HF_CHECK_HIP(hf::launch_pure_unroll_adjoint(st_next, target, weights, scale, gd_next, gnf_next, B, nx, gd,
                                               as_stream(stream)),
                "hf_pure_unroll_adjoint");
+  return HF_OK;
+}
+
+int64_t hf_pure_unroll_workspace_bytes_ex(int B, int nx) {
+  if (!hf::pure_unroll_shape_ok(B, nx)) return -1;
+  return hf::pure_unroll_ws_bytes_ex(B, nx);
+}
+
+int hf_pure_unroll_update_ex(const float *delta, const float *st, const float *x, int B, int nx, float *st_next,
+                             float *nf_next, const float *target, const float *weights, float scale, float *losses,
+                             void *ws, int64_t ws_bytes, const float *cons, float cons_scale, const double *cons_ref,
+                             float *cons_coef, void *stream) {
+  const char *fn = "hf_pure_unroll_update_ex";
+  if (B < 1 || nx < 1) return fail(HF_EINVAL, "hf_pure_unroll_update_ex: need B >= 1, nx >= 1");
+  if (!delta || !st || !x || !st_next) return fail(HF_EINVAL, "hf_pure_unroll_update_ex: NULL pointer");
+  if (st == st_next) return fail(HF_EINVAL, "hf_pure_unroll_update_ex: state and state_next must not alias");
+  if (!hf::pure_unroll_shape_ok(B, nx))
+    return fail(HF_EINVAL, "hf_pure_unroll_update_ex: B * ceil(nx / 1024) >= 2^31");
+  if (target) {
+    if (!weights || !losses || !ws)
+      return fail(HF_EINVAL, "hf_pure_unroll_update_ex: NULL weights, losses or workspace with a target");
+    if (ws_bytes < hf::pure_unroll_ws_bytes(B, nx))
+      return fail(HF_EINVAL, "hf_pure_unroll_update_ex: workspace smaller than hf_pure_unroll_workspace_bytes");
+  }
+  hf::ConsTerms ct{};
+  const hf::ConsTerms *cp = nullptr;
+  if (int rc = cons_args(fn, cons, cons_scale, cons_ref, cons_coef, target, ws, ws_bytes,
+                         hf::pure_unroll_ws_bytes_ex(B, nx), &ct, &cp))
+    return rc;
+  HF_CHECK_HIP(hf::launch_pure_unroll_update_ex(delta, st, x, B, nx, st_next, nf_next, target, weights, scale, losses, ws,
+                                                cp, as_stream(stream)),
+               fn);
+  return HF_OK;
+}
+
+int hf_pure_unroll_adjoint_ex(const float *st_next, const float *target, const float *weights, float scale,
+                              const float *gd_next, const float *gnf_next, int B, int nx, float *gd,
+                              const float *cons_coef, void *stream) {
+  if (B < 1 || nx < 1) return fail(HF_EINVAL, "hf_pure_unroll_adjoint_ex: need B >= 1, nx >= 1");
+  if (!st_next || !target || !weights || !gd) return fail(HF_EINVAL, "hf_pure_unroll_adjoint_ex: NULL pointer");
+  if (!hf::pure_unroll_shape_ok(B, nx))
+    return fail(HF_EINVAL, "hf_pure_unroll_adjoint_ex: B * ceil(nx / 1024) >= 2^31");
+  HF_CHECK_HIP(hf::launch_pure_unroll_adjoint_ex(st_next, target, weights, scale, gd_next, gnf_next, B, nx, gd, cons_coef,
+                                                 as_stream(stream)),
+               "hf_pure_unroll_adjoint_ex");
   return HF_OK;
 }
 
@@ -888,6 +1004,49 @@ int hf_pinn_unroll_adjoint(const float *pred, const float *state, const float *t
   HF_CHECK_HIP(hf::launch_pinn_unroll_adjoint(pred, state, target, pred_next, grad_state_next, B, nx, weights,
                                               loss_scale, phys, phys_scale, dt, dx, nu, plan, grad_out,
                                               as_stream(stream)),
+               fn);
+  return HF_OK;
+}
+
+int64_t hf_pinn_unroll_workspace_bytes_ex(int B, int nx) {
+  if (B < 1 || nx < 1) return -1;
+  return hf::pinn_unroll_ws_bytes_ex(B, nx);
+}
+
+int hf_pinn_unroll_loss_ex(const float *pred, const float *state, const float *target, int B, int nx,
+                           const float *weights, float loss_scale, const float *phys, float phys_scale, double dt,
+                           double dx, double nu, const double *plan, float *losses, void *ws, int64_t ws_bytes,
+                           const float *cons, float cons_scale, const double *cons_ref, float *cons_coef,
+                           void *stream) {
+  const char *fn = "hf_pinn_unroll_loss_ex";
+  if (int rc = pinn_unroll_args(fn, pred, state, target, B, nx, weights, phys, dt, dx, plan)) return rc;
+  if (!losses || !ws) return fail(HF_EINVAL, std::string(fn) + ": NULL pointer");
+  if (ws_bytes < hf::pinn_unroll_ws_bytes(B, nx))
+    return fail(HF_EINVAL, std::string(fn) + ": workspace smaller than hf_pinn_unroll_workspace_bytes");
+  hf::ConsTerms ct{};
+  const hf::ConsTerms *cp = nullptr;
+  if (int rc = cons_args(fn, cons, cons_scale, cons_ref, cons_coef, target, ws, ws_bytes,
+                         hf::pinn_unroll_ws_bytes_ex(B, nx), &ct, &cp))
+    return rc;
+  HF_CHECK_HIP(hf::launch_pinn_unroll_loss_ex(pred, state, target, B, nx, weights, loss_scale, phys, phys_scale, dt, dx,
+                                              nu, plan, losses, ws, cp, as_stream(stream)),
+               fn);
+  return HF_OK;
+}
+
+int hf_pinn_unroll_adjoint_ex(const float *pred, const float *state, const float *target, const float *pred_next,
+                              const float *grad_state_next, int B, int nx, const float *weights, float loss_scale,
+                              const float *phys, float phys_scale, double dt, double dx, double nu, const double *plan,
+                              float *grad_out, const float *cons_coef, void *stream) {
+  const char *fn = "hf_pinn_unroll_adjoint_ex";
+  if (int rc = pinn_unroll_args(fn, pred, state, target, B, nx, weights, phys, dt, dx, plan)) return rc;
+  if (!grad_out) return fail(HF_EINVAL, std::string(fn) + ": NULL pointer");
+  // every phase reads the inputs after the first values of dev_grad_out are written
+  for (const float *in : {pred, state, target, pred_next, grad_state_next, cons_coef})
+    if (in == grad_out) return fail(HF_EINVAL, std::string(fn) + ": dev_grad_out must not alias an input");
+  HF_CHECK_HIP(hf::launch_pinn_unroll_adjoint_ex(pred, state, target, pred_next, grad_state_next, B, nx, weights,
+                                                 loss_scale, phys, phys_scale, dt, dx, nu, plan, grad_out, cons_coef,
+                                                 as_stream(stream)),
                fn);
   return HF_OK;
 }

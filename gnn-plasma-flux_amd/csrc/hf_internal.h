@@ -299,6 +299,21 @@ hipError_t launch_fv_step(const float *in, int64_t ld_in, float *out, int64_t ld
 // Poisson sum run tiled over global memory.
 constexpr int kFvLdsMaxNx = 6144;
 
+// Per-row moments of states [rows][3][nx] (metrics.hip): moments[r] = (e, q) =
+// (0.5 (sum u^2 + sum E^2) / nx, sum n / nx) in float64, one wave per row, a
+// lane's cells in ascending order and the lanes in a fixed tree.  Any nx >= 1.
+hipError_t launch_state_moments(const float *states, int64_t rows, int nx, double *moments, hipStream_t s);
+
+// The energy and charge terms of the unrolled-training _ex calls
+// (include/hybridflux.h): L_cons's step term on the predicted state, the sums
+// riding the kernels' loss reduction.  ref [B][2] (eref, qref) float64, coef
+// [B][2] (ce, cq) float32 out; NULL ConsTerms: the state term alone.
+struct ConsTerms {
+  float lam_e, lam_q, scale;
+  const double *ref;
+  float *coef;
+};
+
 // Unrolled training (unroll.hip): one hybrid step from the FluxGNN's edge flux
 // fe [B][2nx] with the step's extras, and its adjoint; spectral Poisson,
 // nx <= kFvLdsMaxNx (unroll_nx_ok).  Contiguous [B][3][nx] states.
@@ -318,6 +333,18 @@ hipError_t launch_unroll_update(const float *fe, const float *st, const float *x
 hipError_t launch_unroll_adjoint(const float *st, const float *st_next, const float *target, const float *w, float scale,
                                  const float *direct_next, const float *gnf_next, const double *pc, int B, int nx,
                                  float c, float dt, float *g_fe, float *direct, hipStream_t s);
+//  _ex:     losses[4] = (total, state, energy, charge), ws of unroll_ws_bytes_ex
+//           with cons; the adjoint's seed of u', E' gains coef[b][0] u', coef[b][0] E'
+//           (cq is not added: no gradient through the conservative update).  cons /
+//           coef NULL: the plain calls' bits.
+int64_t unroll_ws_bytes_ex(int B, int nx);
+hipError_t launch_unroll_update_ex(const float *fe, const float *st, const float *x, const double *pc, int B, int nx,
+                                   float c, float dt, float *st_next, float *nf_next, const float *target, const float *w,
+                                   float scale, float *losses, void *ws, const ConsTerms *cons, hipStream_t s);
+hipError_t launch_unroll_adjoint_ex(const float *st, const float *st_next, const float *target, const float *w,
+                                    float scale, const float *direct_next, const float *gnf_next, const double *pc, int B,
+                                    int nx, float c, float dt, float *g_fe, float *direct, const float *coef,
+                                    hipStream_t s);
 
 // Unrolled training of PureGNN (pure_unroll.hip): the residual update of one
 // rollout step from PureGNN's delta [B*nx][3] with the step's extras, and its
@@ -337,6 +364,16 @@ hipError_t launch_pure_unroll_update(const float *delta, const float *st, const 
 hipError_t launch_pure_unroll_adjoint(const float *st_next, const float *target, const float *w, float scale,
                                       const float *gd_next, const float *gnf_next, int B, int nx, float *gd,
                                       hipStream_t s);
+//  _ex:     losses[4] = (total, state, energy, charge), ws of
+//           pure_unroll_ws_bytes_ex with cons; the adjoint's seed gains (cq, ce u',
+//           ce E').  cons / coef NULL: the plain calls' bits.
+int64_t pure_unroll_ws_bytes_ex(int B, int nx);
+hipError_t launch_pure_unroll_update_ex(const float *delta, const float *st, const float *x, int B, int nx,
+                                        float *st_next, float *nf_next, const float *target, const float *w, float scale,
+                                        float *losses, void *ws, const ConsTerms *cons, hipStream_t s);
+hipError_t launch_pure_unroll_adjoint_ex(const float *st_next, const float *target, const float *w, float scale,
+                                         const float *gd_next, const float *gnf_next, int B, int nx, float *gd,
+                                         const float *coef, hipStream_t s);
 
 // Unrolled training of PINN (pinn_unroll.hip): the loss term of one rollout
 // step and the gradient its hf_pinn_backward takes in; include/hybridflux.h has
@@ -355,6 +392,19 @@ hipError_t launch_pinn_unroll_adjoint(const float *pred, const float *state, con
                                       const float *grad_state_next, int B, int nx, const float *w, float scale,
                                       const float *phys, float phys_scale, double dt, double dx, double nu,
                                       const double *pc, float *grad_out, hipStream_t s);
+//  _ex:     losses[7] = (total, data, cont, mom, pois, energy, charge), ws of
+//           pinn_unroll_ws_bytes_ex with cons; d term / d pred gains (cq, ce p_u,
+//           ce p_E).  cons / coef NULL: the plain calls' bits.
+int64_t pinn_unroll_ws_bytes_ex(int B, int nx);
+hipError_t launch_pinn_unroll_loss_ex(const float *pred, const float *state, const float *target, int B, int nx,
+                                      const float *w, float scale, const float *phys, float phys_scale, double dt,
+                                      double dx, double nu, const double *pc, float *losses, void *ws,
+                                      const ConsTerms *cons, hipStream_t s);
+hipError_t launch_pinn_unroll_adjoint_ex(const float *pred, const float *state, const float *target,
+                                         const float *pred_next, const float *grad_state_next, int B, int nx,
+                                         const float *w, float scale, const float *phys, float phys_scale, double dt,
+                                         double dx, double nu, const double *pc, float *grad_out, const float *coef,
+                                         hipStream_t s);
 
 // The whole classical rollout (T steps of launch_fv_step's classical update)
 // in one launch, states held in registers: FFT nx up to 1024 (fv_run_fused).

@@ -75,7 +75,43 @@ __global__ __launch_bounds__(kSumThreads) void rollout_summary_kernel(const floa
   }
 }
 
+// (e, q) of one state row per wave: the lane's cells in ascending order, the
+// lanes in a fixed tree, everything in float64 (the squares too).
+constexpr int kMomWaves = 4;
+__global__ __launch_bounds__(64 * kMomWaves) void state_moments_kernel(const float *__restrict__ st, int64_t rows, int nx,
+                                                                      double *__restrict__ mom) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * kMomWaves + (threadIdx.x >> 6);
+  if (r >= rows) return;  // a whole wave; nothing below synchronises the workgroup
+  const float *s = st + r * 3 * nx;
+  double su2 = 0.0, sE2 = 0.0, sn = 0.0;
+  for (int64_t i = lane; i < nx; i += 64) {
+    const double u = (double)s[nx + i], E = (double)s[2 * (int64_t)nx + i];
+    sn += (double)s[i];
+    su2 += u * u;
+    sE2 += E * E;
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    sn += __shfl_xor(sn, o, 64);
+    su2 += __shfl_xor(su2, o, 64);
+    sE2 += __shfl_xor(sE2, o, 64);
+  }
+  if (lane == 0) {
+    mom[2 * r] = 0.5 * (su2 + sE2) / (double)nx;
+    mom[2 * r + 1] = sn / (double)nx;
+  }
+}
+
 }  // namespace
+
+hipError_t launch_state_moments(const float *states, int64_t rows, int nx, double *moments, hipStream_t s) {
+  if (rows <= 0) return hipSuccess;
+  const int64_t grid = (rows - 1) / kMomWaves + 1;
+  if (nx < 1 || grid > 0x7fffffffLL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(state_moments_kernel, dim3((unsigned)grid), dim3(64 * kMomWaves), 0, s, states, rows, nx, moments);
+  return hipGetLastError();
+}
 
 hipError_t launch_rollout_summary(const float *met, const float *mse, const float *met_ref, int B, int T,
                                   float *summary, float *drift, hipStream_t s) {

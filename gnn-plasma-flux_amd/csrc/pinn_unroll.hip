@@ -25,7 +25,9 @@ namespace {
 
 constexpr int kPuThreads = 256;
 // Workspace: [0, 256) the arrival counter (zeroed by the launcher's memset
-// node before every launch), then four float64 partials per IC (data, cont, mom, pois).
+// node before every launch), then four float64 partials per IC (data, cont, mom, pois);
+// the _ex call with the conservation terms adds two per IC behind them
+// (lam_e r_e^2, lam_q r_q^2).
 constexpr size_t kPuCounterBytes = 256;
 
 inline size_t al256(size_t b) { return (b + 255) / 256 * 256; }
@@ -71,8 +73,15 @@ struct LossArgs {
   double *part;         // [B][4]
   unsigned *cnt;
   float *losses;
+  // the _ex call's energy and charge terms (include/hybridflux.h); cons == false: the wider row only
+  bool cons;
+  double lam_e, lam_q, cscale;  // cscale = cons_scale
+  const double *cref;           // [B][2] (eref, qref)
+  float *coef;                  // [B][2] (ce, cq)
+  double *cpart;                // [B][2]
 };
 
+template <bool EX>
 __global__ __launch_bounds__(kPuThreads) void pinn_unroll_loss_kernel(LossArgs a) {
   extern __shared__ double s_dyn[];
   __shared__ double red[4][4];
@@ -89,10 +98,16 @@ __global__ __launch_bounds__(kPuThreads) void pinn_unroll_loss_kernel(LossArgs a
     }
     __syncthreads();
   }
-  double sd = 0.0, sc = 0.0, sm = 0.0, sp = 0.0;
+  const bool cons = EX && a.cons;
+  double sd = 0.0, sc = 0.0, sm = 0.0, sp = 0.0, su2 = 0.0, sE2 = 0.0, sn = 0.0;
   for (int i = threadIdx.x; i < nx; i += kPuThreads) {
     const float pn = P[i], pu = P[nx + i], pE = P[2 * nx + i];
     sd += sq_err(pn, T[i], a.w0) + sq_err(pu, T[nx + i], a.w1) + sq_err(pE, T[2 * nx + i], a.w2);
+    if (cons) {
+      su2 += (double)pu * (double)pu;
+      sE2 += (double)pE * (double)pE;
+      sn += (double)pn;
+    }
     if (a.f.on) {
       double rc, rm;
       residuals(S, i, nx, pn, pu, a.f, rc, rm);
@@ -112,8 +127,31 @@ __global__ __launch_bounds__(kPuThreads) void pinn_unroll_loss_kernel(LossArgs a
   sp = wave_sum(sp);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) red[wave][0] = sd, red[wave][1] = sc, red[wave][2] = sm, red[wave][3] = sp;
-  __syncthreads();
-  if (threadIdx.x >= 64) return;
+  if constexpr (EX) {
+    __shared__ double redc[4][3];
+    if (cons) {  // (uniform)
+      su2 = wave_sum(su2);
+      sE2 = wave_sum(sE2);
+      sn = wave_sum(sn);
+      if (lane == 0) redc[wave][0] = su2, redc[wave][1] = sE2, redc[wave][2] = sn;
+    }
+    __syncthreads();
+    if (threadIdx.x >= 64) return;
+    if (cons && lane == 0) {
+      // this IC's complete sums: its coefficients (float64, rounded once) and its two term partials
+      const double tu = ((redc[0][0] + redc[1][0]) + redc[2][0]) + redc[3][0];
+      const double tE = ((redc[0][1] + redc[1][1]) + redc[2][1]) + redc[3][1];
+      const double tn = ((redc[0][2] + redc[1][2]) + redc[2][2]) + redc[3][2];
+      const double re = 0.5 * (tu + tE) / (double)nx - a.cref[2 * b], rq = tn / (double)nx - a.cref[2 * b + 1];
+      a.coef[2 * b] = (float)(2.0 * a.lam_e * a.cscale * re / (double)nx);
+      a.coef[2 * b + 1] = (float)(2.0 * a.lam_q * a.cscale * rq / (double)nx);
+      a.cpart[2 * b] = a.lam_e * (re * re);
+      a.cpart[2 * b + 1] = a.lam_q * (rq * rq);
+    }
+  } else {
+    __syncthreads();
+    if (threadIdx.x >= 64) return;
+  }
   if (lane < 4) a.part[b * 4 + lane] = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
   // The last workgroup to arrive sums the partials: agent-scope release before
   // the ticket, agent-scope acquire after the last one (the per-XCD L2s are not
@@ -134,8 +172,26 @@ __global__ __launch_bounds__(kPuThreads) void pinn_unroll_loss_kernel(LossArgs a
   }
 #pragma unroll
   for (int k = 0; k < 4; ++k) q[k] = wave_sum(q[k]);
+  double qe = 0.0, qq = 0.0;
+  if (cons) {  // (uniform)
+    for (int i = lane; i < a.B; i += 64) qe += a.cpart[2 * (int64_t)i], qq += a.cpart[2 * (int64_t)i + 1];
+    qe = wave_sum(qe);
+    qq = wave_sum(qq);
+  }
   if (lane == 0) {
     const double ld = q[0] * a.scale, lc = q[1] * a.sc, lm = q[2] * a.sm, lp = q[3] * a.sp;
+    if constexpr (EX) {
+      // (total, data, cont, mom, pois, energy, charge): entries 1..4 are the plain call's, and so is 0 without the terms
+      const double le = qe * a.cscale, lq = qq * a.cscale;
+      a.losses[0] = cons ? (float)(((((ld + lc) + lm) + lp) + le) + lq) : (float)(((ld + lc) + lm) + lp);
+      a.losses[1] = (float)ld;
+      a.losses[2] = (float)lc;
+      a.losses[3] = (float)lm;
+      a.losses[4] = (float)lp;
+      a.losses[5] = (float)le;
+      a.losses[6] = (float)lq;
+      return;
+    }
     a.losses[0] = (float)(((ld + lc) + lm) + lp);
     a.losses[1] = (float)ld;
     a.losses[2] = (float)lc;
@@ -155,8 +211,12 @@ struct AdjArgs {
   double gc, gm, gp;     // 2 phys_scale lambda_c / dt, ... lambda_m / dt, ... lambda_p
   double qc, qm;         // 2 phys_scale lambda_c, ... lambda_m
   float *g;
+  const float *coef;     // [B][2] = (ce, cq) or NULL (read by the EX kernel only)
 };
 
+// EX with coef: d term_k / d p gains cq_b, ce_b p_u, ce_b p_E on its three
+// channels (one float32 product; added to the state seed before the residual terms).
+template <bool EX>
 __global__ __launch_bounds__(kPuThreads) void pinn_unroll_adjoint_kernel(AdjArgs a) {
   extern __shared__ double s_dyn[];
   const int nx = a.nx;
@@ -178,6 +238,14 @@ __global__ __launch_bounds__(kPuThreads) void pinn_unroll_adjoint_kernel(AdjArgs
     const double pn = P[i], pu = P[nx + i], pE = P[2 * nx + i];
     double gn = a.gd0 * (pn - (double)T[i]), gu = a.gd1 * (pu - (double)T[nx + i]),
            gE = a.gd2 * (pE - (double)T[2 * nx + i]);
+    if constexpr (EX) {
+      if (a.coef) {  // (uniform)
+        const float ce = a.coef[2 * b];
+        gn += (double)a.coef[2 * b + 1];
+        gu += (double)(ce * P[nx + i]);
+        gE += (double)(ce * P[2 * nx + i]);
+      }
+    }
     if (a.f.on) {
       double rc, rm;
       residuals(S, i, nx, pn, pu, a.f, rc, rm);
@@ -262,9 +330,16 @@ int64_t pinn_unroll_ws_bytes(int B, int nx) {
   return (int64_t)(kPuCounterBytes + al256(sizeof(double) * 4 * (size_t)B));
 }
 
-hipError_t launch_pinn_unroll_loss(const float *pred, const float *state, const float *target, int B, int nx,
-                                   const float *w, float scale, const float *phys, float phys_scale, double dt,
-                                   double dx, double nu, const double *pc, float *losses, void *ws, hipStream_t s) {
+int64_t pinn_unroll_ws_bytes_ex(int B, int nx) {
+  return pinn_unroll_ws_bytes(B, nx) + (int64_t)al256(2 * sizeof(double) * (size_t)B);
+}
+
+namespace {
+
+template <bool EX>
+hipError_t loss_any(const float *pred, const float *state, const float *target, int B, int nx, const float *w,
+                    float scale, const float *phys, float phys_scale, double dt, double dx, double nu, const double *pc,
+                    float *losses, void *ws, const ConsTerms *cons, hipStream_t s) {
   if (!pinn_unroll_nx_ok(nx) || B < 1) return hipErrorInvalidValue;
   LossArgs a{};
   a.p = pred, a.t = target;
@@ -280,16 +355,23 @@ hipError_t launch_pinn_unroll_loss(const float *pred, const float *state, const 
   a.cnt = static_cast<unsigned *>(ws);
   a.part = reinterpret_cast<double *>(static_cast<char *>(ws) + kPuCounterBytes);
   a.losses = losses;
+  if (EX && cons) {
+    a.cons = true;
+    a.lam_e = (double)cons->lam_e, a.lam_q = (double)cons->lam_q, a.cscale = (double)cons->scale;
+    a.cref = cons->ref, a.coef = cons->coef;
+    a.cpart = reinterpret_cast<double *>(static_cast<char *>(ws) + pinn_unroll_ws_bytes(B, nx));
+  }
   // the arrival counter starts every launch at 0 (a memset node, not a kernel)
   if (hipError_t e = hipMemsetAsync(ws, 0, 16, s)) return e;
-  hipLaunchKernelGGL(pinn_unroll_loss_kernel, dim3((unsigned)B), dim3(kPuThreads), lds_bytes(a.f, nx), s, a);
+  hipLaunchKernelGGL(pinn_unroll_loss_kernel<EX>, dim3((unsigned)B), dim3(kPuThreads), lds_bytes(a.f, nx), s, a);
   return hipGetLastError();
 }
 
-hipError_t launch_pinn_unroll_adjoint(const float *pred, const float *state, const float *target, const float *pred_next,
-                                      const float *grad_state_next, int B, int nx, const float *w, float scale,
-                                      const float *phys, float phys_scale, double dt, double dx, double nu,
-                                      const double *pc, float *grad_out, hipStream_t s) {
+template <bool EX>
+hipError_t adjoint_any(const float *pred, const float *state, const float *target, const float *pred_next,
+                       const float *grad_state_next, int B, int nx, const float *w, float scale, const float *phys,
+                       float phys_scale, double dt, double dx, double nu, const double *pc, float *grad_out,
+                       const float *coef, hipStream_t s) {
   if (!pinn_unroll_nx_ok(nx) || B < 1) return hipErrorInvalidValue;
   AdjArgs a{};
   a.p = pred, a.t = target;
@@ -308,8 +390,39 @@ hipError_t launch_pinn_unroll_adjoint(const float *pred, const float *state, con
     a.gp = 2.0 * (double)phys_scale * (double)phys[2];
   }
   a.g = grad_out;
-  hipLaunchKernelGGL(pinn_unroll_adjoint_kernel, dim3((unsigned)B), dim3(kPuThreads), lds_bytes(a.f, nx), s, a);
+  a.coef = coef;
+  hipLaunchKernelGGL(pinn_unroll_adjoint_kernel<EX>, dim3((unsigned)B), dim3(kPuThreads), lds_bytes(a.f, nx), s, a);
   return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_pinn_unroll_loss(const float *pred, const float *state, const float *target, int B, int nx,
+                                   const float *w, float scale, const float *phys, float phys_scale, double dt,
+                                   double dx, double nu, const double *pc, float *losses, void *ws, hipStream_t s) {
+  return loss_any<false>(pred, state, target, B, nx, w, scale, phys, phys_scale, dt, dx, nu, pc, losses, ws, nullptr, s);
+}
+hipError_t launch_pinn_unroll_loss_ex(const float *pred, const float *state, const float *target, int B, int nx,
+                                      const float *w, float scale, const float *phys, float phys_scale, double dt,
+                                      double dx, double nu, const double *pc, float *losses, void *ws,
+                                      const ConsTerms *cons, hipStream_t s) {
+  return loss_any<true>(pred, state, target, B, nx, w, scale, phys, phys_scale, dt, dx, nu, pc, losses, ws, cons, s);
+}
+
+hipError_t launch_pinn_unroll_adjoint(const float *pred, const float *state, const float *target, const float *pred_next,
+                                      const float *grad_state_next, int B, int nx, const float *w, float scale,
+                                      const float *phys, float phys_scale, double dt, double dx, double nu,
+                                      const double *pc, float *grad_out, hipStream_t s) {
+  return adjoint_any<false>(pred, state, target, pred_next, grad_state_next, B, nx, w, scale, phys, phys_scale, dt, dx,
+                            nu, pc, grad_out, nullptr, s);
+}
+hipError_t launch_pinn_unroll_adjoint_ex(const float *pred, const float *state, const float *target,
+                                         const float *pred_next, const float *grad_state_next, int B, int nx,
+                                         const float *w, float scale, const float *phys, float phys_scale, double dt,
+                                         double dx, double nu, const double *pc, float *grad_out, const float *coef,
+                                         hipStream_t s) {
+  return adjoint_any<true>(pred, state, target, pred_next, grad_state_next, B, nx, w, scale, phys, phys_scale, dt, dx,
+                           nu, pc, grad_out, coef, s);
 }
 
 }  // namespace hf

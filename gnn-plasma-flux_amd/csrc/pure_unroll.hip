@@ -26,7 +26,9 @@ inline size_t al256(size_t b) { return (b + 255) / 256 * 256; }
 inline int64_t tiles_of(int nx) { return ((int64_t)nx + kPuTile - 1) / kPuTile; }
 
 // Workspace: [0, 256) the arrival counter (zeroed by the launcher's memset
-// node before every launch), then one float64 loss partial per workgroup.
+// node before every launch), then one float64 loss partial per workgroup; the
+// _ex calls with the conservation terms add three float64 sums per workgroup
+// behind them (sum u^2, sum E^2, sum n of the tile).
 constexpr size_t kPuCounterBytes = 256;
 
 struct LossArgs {
@@ -44,13 +46,29 @@ __device__ __forceinline__ double wave_sum(double a) {
   return a;
 }
 
+// The energy and charge terms of the _ex calls (include/hybridflux.h): on ==
+// false leaves the kernel with the state term alone and the wider loss row.
+struct ConsArgs {
+  bool on;
+  double lam_e, lam_q, scale;  // scale = cons_scale
+  const double *ref;           // [B][2] (eref, qref)
+  float *coef;                 // [B][2] (ce, cq)
+  double *part;                // [B * tiles][3]
+  int B, nx, tiles;
+};
+
 // The step's loss from the per-workgroup partials, by the wave that arrives
 // last (unroll.hip's scheme).  Called by a whole wave after its partial store;
 // `total` waves call it per launch.  Agent-scope release before the ticket,
 // agent-scope acquire after the last one (the per-XCD L2s are not coherent);
 // the partials are summed in workgroup order per lane and then across the lanes
 // in a fixed tree, so the value does not depend on which wave arrives last.
-__device__ __forceinline__ void loss_arrive(const LossArgs &la, unsigned total, int lane) {
+// EX with the conservation terms: an IC's sums are complete only here, so this
+// wave also adds each IC's tiles in tile order (a lane takes ICs lane, lane +
+// 64, ...), writes the IC's two coefficients (float64, rounded once) and adds
+// the ICs' terms in the same fixed order.
+template <bool EX>
+__device__ __forceinline__ void loss_arrive(const LossArgs &la, const ConsArgs &ca, unsigned total, int lane) {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   unsigned t = 0;
@@ -63,7 +81,34 @@ __device__ __forceinline__ void loss_arrive(const LossArgs &la, unsigned total, 
   double a = 0.0;
   for (unsigned i = lane; i < total; i += 64) a += part[i];
   a = wave_sum(a);
-  if (lane == 0) la.loss[0] = (float)(a * la.scale);
+  if constexpr (!EX) {
+    if (lane == 0) la.loss[0] = (float)(a * la.scale);
+  } else {
+    double e = 0.0, q = 0.0;
+    if (ca.on) {
+      const double nx = (double)ca.nx;
+      for (int b = lane; b < ca.B; b += 64) {
+        const double *t = ca.part + (int64_t)b * ca.tiles * 3;
+        double su2 = 0.0, sE2 = 0.0, sn = 0.0;
+        for (int j = 0; j < ca.tiles; ++j) su2 += t[3 * j], sE2 += t[3 * j + 1], sn += t[3 * j + 2];
+        const double re = 0.5 * (su2 + sE2) / nx - ca.ref[2 * b], rq = sn / nx - ca.ref[2 * b + 1];
+        ca.coef[2 * b] = (float)(2.0 * ca.lam_e * ca.scale * re / nx);
+        ca.coef[2 * b + 1] = (float)(2.0 * ca.lam_q * ca.scale * rq / nx);
+        e += ca.lam_e * (re * re);
+        q += ca.lam_q * (rq * rq);
+      }
+      e = wave_sum(e);
+      q = wave_sum(q);
+    }
+    if (lane == 0) {
+      // (total, state, energy, charge): the state value is the plain call's
+      const double ls = a * la.scale, le = e * ca.scale, lq = q * ca.scale;
+      la.loss[0] = ca.on ? (float)((ls + le) + lq) : (float)ls;
+      la.loss[1] = (float)ls;
+      la.loss[2] = (float)le;
+      la.loss[3] = (float)lq;
+    }
+  }
 }
 
 // w (pred - target)^2 of one value, the difference rounded to float32
@@ -74,11 +119,12 @@ __device__ __forceinline__ double sq_err(float pred, float tgt, float w) {
 
 // ---------------------------------------------------------------------- forward
 // Workgroup blockIdx.x = b * tiles + t owns cells [t kPuTile, t kPuTile + n) of IC b.
+template <bool EX>
 __global__ __launch_bounds__(kPuThreads) void pure_unroll_update_kernel(const float *__restrict__ delta,
                                                                         const float *__restrict__ in,
                                                                         const float *__restrict__ x, int nx, int tiles,
                                                                         float *__restrict__ out, float *__restrict__ nf,
-                                                                        LossArgs la) {
+                                                                        LossArgs la, ConsArgs ca) {
   __shared__ __attribute__((aligned(16))) float Ld[3 * kPuTile];
   __shared__ double red[kPuThreads / 64];
   const int64_t b = blockIdx.x / (unsigned)tiles;
@@ -89,7 +135,8 @@ __global__ __launch_bounds__(kPuThreads) void pure_unroll_update_kernel(const fl
   __syncthreads();
   const int64_t sb = b * 3 * nx + c0;  // row 0 of the tile in the [B][3][nx] tensors
   const float *tg = la.tgt ? la.tgt + sb : nullptr;
-  double acc = 0.0;
+  const bool cons = EX && ca.on && tg;
+  double acc = 0.0, su2 = 0.0, sE2 = 0.0, sn = 0.0;
   for (int i = threadIdx.x; i < n; i += kPuThreads) {
     const float n_new = __fadd_rn(in[sb + i], Ld[3 * i]);
     const float u_new = __fadd_rn(in[sb + nx + i], Ld[3 * i + 1]);
@@ -101,35 +148,77 @@ __global__ __launch_bounds__(kPuThreads) void pure_unroll_update_kernel(const fl
     if (tg)
       acc += sq_err(n_new, tg[i], la.w0) + sq_err(u_new, tg[nx + i], la.w1) +
              sq_err(E_new, tg[2 * (int64_t)nx + i], la.w2);
+    if (cons) {
+      su2 += (double)u_new * (double)u_new;
+      sE2 += (double)E_new * (double)E_new;
+      sn += (double)n_new;
+    }
   }
   if (!tg) return;  // (uniform)
   acc = wave_sum(acc);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x >= 64) return;
-  if (threadIdx.x == 0) la.part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
-  loss_arrive(la, gridDim.x, threadIdx.x);
+  if constexpr (EX) {
+    __shared__ double redc[3][4];
+    if (cons) {  // (uniform)
+      su2 = wave_sum(su2);
+      sE2 = wave_sum(sE2);
+      sn = wave_sum(sn);
+      if ((threadIdx.x & 63) == 0) {
+        const int wv = threadIdx.x >> 6;
+        redc[0][wv] = su2, redc[1][wv] = sE2, redc[2][wv] = sn;
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x >= 64) return;
+    if (threadIdx.x == 0) la.part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+    if (cons && threadIdx.x < 3)
+      ca.part[(int64_t)blockIdx.x * 3 + threadIdx.x] =
+          ((redc[threadIdx.x][0] + redc[threadIdx.x][1]) + redc[threadIdx.x][2]) + redc[threadIdx.x][3];
+  } else {
+    __syncthreads();
+    if (threadIdx.x >= 64) return;
+    if (threadIdx.x == 0) la.part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+  }
+  loss_arrive<EX>(la, ca, gridDim.x, threadIdx.x);
 }
 
 // ---------------------------------------------------------------------- adjoint
 // grad_delta[cell][ch] = (seed + grad_delta_next[cell][ch]) + grad_nf_next[cell][ch],
-// seed = gs_ch (s' - target)[ch][cell]; a NULL term is left out.
+// seed = gs_ch (s' - target)[ch][cell]; a NULL term is left out.  EX with coef
+// [B][2] = (ce, cq): the seed gains cq_b, ce_b u', ce_b E' on its three
+// channels (one float32 product, added to the seed before the other terms).
+template <bool EX>
 __global__ __launch_bounds__(kPuThreads) void pure_unroll_adjoint_kernel(const float *__restrict__ sn,
                                                                          const float *__restrict__ tgt, float gs0,
                                                                          float gs1, float gs2,
                                                                          const float *__restrict__ gd_next,
                                                                          const float *__restrict__ gnf_next, int nx,
-                                                                         int tiles, float *__restrict__ gd) {
+                                                                         int tiles, float *__restrict__ gd,
+                                                                         const float *__restrict__ coef) {
   __shared__ __attribute__((aligned(16))) float Ls[3 * kPuTile];  // the seeds, (cell, channel) order
   __shared__ __attribute__((aligned(16))) float Lg[3 * kPuTile];  // columns 0..2 of grad_nf_next
   const int64_t b = blockIdx.x / (unsigned)tiles;
   const int c0 = (int)(blockIdx.x % (unsigned)tiles) * kPuTile;
   const int n = min(kPuTile, nx - c0);
   const int64_t sb = b * 3 * nx + c0;
+  float ce = 0.f, cq = 0.f;
+  if constexpr (EX) {
+    if (coef) ce = coef[2 * b], cq = coef[2 * b + 1];
+  }
   for (int i = threadIdx.x; i < n; i += kPuThreads) {
-    Ls[3 * i] = gs0 * (sn[sb + i] - tgt[sb + i]);
-    Ls[3 * i + 1] = gs1 * (sn[sb + nx + i] - tgt[sb + nx + i]);
-    Ls[3 * i + 2] = gs2 * (sn[sb + 2 * (int64_t)nx + i] - tgt[sb + 2 * (int64_t)nx + i]);
+    if constexpr (EX) {
+      if (coef) {  // (uniform)
+        const float un = sn[sb + nx + i], En = sn[sb + 2 * (int64_t)nx + i];
+        Ls[3 * i] = gs0 * (sn[sb + i] - tgt[sb + i]) + cq;
+        Ls[3 * i + 1] = gs1 * (un - tgt[sb + nx + i]) + ce * un;
+        Ls[3 * i + 2] = gs2 * (En - tgt[sb + 2 * (int64_t)nx + i]) + ce * En;
+      }
+    }
+    if (!EX || !coef) {
+      Ls[3 * i] = gs0 * (sn[sb + i] - tgt[sb + i]);
+      Ls[3 * i + 1] = gs1 * (sn[sb + nx + i] - tgt[sb + nx + i]);
+      Ls[3 * i + 2] = gs2 * (sn[sb + 2 * (int64_t)nx + i] - tgt[sb + 2 * (int64_t)nx + i]);
+    }
     if (gnf_next) {
       const pu_f4 g = *reinterpret_cast<const pu_f4 *>(gnf_next + 4 * (b * nx + c0 + i));
       Lg[3 * i] = g.x;
@@ -147,10 +236,57 @@ __global__ __launch_bounds__(kPuThreads) void pure_unroll_adjoint_kernel(const f
   }
 }
 
+template <bool EX>
+hipError_t update_any(const float *delta, const float *st, const float *x, int B, int nx, float *st_next, float *nf_next,
+                      const float *target, const float *w, float scale, float *loss, void *ws, const ConsTerms *cons,
+                      hipStream_t s) {
+  if (!pure_unroll_shape_ok(B, nx)) return hipErrorInvalidValue;
+  const int tiles = (int)tiles_of(nx);
+  const unsigned grid = (unsigned)((int64_t)B * tiles);
+  LossArgs la{};
+  ConsArgs ca{};
+  if (target) {
+    la.tgt = target;
+    la.w0 = w[0], la.w1 = w[1], la.w2 = w[2];
+    la.scale = (double)scale;
+    la.cnt = static_cast<unsigned *>(ws);
+    la.part = reinterpret_cast<double *>(static_cast<char *>(ws) + kPuCounterBytes);
+    la.loss = loss;
+    if (EX && cons) {
+      ca.on = true;
+      ca.lam_e = (double)cons->lam_e, ca.lam_q = (double)cons->lam_q, ca.scale = (double)cons->scale;
+      ca.ref = cons->ref, ca.coef = cons->coef;
+      ca.part = reinterpret_cast<double *>(static_cast<char *>(ws) + pure_unroll_ws_bytes(B, nx));
+      ca.B = B, ca.nx = nx, ca.tiles = tiles;
+    }
+    // the arrival counter starts every launch at 0 (a memset node, not a kernel)
+    if (hipError_t e = hipMemsetAsync(ws, 0, 16, s)) return e;
+  }
+  hipLaunchKernelGGL(pure_unroll_update_kernel<EX>, dim3(grid), dim3(kPuThreads), 0, s, delta, st, x, nx, tiles, st_next,
+                     nf_next, la, ca);
+  return hipGetLastError();
+}
+
+template <bool EX>
+hipError_t adjoint_any(const float *st_next, const float *target, const float *w, float scale, const float *gd_next,
+                       const float *gnf_next, int B, int nx, float *gd, const float *coef, hipStream_t s) {
+  if (!pure_unroll_shape_ok(B, nx)) return hipErrorInvalidValue;
+  const int tiles = (int)tiles_of(nx);
+  const unsigned grid = (unsigned)((int64_t)B * tiles);
+  float gs[3];
+  for (int k = 0; k < 3; ++k) gs[k] = (float)(2.0 * (double)w[k] * (double)scale);
+  hipLaunchKernelGGL(pure_unroll_adjoint_kernel<EX>, dim3(grid), dim3(kPuThreads), 0, s, st_next, target, gs[0], gs[1],
+                     gs[2], gd_next, gnf_next, nx, tiles, gd, coef);
+  return hipGetLastError();
+}
+
 }  // namespace
 
 int64_t pure_unroll_ws_bytes(int B, int nx) {
   return (int64_t)(kPuCounterBytes + al256(sizeof(double) * (size_t)((int64_t)B * tiles_of(nx))));
+}
+int64_t pure_unroll_ws_bytes_ex(int B, int nx) {
+  return pure_unroll_ws_bytes(B, nx) + (int64_t)al256(3 * sizeof(double) * (size_t)((int64_t)B * tiles_of(nx)));
 }
 
 // one workgroup per tile: B * tiles of them must fit a grid
@@ -159,36 +295,23 @@ bool pure_unroll_shape_ok(int B, int nx) { return B >= 1 && nx >= 1 && (int64_t)
 hipError_t launch_pure_unroll_update(const float *delta, const float *st, const float *x, int B, int nx, float *st_next,
                                      float *nf_next, const float *target, const float *w, float scale, float *loss,
                                      void *ws, hipStream_t s) {
-  if (!pure_unroll_shape_ok(B, nx)) return hipErrorInvalidValue;
-  const int tiles = (int)tiles_of(nx);
-  const unsigned grid = (unsigned)((int64_t)B * tiles);
-  LossArgs la{};
-  if (target) {
-    la.tgt = target;
-    la.w0 = w[0], la.w1 = w[1], la.w2 = w[2];
-    la.scale = (double)scale;
-    la.cnt = static_cast<unsigned *>(ws);
-    la.part = reinterpret_cast<double *>(static_cast<char *>(ws) + kPuCounterBytes);
-    la.loss = loss;
-    // the arrival counter starts every launch at 0 (a memset node, not a kernel)
-    if (hipError_t e = hipMemsetAsync(ws, 0, 16, s)) return e;
-  }
-  hipLaunchKernelGGL(pure_unroll_update_kernel, dim3(grid), dim3(kPuThreads), 0, s, delta, st, x, nx, tiles, st_next,
-                     nf_next, la);
-  return hipGetLastError();
+  return update_any<false>(delta, st, x, B, nx, st_next, nf_next, target, w, scale, loss, ws, nullptr, s);
+}
+hipError_t launch_pure_unroll_update_ex(const float *delta, const float *st, const float *x, int B, int nx,
+                                        float *st_next, float *nf_next, const float *target, const float *w, float scale,
+                                        float *losses, void *ws, const ConsTerms *cons, hipStream_t s) {
+  return update_any<true>(delta, st, x, B, nx, st_next, nf_next, target, w, scale, losses, ws, cons, s);
 }
 
 hipError_t launch_pure_unroll_adjoint(const float *st_next, const float *target, const float *w, float scale,
                                       const float *gd_next, const float *gnf_next, int B, int nx, float *gd,
                                       hipStream_t s) {
-  if (!pure_unroll_shape_ok(B, nx)) return hipErrorInvalidValue;
-  const int tiles = (int)tiles_of(nx);
-  const unsigned grid = (unsigned)((int64_t)B * tiles);
-  float gs[3];
-  for (int k = 0; k < 3; ++k) gs[k] = (float)(2.0 * (double)w[k] * (double)scale);
-  hipLaunchKernelGGL(pure_unroll_adjoint_kernel, dim3(grid), dim3(kPuThreads), 0, s, st_next, target, gs[0], gs[1],
-                     gs[2], gd_next, gnf_next, nx, tiles, gd);
-  return hipGetLastError();
+  return adjoint_any<false>(st_next, target, w, scale, gd_next, gnf_next, B, nx, gd, nullptr, s);
+}
+hipError_t launch_pure_unroll_adjoint_ex(const float *st_next, const float *target, const float *w, float scale,
+                                         const float *gd_next, const float *gnf_next, int B, int nx, float *gd,
+                                         const float *coef, hipStream_t s) {
+  return adjoint_any<true>(st_next, target, w, scale, gd_next, gnf_next, B, nx, gd, coef, s);
 }
 
 }  // namespace hf

@@ -24,7 +24,9 @@ typedef float un_f4 __attribute__((ext_vector_type(4)));
 inline size_t al256(size_t b) { return (b + 255) / 256 * 256; }
 
 // Workspace: [0, 256) the arrival counter (zeroed by the launcher's memset
-// node before every launch), then one float64 loss partial per IC.
+// node before every launch), then one float64 loss partial per IC; the _ex
+// calls with the conservation terms add two float64 values per IC behind them
+// (lam_e r_e^2, lam_q r_q^2).
 constexpr size_t kUnCounterBytes = 256;
 
 struct LossArgs {
@@ -42,13 +44,35 @@ __device__ __forceinline__ double wave_sum(double a) {
   return a;
 }
 
+// The energy and charge terms of the _ex calls (include/hybridflux.h): on ==
+// false leaves the kernel with the state term alone and the wider loss row.
+struct ConsArgs {
+  bool on;
+  double lam_e, lam_q, scale;  // scale = cons_scale
+  const double *ref;           // [B][2] (eref, qref)
+  float *coef;                 // [B][2] (ce, cq)
+  double *part;                // [B][2] (lam_e r_e^2, lam_q r_q^2)
+};
+
+// One IC's complete sums -> its two coefficients and its two term partials, by
+// the one lane that holds them: everything in float64, the coefficients rounded once.
+__device__ __forceinline__ void cons_finish(const ConsArgs &ca, int64_t b, int nx, double su2, double sE2, double sn) {
+  const double e = 0.5 * (su2 + sE2) / (double)nx, q = sn / (double)nx;
+  const double re = e - ca.ref[2 * b], rq = q - ca.ref[2 * b + 1];
+  ca.coef[2 * b] = (float)(2.0 * ca.lam_e * ca.scale * re / (double)nx);
+  ca.coef[2 * b + 1] = (float)(2.0 * ca.lam_q * ca.scale * rq / (double)nx);
+  ca.part[2 * b] = ca.lam_e * (re * re);
+  ca.part[2 * b + 1] = ca.lam_q * (rq * rq);
+}
+
 // The step's loss from the per-IC partials, by the wave that arrives last.
 // Called by a whole wave after its partial stores; `total` waves call it per
 // launch.  Agent-scope release before the ticket, agent-scope acquire after
 // the last one (the per-XCD L2s are not coherent); the partials are summed in
 // IC order per lane and then across the lanes in a fixed tree, so the value
 // does not depend on which wave arrives last.
-__device__ __forceinline__ void loss_arrive(const LossArgs &la, unsigned total, int B, int lane) {
+template <bool EX>
+__device__ __forceinline__ void loss_arrive(const LossArgs &la, const ConsArgs &ca, unsigned total, int B, int lane) {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   unsigned t = 0;
@@ -61,7 +85,24 @@ __device__ __forceinline__ void loss_arrive(const LossArgs &la, unsigned total, 
   double a = 0.0;
   for (int i = lane; i < B; i += 64) a += part[i];
   a = wave_sum(a);
-  if (lane == 0) la.loss[0] = (float)(a * la.scale);
+  if constexpr (!EX) {
+    if (lane == 0) la.loss[0] = (float)(a * la.scale);
+  } else {
+    // (total, state, energy, charge): the state value is the plain call's
+    double e = 0.0, q = 0.0;
+    if (ca.on) {
+      for (int i = lane; i < B; i += 64) e += ca.part[2 * i], q += ca.part[2 * i + 1];
+      e = wave_sum(e);
+      q = wave_sum(q);
+    }
+    if (lane == 0) {
+      const double ls = a * la.scale, le = e * ca.scale, lq = q * ca.scale;
+      la.loss[0] = ca.on ? (float)((ls + le) + lq) : (float)ls;
+      la.loss[1] = (float)ls;
+      la.loss[2] = (float)le;
+      la.loss[3] = (float)lq;
+    }
+  }
 }
 
 // w (pred - target)^2 of one value, the difference rounded to float32
@@ -74,11 +115,13 @@ __device__ __forceinline__ double sq_err(float pred, float tgt, float w) {
 // LDS: red[4] | c[nx] (double) | u, F, rho (float)
 inline size_t update_lds_bytes(int nx) { return 4 * sizeof(double) + (size_t)nx * (sizeof(double) + 3 * sizeof(float)); }
 
+template <bool EX>
 __global__ __launch_bounds__(kUnThreads) void unroll_update_kernel(const float *__restrict__ fe,
                                                                    const float *__restrict__ in,
                                                                    const float *__restrict__ x,
                                                                    const double *__restrict__ pc, int nx, float c,
-                                                                   float dt, float *out, float *nf, LossArgs la, int B) {
+                                                                   float dt, float *out, float *nf, LossArgs la, int B,
+                                                                   ConsArgs ca) {
   extern __shared__ double s_dyn[];
   double *red = s_dyn, *Lc = s_dyn + 4;
   float *Lu = reinterpret_cast<float *>(Lc + nx), *LF = Lu + nx, *Lrho = LF + nx;
@@ -101,21 +144,49 @@ __global__ __launch_bounds__(kUnThreads) void unroll_update_kernel(const float *
   }
   __syncthreads();
   const float *tg = la.tgt ? la.tgt + b * 3 * nx : nullptr;
-  double acc = 0.0;
+  const bool cons = EX && ca.on;
+  double acc = 0.0, su2 = 0.0, sE2 = 0.0, sn = 0.0;
   for (int i = threadIdx.x; i < nx; i += kUnThreads) {
     const float E_new = poisson_cell(Lrho, Lc, i, nx);
     so[2 * nx + i] = E_new;
     const float n_new = so[i], u_new = so[nx + i];  // this thread's own stores
     if (nf) *reinterpret_cast<un_f4 *>(nf + 4 * (b * nx + i)) = un_f4{n_new, u_new, E_new, x[i]};
     if (tg) acc += sq_err(n_new, tg[i], la.w0) + sq_err(u_new, tg[nx + i], la.w1) + sq_err(E_new, tg[2 * nx + i], la.w2);
+    if (cons) {
+      su2 += (double)u_new * (double)u_new;
+      sE2 += (double)E_new * (double)E_new;
+      sn += (double)n_new;
+    }
   }
   if (!tg) return;  // (uniform)
   acc = wave_sum(acc);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x >= 64) return;
-  if (threadIdx.x == 0) la.part[b] = ((red[0] + red[1]) + red[2]) + red[3];
-  loss_arrive(la, gridDim.x, B, threadIdx.x);
+  if constexpr (EX) {
+    __shared__ double redc[3][4];
+    if (cons) {  // (uniform)
+      su2 = wave_sum(su2);
+      sE2 = wave_sum(sE2);
+      sn = wave_sum(sn);
+      if ((threadIdx.x & 63) == 0) {
+        const int wv = threadIdx.x >> 6;
+        redc[0][wv] = su2, redc[1][wv] = sE2, redc[2][wv] = sn;
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x >= 64) return;
+    if (threadIdx.x == 0) {
+      la.part[b] = ((red[0] + red[1]) + red[2]) + red[3];
+      if (cons)
+        cons_finish(ca, b, nx, ((redc[0][0] + redc[0][1]) + redc[0][2]) + redc[0][3],
+                    ((redc[1][0] + redc[1][1]) + redc[1][2]) + redc[1][3],
+                    ((redc[2][0] + redc[2][1]) + redc[2][2]) + redc[2][3]);
+    }
+  } else {
+    __syncthreads();
+    if (threadIdx.x >= 64) return;
+    if (threadIdx.x == 0) la.part[b] = ((red[0] + red[1]) + red[2]) + red[3];
+  }
+  loss_arrive<EX>(la, ca, gridDim.x, B, threadIdx.x);
 }
 
 // ------------------------------------------------------------ forward, FFT sizes
@@ -146,10 +217,11 @@ __device__ __forceinline__ void update_ic(const float *__restrict__ st, const fl
 }
 
 // E' of one IC of the pair, the next node features and the IC's loss partial.
-template <int N, bool IMAG>
+template <int N, bool IMAG, bool EX>
 __device__ __forceinline__ void finish_ic(float *so, const double2 (&v)[N / 64], const float *__restrict__ x, float *nfb,
-                                          const float *tg, const LossArgs &la, int64_t ic, int lane) {
-  double acc = 0.0;
+                                          const float *tg, const LossArgs &la, const ConsArgs &ca, int64_t ic, int lane) {
+  const bool cons = EX && ca.on && tg;
+  double acc = 0.0, su2 = 0.0, sE2 = 0.0, sn = 0.0;
 #pragma unroll
   for (int i = 0; i < N / 64; ++i) {
     const int cell = lane + 64 * i;
@@ -158,17 +230,28 @@ __device__ __forceinline__ void finish_ic(float *so, const double2 (&v)[N / 64],
     const float n_new = so[cell], u_new = so[N + cell];  // this lane's own stores
     if (nfb) *reinterpret_cast<un_f4 *>(nfb + 4 * cell) = un_f4{n_new, u_new, E_new, x[cell]};
     if (tg) acc += sq_err(n_new, tg[cell], la.w0) + sq_err(u_new, tg[N + cell], la.w1) + sq_err(E_new, tg[2 * N + cell], la.w2);
+    if (cons) {
+      su2 += (double)u_new * (double)u_new;
+      sE2 += (double)E_new * (double)E_new;
+      sn += (double)n_new;
+    }
   }
   if (tg) {
     acc = wave_sum(acc);
     if (lane == 0) la.part[ic] = acc;
   }
+  if (cons) {
+    su2 = wave_sum(su2);
+    sE2 = wave_sum(sE2);
+    sn = wave_sum(sn);
+    if (lane == 0) cons_finish(ca, ic, N, su2, sE2, sn);
+  }
 }
 
-template <int N>
+template <int N, bool EX>
 __global__ __launch_bounds__(64 * kFftWaves, N >= 2048 ? 1 : 2) void unroll_update_fft_kernel(
     const float *__restrict__ fe, const float *__restrict__ in, const float *__restrict__ x,
-    const double *__restrict__ pc, float c, float dt, float *out, float *nf, LossArgs la, int B) {
+    const double *__restrict__ pc, float c, float dt, float *out, float *nf, LossArgs la, int B, ConsArgs ca) {
   constexpr int V = N / 64;
   __shared__ double2 s_fft[kFftWaves][fft_lds_elems<N>()];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -191,27 +274,35 @@ __global__ __launch_bounds__(64 * kFftWaves, N >= 2048 ? 1 : 2) void unroll_upda
     for (int i = 0; i < V; ++i) v[i] = make_double2(rho_a[lane + 64 * i], two ? r[i] : 0.0);
   }
   poisson_wave_tw<N>(v, s_fft[wave], reinterpret_cast<const double2 *>(pc + N), pc + 2 * N, lane);
-  finish_ic<N, false>(out + a * 3 * N, v, x, nf ? nf + a * 4 * N : nullptr, la.tgt ? la.tgt + a * 3 * N : nullptr, la, a,
-                      lane);
+  finish_ic<N, false, EX>(out + a * 3 * N, v, x, nf ? nf + a * 4 * N : nullptr, la.tgt ? la.tgt + a * 3 * N : nullptr,
+                          la, ca, a, lane);
   if (two)
-    finish_ic<N, true>(out + b * 3 * N, v, x, nf ? nf + b * 4 * N : nullptr, la.tgt ? la.tgt + b * 3 * N : nullptr, la,
-                       b, lane);
-  if (la.tgt) loss_arrive(la, (unsigned)((B + 1) / 2), B, lane);
+    finish_ic<N, true, EX>(out + b * 3 * N, v, x, nf ? nf + b * 4 * N : nullptr, la.tgt ? la.tgt + b * 3 * N : nullptr,
+                           la, ca, b, lane);
+  if (la.tgt) loss_arrive<EX>(la, ca, (unsigned)((B + 1) / 2), B, lane);
 }
 
 // --------------------------------------------------------------------- adjoint
 // The total gradient dL/d s^_{k+1} of one value (channel ch, cell i of IC b):
 // the previous adjoint call's direct part + the FluxGNN backward's
-// d node_features (both optional) + the loss seed gs_ch (s^ - s*).
+// d node_features (both optional) + the loss seed gs_ch (s^ - s*).  EX with
+// coef [B][2] = (ce, cq): the seed of u and of E gains ce_b u, ce_b E (one
+// float32 product, added to the seed before the other parts); cq_b is not
+// added, the charge term has no gradient through the conservative update.
 struct AdjIn {
   const float *sn, *tg;  // s^_{k+1}, s*_{k+1}  [B][3][nx]
   const float *din;      // direct part of step k+1 [B][3][nx] or NULL
   const float *gnf;      // d node_features of step k+1 [B*nx][4] or NULL
   float gs[3];           // 2 w_ch scale
+  const float *coef;     // [B][2] or NULL (read by the EX kernels only)
 };
+template <bool EX>
 __device__ __forceinline__ float total_g(const AdjIn &g, int64_t b, int ch, int i, int nx) {
   const int64_t o = b * 3 * nx + (int64_t)ch * nx + i;
   float v = g.gs[ch] * (g.sn[o] - g.tg[o]);
+  if constexpr (EX) {
+    if (g.coef && ch != 0) v = v + g.coef[2 * b] * g.sn[o];
+  }
   if (g.gnf) v += g.gnf[4 * (b * nx + i) + ch];
   if (g.din) v += g.din[o];
   return v;
@@ -220,6 +311,7 @@ __device__ __forceinline__ float total_g(const AdjIn &g, int64_t b, int ch, int 
 // LDS: c[nx] (double) | e, a~, b (float)
 inline size_t adjoint_lds_bytes(int nx) { return (size_t)nx * (sizeof(double) + 3 * sizeof(float)); }
 
+template <bool EX>
 __global__ __launch_bounds__(kUnThreads) void unroll_adjoint_kernel(const float *__restrict__ st, AdjIn g,
                                                                     const double *__restrict__ pc, int nx, float c,
                                                                     float dt, float *__restrict__ g_fe,
@@ -230,9 +322,9 @@ __global__ __launch_bounds__(kUnThreads) void unroll_adjoint_kernel(const float 
   const int64_t b = blockIdx.x;
   for (int i = threadIdx.x; i < nx; i += kUnThreads) {
     Lc[i] = pc[i];
-    La[i] = total_g(g, b, 0, i, nx);
-    Lb[i] = total_g(g, b, 1, i, nx);
-    Le[i] = total_g(g, b, 2, i, nx);
+    La[i] = total_g<EX>(g, b, 0, i, nx);
+    Lb[i] = total_g<EX>(g, b, 1, i, nx);
+    Le[i] = total_g<EX>(g, b, 2, i, nx);
   }
   __syncthreads();
   // a~ = a + P^T e = a - P e (only this thread reads La[i] before the barrier)
@@ -254,7 +346,7 @@ __global__ __launch_bounds__(kUnThreads) void unroll_adjoint_kernel(const float 
   }
 }
 
-template <int N, bool IMAG>
+template <int N, bool IMAG, bool EX>
 __device__ __forceinline__ void adjoint_ic(const float *__restrict__ st, const AdjIn &g, const double2 (&v)[N / 64],
                                            int64_t ic, float c, float dt, float *__restrict__ g_fe,
                                            float *__restrict__ dout, int lane) {
@@ -263,8 +355,8 @@ __device__ __forceinline__ void adjoint_ic(const float *__restrict__ st, const A
 #pragma unroll
   for (int i = 0; i < V; ++i) {
     const int cell = lane + 64 * i;
-    at[i] = total_g(g, ic, 0, cell, N) - (float)((IMAG ? v[i].y : v[i].x) / N);
-    bb[i] = total_g(g, ic, 1, cell, N);
+    at[i] = total_g<EX>(g, ic, 0, cell, N) - (float)((IMAG ? v[i].y : v[i].x) / N);
+    bb[i] = total_g<EX>(g, ic, 1, cell, N);
   }
   right_of<V>(at, atr);
   right_of<V>(bb, bbr);
@@ -283,7 +375,7 @@ __device__ __forceinline__ void adjoint_ic(const float *__restrict__ st, const A
   }
 }
 
-template <int N>
+template <int N, bool EX>
 __global__ __launch_bounds__(64 * kFftWaves, N >= 2048 ? 1 : 2) void unroll_adjoint_fft_kernel(
     const float *__restrict__ st, AdjIn g, const double *__restrict__ pc, float c, float dt, float *__restrict__ g_fe,
     float *__restrict__ dout, int B) {
@@ -297,27 +389,103 @@ __global__ __launch_bounds__(64 * kFftWaves, N >= 2048 ? 1 : 2) void unroll_adjo
 #pragma unroll
   for (int i = 0; i < V; ++i) {
     const int cell = lane + 64 * i;
-    v[i] = make_double2((double)total_g(g, a, 2, cell, N), two ? (double)total_g(g, b, 2, cell, N) : 0.0);
+    v[i] = make_double2((double)total_g<EX>(g, a, 2, cell, N), two ? (double)total_g<EX>(g, b, 2, cell, N) : 0.0);
   }
   poisson_wave_tw<N>(v, s_fft[wave], reinterpret_cast<const double2 *>(pc + N), pc + 2 * N, lane);  // N P e
-  adjoint_ic<N, false>(st, g, v, a, c, dt, g_fe, dout, lane);
-  if (two) adjoint_ic<N, true>(st, g, v, b, c, dt, g_fe, dout, lane);
+  adjoint_ic<N, false, EX>(st, g, v, a, c, dt, g_fe, dout, lane);
+  if (two) adjoint_ic<N, true, EX>(st, g, v, b, c, dt, g_fe, dout, lane);
 }
 
+// ex: the _ex entry points' instantiation (the wider loss row, the conservation terms, the coefficients)
 template <int N>
 hipError_t update_fft_launch(const float *fe, const float *st, const float *x, const double *pc, int B, float c, float dt,
-                             float *out, float *nf, const LossArgs &la, hipStream_t s) {
+                             float *out, float *nf, const LossArgs &la, const ConsArgs &ca, bool ex, hipStream_t s) {
   const unsigned grid = (unsigned)((B + 2 * kFftWaves - 1) / (2 * kFftWaves));
-  hipLaunchKernelGGL((unroll_update_fft_kernel<N>), dim3(grid), dim3(64 * kFftWaves), 0, s, fe, st, x, pc, c, dt, out, nf,
-                     la, B);
+  if (ex)
+    hipLaunchKernelGGL((unroll_update_fft_kernel<N, true>), dim3(grid), dim3(64 * kFftWaves), 0, s, fe, st, x, pc, c, dt,
+                       out, nf, la, B, ca);
+  else
+    hipLaunchKernelGGL((unroll_update_fft_kernel<N, false>), dim3(grid), dim3(64 * kFftWaves), 0, s, fe, st, x, pc, c, dt,
+                       out, nf, la, B, ca);
   return hipGetLastError();
 }
 template <int N>
 hipError_t adjoint_fft_launch(const float *st, const AdjIn &g, const double *pc, int B, float c, float dt, float *g_fe,
-                              float *dout, hipStream_t s) {
+                              float *dout, bool ex, hipStream_t s) {
   const unsigned grid = (unsigned)((B + 2 * kFftWaves - 1) / (2 * kFftWaves));
-  hipLaunchKernelGGL((unroll_adjoint_fft_kernel<N>), dim3(grid), dim3(64 * kFftWaves), 0, s, st, g, pc, c, dt, g_fe, dout,
-                     B);
+  if (ex)
+    hipLaunchKernelGGL((unroll_adjoint_fft_kernel<N, true>), dim3(grid), dim3(64 * kFftWaves), 0, s, st, g, pc, c, dt,
+                       g_fe, dout, B);
+  else
+    hipLaunchKernelGGL((unroll_adjoint_fft_kernel<N, false>), dim3(grid), dim3(64 * kFftWaves), 0, s, st, g, pc, c, dt,
+                       g_fe, dout, B);
+  return hipGetLastError();
+}
+
+hipError_t update_any(bool ex, const float *fe, const float *st, const float *x, const double *pc, int B, int nx, float c, float dt,
+                      float *st_next, float *nf_next, const float *target, const float *w, float scale, float *loss,
+                      void *ws, const ConsTerms *cons, hipStream_t s) {
+  if (B <= 0) return hipSuccess;
+  if (!unroll_nx_ok(nx)) return hipErrorInvalidValue;
+  LossArgs la{};
+  ConsArgs ca{};
+  if (target) {
+    la.tgt = target;
+    la.w0 = w[0], la.w1 = w[1], la.w2 = w[2];
+    la.scale = (double)scale;
+    la.cnt = static_cast<unsigned *>(ws);
+    la.part = reinterpret_cast<double *>(static_cast<char *>(ws) + kUnCounterBytes);
+    la.loss = loss;
+    if (ex && cons) {
+      ca.on = true;
+      ca.lam_e = (double)cons->lam_e, ca.lam_q = (double)cons->lam_q, ca.scale = (double)cons->scale;
+      ca.ref = cons->ref, ca.coef = cons->coef;
+      ca.part = reinterpret_cast<double *>(static_cast<char *>(ws) + unroll_ws_bytes(B, nx));
+    }
+    // the arrival counter starts every launch at 0 (a memset node, not a kernel)
+    if (hipError_t e = hipMemsetAsync(ws, 0, 16, s)) return e;
+  }
+  switch (poisson_uses_fft(nx) ? nx : 0) {
+    case 256: return update_fft_launch<256>(fe, st, x, pc, B, c, dt, st_next, nf_next, la, ca, ex, s);
+    case 512: return update_fft_launch<512>(fe, st, x, pc, B, c, dt, st_next, nf_next, la, ca, ex, s);
+    case 1024: return update_fft_launch<1024>(fe, st, x, pc, B, c, dt, st_next, nf_next, la, ca, ex, s);
+    case 2048: return update_fft_launch<2048>(fe, st, x, pc, B, c, dt, st_next, nf_next, la, ca, ex, s);
+    default: break;
+  }
+  if (ex)
+    hipLaunchKernelGGL(unroll_update_kernel<true>, dim3((unsigned)B), dim3(kUnThreads), update_lds_bytes(nx), s, fe, st, x,
+                       pc, nx, c, dt, st_next, nf_next, la, B, ca);
+  else
+    hipLaunchKernelGGL(unroll_update_kernel<false>, dim3((unsigned)B), dim3(kUnThreads), update_lds_bytes(nx), s, fe, st, x,
+                       pc, nx, c, dt, st_next, nf_next, la, B, ca);
+  return hipGetLastError();
+}
+
+hipError_t adjoint_any(bool ex, const float *st, const float *st_next, const float *target, const float *w, float scale,
+                       const float *direct_next, const float *gnf_next, const double *pc, int B, int nx, float c,
+                       float dt, float *g_fe, float *direct, const float *coef, hipStream_t s) {
+  if (B <= 0) return hipSuccess;
+  if (!unroll_nx_ok(nx)) return hipErrorInvalidValue;
+  AdjIn g{};
+  g.sn = st_next;
+  g.tg = target;
+  g.din = direct_next;
+  g.gnf = gnf_next;
+  g.coef = coef;
+  for (int k = 0; k < 3; ++k) g.gs[k] = (float)(2.0 * (double)w[k] * (double)scale);
+  switch (poisson_uses_fft(nx) ? nx : 0) {
+    case 256: return adjoint_fft_launch<256>(st, g, pc, B, c, dt, g_fe, direct, ex, s);
+    case 512: return adjoint_fft_launch<512>(st, g, pc, B, c, dt, g_fe, direct, ex, s);
+    case 1024: return adjoint_fft_launch<1024>(st, g, pc, B, c, dt, g_fe, direct, ex, s);
+    case 2048: return adjoint_fft_launch<2048>(st, g, pc, B, c, dt, g_fe, direct, ex, s);
+    default: break;
+  }
+  if (ex)
+    hipLaunchKernelGGL(unroll_adjoint_kernel<true>, dim3((unsigned)B), dim3(kUnThreads), adjoint_lds_bytes(nx), s, st, g,
+                       pc, nx, c, dt, g_fe, direct);
+  else
+    hipLaunchKernelGGL(unroll_adjoint_kernel<false>, dim3((unsigned)B), dim3(kUnThreads), adjoint_lds_bytes(nx), s, st, g,
+                       pc, nx, c, dt, g_fe, direct);
   return hipGetLastError();
 }
 
@@ -329,56 +497,30 @@ int64_t unroll_ws_bytes(int B, int nx) {
   (void)nx;
   return (int64_t)(kUnCounterBytes + al256(sizeof(double) * (size_t)B));
 }
+int64_t unroll_ws_bytes_ex(int B, int nx) { return unroll_ws_bytes(B, nx) + (int64_t)al256(2 * sizeof(double) * (size_t)B); }
 
 hipError_t launch_unroll_update(const float *fe, const float *st, const float *x, const double *pc, int B, int nx,
                                 float c, float dt, float *st_next, float *nf_next, const float *target, const float *w,
                                 float scale, float *loss, void *ws, hipStream_t s) {
-  if (B <= 0) return hipSuccess;
-  if (!unroll_nx_ok(nx)) return hipErrorInvalidValue;
-  LossArgs la{};
-  if (target) {
-    la.tgt = target;
-    la.w0 = w[0], la.w1 = w[1], la.w2 = w[2];
-    la.scale = (double)scale;
-    la.cnt = static_cast<unsigned *>(ws);
-    la.part = reinterpret_cast<double *>(static_cast<char *>(ws) + kUnCounterBytes);
-    la.loss = loss;
-    // the arrival counter starts every launch at 0 (a memset node, not a kernel)
-    if (hipError_t e = hipMemsetAsync(ws, 0, 16, s)) return e;
-  }
-  switch (poisson_uses_fft(nx) ? nx : 0) {
-    case 256: return update_fft_launch<256>(fe, st, x, pc, B, c, dt, st_next, nf_next, la, s);
-    case 512: return update_fft_launch<512>(fe, st, x, pc, B, c, dt, st_next, nf_next, la, s);
-    case 1024: return update_fft_launch<1024>(fe, st, x, pc, B, c, dt, st_next, nf_next, la, s);
-    case 2048: return update_fft_launch<2048>(fe, st, x, pc, B, c, dt, st_next, nf_next, la, s);
-    default: break;
-  }
-  hipLaunchKernelGGL(unroll_update_kernel, dim3((unsigned)B), dim3(kUnThreads), update_lds_bytes(nx), s, fe, st, x, pc,
-                     nx, c, dt, st_next, nf_next, la, B);
-  return hipGetLastError();
+  return update_any(false, fe, st, x, pc, B, nx, c, dt, st_next, nf_next, target, w, scale, loss, ws, nullptr, s);
+}
+hipError_t launch_unroll_update_ex(const float *fe, const float *st, const float *x, const double *pc, int B, int nx,
+                                   float c, float dt, float *st_next, float *nf_next, const float *target, const float *w,
+                                   float scale, float *losses, void *ws, const ConsTerms *cons, hipStream_t s) {
+  return update_any(true, fe, st, x, pc, B, nx, c, dt, st_next, nf_next, target, w, scale, losses, ws, cons, s);
 }
 
 hipError_t launch_unroll_adjoint(const float *st, const float *st_next, const float *target, const float *w, float scale,
                                  const float *direct_next, const float *gnf_next, const double *pc, int B, int nx,
                                  float c, float dt, float *g_fe, float *direct, hipStream_t s) {
-  if (B <= 0) return hipSuccess;
-  if (!unroll_nx_ok(nx)) return hipErrorInvalidValue;
-  AdjIn g{};
-  g.sn = st_next;
-  g.tg = target;
-  g.din = direct_next;
-  g.gnf = gnf_next;
-  for (int k = 0; k < 3; ++k) g.gs[k] = (float)(2.0 * (double)w[k] * (double)scale);
-  switch (poisson_uses_fft(nx) ? nx : 0) {
-    case 256: return adjoint_fft_launch<256>(st, g, pc, B, c, dt, g_fe, direct, s);
-    case 512: return adjoint_fft_launch<512>(st, g, pc, B, c, dt, g_fe, direct, s);
-    case 1024: return adjoint_fft_launch<1024>(st, g, pc, B, c, dt, g_fe, direct, s);
-    case 2048: return adjoint_fft_launch<2048>(st, g, pc, B, c, dt, g_fe, direct, s);
-    default: break;
-  }
-  hipLaunchKernelGGL(unroll_adjoint_kernel, dim3((unsigned)B), dim3(kUnThreads), adjoint_lds_bytes(nx), s, st, g, pc, nx,
-                     c, dt, g_fe, direct);
-  return hipGetLastError();
+  return adjoint_any(false, st, st_next, target, w, scale, direct_next, gnf_next, pc, B, nx, c, dt, g_fe, direct, nullptr,
+                            s);
+}
+hipError_t launch_unroll_adjoint_ex(const float *st, const float *st_next, const float *target, const float *w,
+                                    float scale, const float *direct_next, const float *gnf_next, const double *pc, int B,
+                                    int nx, float c, float dt, float *g_fe, float *direct, const float *coef,
+                                    hipStream_t s) {
+  return adjoint_any(true, st, st_next, target, w, scale, direct_next, gnf_next, pc, B, nx, c, dt, g_fe, direct, coef, s);
 }
 
 }  // namespace hf

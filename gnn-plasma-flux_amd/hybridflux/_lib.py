@@ -156,6 +156,26 @@ SIGNATURES = {
                                       c_void_p, c_float, c_void_p, c_void_p, c_int64, c_void_p]),
     "hf_pure_unroll_adjoint": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_int,
                                        c_void_p, c_void_p]),
+    "hf_state_moments": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "hf_unroll_workspace_bytes_ex": (c_int64, [c_int, c_int]),
+    "hf_unroll_update_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int64,
+                                    c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
+    "hf_unroll_adjoint_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p,
+                                     c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "hf_pure_unroll_workspace_bytes_ex": (c_int64, [c_int, c_int]),
+    "hf_pure_unroll_update_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_float, c_void_p, c_void_p, c_int64, c_void_p, c_float, c_void_p,
+                                         c_void_p, c_void_p]),
+    "hf_pure_unroll_adjoint_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_int,
+                                          c_void_p, c_void_p, c_void_p]),
+    "hf_pinn_unroll_workspace_bytes_ex": (c_int64, [c_int, c_int]),
+    "hf_pinn_unroll_loss_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_void_p,
+                                       c_float, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_int64,
+                                       c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
+    "hf_pinn_unroll_adjoint_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                          c_float, c_void_p, c_float, c_double, c_double, c_double, c_void_p, c_void_p,
+                                          c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -887,19 +887,92 @@ def _weights3(weights):
     return w
 
 
+def state_moments(states):
+    """hf_state_moments: (e, q) = (0.5 (sum u^2 + sum E^2) / nx, sum n / nx) of
+    every state of `states` [..., 3, nx] (contiguous float32 on the device), in
+    float64 [..., 2]: HF_NUM_METRICS [0] and [1] without the rounding to float32."""
+    require_device(states, "states")
+    if states.dim() < 3 or states.shape[-2] != 3 or states.shape[-1] < 1 or states.dtype != torch.float32 \
+            or not states.is_contiguous():
+        raise ValueError(f"states must be contiguous float32 [...,3,nx], got {tuple(states.shape)} {states.dtype}")
+    rows, nx = states.numel() // (3 * states.shape[-1]), states.shape[-1]
+    if rows < 1:
+        raise ValueError("state moments: need at least one state")
+    out = torch.empty(*states.shape[:-2], 2, dtype=torch.float64, device=states.device)
+    with torch.cuda.device(states.device):
+        check(lib().hf_state_moments(ptr(states), rows, nx, ptr(out), stream_of(states.device)))
+    return out
+
+
+def _cons_terms(what, cons, cons_scale, cons_ref, cons_coef, B, dev, target):
+    """The conservation arguments of an _ex update: (lam [2] host float32,
+    cons_scale, ref [B,2] float64, coef [B,2] float32 (allocated when None))."""
+    lam = np.ascontiguousarray(np.asarray(cons, dtype=np.float32).reshape(-1))
+    if lam.size != 2 or not (lam >= 0).all():
+        raise ValueError(f"{what}: cons must be (lam_e, lam_q), both >= 0")
+    if target is None:
+        raise ValueError(f"{what}: cons needs a target")
+    if cons_ref is None or cons_ref.dtype != torch.float64 or tuple(cons_ref.shape) != (B, 2) or cons_ref.device != dev \
+            or not cons_ref.is_contiguous():
+        raise ValueError(f"{what}: cons_ref must be contiguous float64 [{B},2] on {dev}")
+    cons_coef = torch.empty(B, 2, device=dev) if cons_coef is None else cons_coef
+    _cons_coef(what, cons_coef, B, dev)
+    return lam, float(cons_scale), cons_ref, cons_coef
+
+
+def _cons_coef(what, coef, B, dev):
+    if coef.dtype != torch.float32 or tuple(coef.shape) != (B, 2) or coef.device != dev or not coef.is_contiguous():
+        raise ValueError(f"{what}: cons_coef must be contiguous float32 [{B},2] on {dev}")
+    return coef
+
+
+def _loss_row(what, loss, n, dev):
+    loss = torch.empty(n, device=dev) if loss is None else loss
+    if loss.dtype != torch.float32 or loss.numel() != n or loss.device != dev or not loss.is_contiguous():
+        raise ValueError(f"{what}: loss must be {n} contiguous float32 element(s) on the state's device")
+    return loss
+
+
+def _ws_ex(query, B, nx, dev, what):
+    nb = int(query(B, nx))
+    if nb < 0:
+        raise ValueError(f"{what}: need B >= 1, nx >= 1 (B = {B}, nx = {nx})")
+    return torch.empty(nb, dtype=torch.uint8, device=dev)
+
+
+def unroll_workspace_ex(B, nx, dev):
+    """hf_unroll_workspace_bytes_ex of scratch for unroll_update with cons on `dev` (a uint8 tensor)."""
+    return _ws_ex(lib().hf_unroll_workspace_bytes_ex, B, nx, dev, "unroll workspace")
+
+
+def pure_unroll_workspace_ex(B, nx, dev):
+    """hf_pure_unroll_workspace_bytes_ex of scratch for pure_unroll_update with cons on `dev` (a uint8 tensor)."""
+    return _ws_ex(lib().hf_pure_unroll_workspace_bytes_ex, B, nx, dev, "pure unroll workspace")
+
+
+def pinn_unroll_workspace_ex(B, nx, dev):
+    """hf_pinn_unroll_workspace_bytes_ex of scratch for pinn_unroll_loss with cons on `dev` (a uint8 tensor)."""
+    return _ws_ex(lib().hf_pinn_unroll_workspace_bytes_ex, B, nx, dev, "pinn unroll workspace")
+
+
 def unroll_update(grid, flux_edge, state, x=None, target=None, weights=(1.0, 1.0, 1.0), scale=0.0, want_nf=True,
-                  out=None, loss=None, ws=None):
+                  out=None, loss=None, ws=None, cons=None, cons_scale=0.0, cons_ref=None, cons_coef=None, ex=False):
     """hf_unroll_update: one hybrid step of `state` [B,3,nx] from FluxGNN's edge
     fluxes flux_edge [B*2nx] (src/hybrid_solver.py:45-63).  Returns (state_next
     [B,3,nx], node_features_next [B*nx,4] or None, loss [1] or None): the next
     step's FluxGNN input, and with `target` [B,3,nx] the term scale * sum w_ch
     (state_next - target)^2.  x: the positions [nx] of the node features
     (default the grid's).  out / loss / ws: preallocated state_next, loss
-    element and workspace (unroll_workspace)."""
+    element and workspace (unroll_workspace).  cons = (lam_e, lam_q) (or
+    ex=True): hf_unroll_update_ex -- loss is the row [4] = (total, state, energy,
+    charge) of the step with the energy and charge terms against cons_ref [B,2]
+    float64 at cons_scale, the workspace unroll_workspace_ex's, and cons_coef
+    [B,2] receives (ce, cq) for unroll_adjoint."""
     require_device(state, "state")
     B, _, nx = state.shape
     dev = state.device
     st = _unroll_state(state, B, nx, dev, "state")
+    ex = ex or cons is not None
     fe = flux_edge.detach()
     if fe.dtype != torch.float32 or fe.numel() != B * 2 * nx or fe.device != dev or not fe.is_contiguous() \
             or nx != grid.nx:
@@ -915,12 +988,28 @@ def unroll_update(grid, flux_edge, state, x=None, target=None, weights=(1.0, 1.0
     if target is not None:
         target = _unroll_state(target, B, nx, dev, "target")
         w = _weights3(weights)
-        loss = torch.empty(1, device=dev) if loss is None else loss
-        if loss.dtype != torch.float32 or loss.numel() != 1 or loss.device != dev:
-            raise ValueError("unroll update: loss must be one float32 element on the state's device")
+        if ex:
+            loss = _loss_row("unroll update", loss, 4, dev)
+        else:
+            loss = torch.empty(1, device=dev) if loss is None else loss
+            if loss.dtype != torch.float32 or loss.numel() != 1 or loss.device != dev:
+                raise ValueError("unroll update: loss must be one float32 element on the state's device")
     else:
         loss = None
+    if cons is not None:
+        lam, cons_scale, cons_ref, cons_coef = _cons_terms("unroll update", cons, cons_scale, cons_ref, cons_coef, B,
+                                                           dev, target)
+        ws = unroll_workspace_ex(B, nx, dev) if ws is None else ws
+    else:
+        lam = cons_ref = cons_coef = None
     ws = unroll_workspace(B, nx, dev) if ws is None else ws
+    if ex:
+        with torch.cuda.device(dev):
+            check(lib().hf_unroll_update_ex(ptr(fe), ptr(st), ptr(x), ptr(pc), grid.pmode, B, nx, grid.c32, grid.dt32,
+                                            ptr(out), ptr(nf), ptr(target), ptr(w), float(scale), ptr(loss), ptr(ws),
+                                            ws.numel() * ws.element_size(), ptr(lam), float(cons_scale), ptr(cons_ref),
+                                            ptr(cons_coef), stream_of(dev)))
+        return out, nf, loss
     with torch.cuda.device(dev):
         check(lib().hf_unroll_update(ptr(fe), ptr(st), ptr(x), ptr(pc), grid.pmode, B, nx, grid.c32, grid.dt32, ptr(out),
                                      ptr(nf), ptr(target), ptr(w), float(scale), ptr(loss), ptr(ws),
@@ -928,13 +1017,15 @@ def unroll_update(grid, flux_edge, state, x=None, target=None, weights=(1.0, 1.0
     return out, nf, loss
 
 
-def unroll_adjoint(grid, state, state_next, target, weights, scale, direct_next=None, gnf_next=None, want_direct=True):
+def unroll_adjoint(grid, state, state_next, target, weights, scale, direct_next=None, gnf_next=None, want_direct=True,
+                   cons_coef=None, ex=False):
     """hf_unroll_adjoint: the adjoint of unroll_update's step.  state (s_k),
     state_next (the predicted s_{k+1}) and target (s*_{k+1}) [B,3,nx];
     direct_next [B,3,nx] / gnf_next [B*nx,4]: the direct part this call returned
     for step k+1 and FluxGNN's d node_features of step k+1 (None at the last
     step, or to cut the state gradient).  Returns (d loss / d flux_edge [B,2nx],
-    direct part [B,3,nx] or None)."""
+    direct part [B,3,nx] or None).  cons_coef [B,2] (or ex=True):
+    hf_unroll_adjoint_ex, the seed with the energy term's ce u, ce E."""
     require_device(state, "state")
     B, _, nx = state.shape
     dev = state.device
@@ -952,6 +1043,14 @@ def unroll_adjoint(grid, state, state_next, target, weights, scale, direct_next=
     pc = grid.spectral_plan(dev)
     g_fe = torch.empty(B, 2 * nx, device=dev)
     direct = torch.empty(B, 3, nx, device=dev) if want_direct else None
+    if ex or cons_coef is not None:
+        if cons_coef is not None:
+            _cons_coef("unroll adjoint", cons_coef, B, dev)
+        with torch.cuda.device(dev):
+            check(lib().hf_unroll_adjoint_ex(ptr(st), ptr(sn), ptr(tg), ptr(w), float(scale), ptr(direct_next),
+                                             ptr(gnf_next), ptr(pc), grid.pmode, B, nx, grid.c32, grid.dt32, ptr(g_fe),
+                                             ptr(direct), ptr(cons_coef), stream_of(dev)))
+        return g_fe, direct
     with torch.cuda.device(dev):
         check(lib().hf_unroll_adjoint(ptr(st), ptr(sn), ptr(tg), ptr(w), float(scale), ptr(direct_next), ptr(gnf_next),
                                       ptr(pc), grid.pmode, B, nx, grid.c32, grid.dt32, ptr(g_fe), ptr(direct),
@@ -977,15 +1076,18 @@ def _unroll_cells(t, B, nx, width, dev, what):
 
 
 def pure_unroll_update(delta, state, x, target=None, weights=(1.0, 1.0, 1.0), scale=0.0, want_nf=True, out=None,
-                       loss=None, ws=None):
+                       loss=None, ws=None, cons=None, cons_scale=0.0, cons_ref=None, cons_coef=None, ex=False):
     """hf_pure_unroll_update: one step of PureGNN's rollout, state_next = state
     + delta^T for `state` [B,3,nx] and PureGNN's delta [B*nx,3]
     (evaluate_multi_ic.py:53-64).  Returns (state_next [B,3,nx],
     node_features_next [B*nx,4] = [n', u', E', x] or None, loss [1] or None):
     the next step's PureGNN input, and with `target` [B,3,nx] the term scale *
     sum w_ch (state_next - target)^2.  x: the positions [nx].  out / loss / ws:
-    preallocated state_next, loss element and workspace (pure_unroll_workspace)."""
+    preallocated state_next, loss element and workspace (pure_unroll_workspace).
+    cons = (lam_e, lam_q) (or ex=True): hf_pure_unroll_update_ex, as
+    unroll_update's (loss row [4], pure_unroll_workspace_ex, cons_ref, cons_coef)."""
     require_device(state, "state")
+    ex = ex or cons is not None
     if state.dim() != 3:
         raise ValueError(f"state must be [B,3,nx], got {tuple(state.shape)}")
     B, _, nx = state.shape
@@ -1001,27 +1103,45 @@ def pure_unroll_update(delta, state, x, target=None, weights=(1.0, 1.0, 1.0), sc
     if target is not None:
         target = _unroll_state(target, B, nx, dev, "target")
         w = _weights3(weights)
-        loss = torch.empty(1, device=dev) if loss is None else loss
-        if loss.dtype != torch.float32 or loss.numel() != 1 or loss.device != dev:
-            raise ValueError("pure unroll update: loss must be one float32 element on the state's device")
-        ws = pure_unroll_workspace(B, nx, dev) if ws is None else ws
+        if ex:
+            loss = _loss_row("pure unroll update", loss, 4, dev)
+        else:
+            loss = torch.empty(1, device=dev) if loss is None else loss
+            if loss.dtype != torch.float32 or loss.numel() != 1 or loss.device != dev:
+                raise ValueError("pure unroll update: loss must be one float32 element on the state's device")
+        if ws is None:
+            ws = pure_unroll_workspace_ex(B, nx, dev) if cons is not None else pure_unroll_workspace(B, nx, dev)
         if ws.device != dev or not ws.is_contiguous():
             raise ValueError(f"pure unroll update: the workspace must be contiguous on {dev}")
         nb = ws.numel() * ws.element_size()
     else:
         loss = ws = None
+    if cons is not None:
+        lam, cons_scale, cons_ref, cons_coef = _cons_terms("pure unroll update", cons, cons_scale, cons_ref, cons_coef,
+                                                           B, dev, target)
+    else:
+        lam = cons_ref = cons_coef = None
+    if ex:
+        with torch.cuda.device(dev):
+            check(lib().hf_pure_unroll_update_ex(ptr(d), ptr(st), ptr(x), B, nx, ptr(out), ptr(nf), ptr(target), ptr(w),
+                                                 float(scale), ptr(loss), ptr(ws), nb, ptr(lam), float(cons_scale),
+                                                 ptr(cons_ref), ptr(cons_coef), stream_of(dev)))
+        return out, nf, loss
     with torch.cuda.device(dev):
         check(lib().hf_pure_unroll_update(ptr(d), ptr(st), ptr(x), B, nx, ptr(out), ptr(nf), ptr(target), ptr(w),
                                           float(scale), ptr(loss), ptr(ws), nb, stream_of(dev)))
     return out, nf, loss
 
 
-def pure_unroll_adjoint(state_next, target, weights, scale, grad_delta_next=None, gnf_next=None):
+def pure_unroll_adjoint(state_next, target, weights, scale, grad_delta_next=None, gnf_next=None, cons_coef=None,
+                        ex=False):
     """hf_pure_unroll_adjoint: the adjoint of pure_unroll_update's step.
     state_next (the predicted s_{k+1}) and target (s*_{k+1}) [B,3,nx];
     grad_delta_next [B*nx,3] / gnf_next [B*nx,4]: what this call returned for
     step k+1 and PureGNN's d node_features of step k+1 (None at the last step,
-    or to cut the state gradient).  Returns d loss / d delta [B*nx,3]."""
+    or to cut the state gradient).  Returns d loss / d delta [B*nx,3].
+    cons_coef [B,2] (or ex=True): hf_pure_unroll_adjoint_ex, the seed with the
+    terms' (cq, ce u, ce E)."""
     require_device(state_next, "state_next")
     if state_next.dim() != 3:
         raise ValueError(f"state_next must be [B,3,nx], got {tuple(state_next.shape)}")
@@ -1035,6 +1155,13 @@ def pure_unroll_adjoint(state_next, target, weights, scale, grad_delta_next=None
         gnf_next = _unroll_cells(gnf_next, B, nx, 4, dev, "gnf_next")
     w = _weights3(weights)
     gd = torch.empty(B * nx, 3, device=dev)
+    if ex or cons_coef is not None:
+        if cons_coef is not None:
+            _cons_coef("pure unroll adjoint", cons_coef, B, dev)
+        with torch.cuda.device(dev):
+            check(lib().hf_pure_unroll_adjoint_ex(ptr(sn), ptr(tg), ptr(w), float(scale), ptr(grad_delta_next),
+                                                  ptr(gnf_next), B, nx, ptr(gd), ptr(cons_coef), stream_of(dev)))
+        return gd
     with torch.cuda.device(dev):
         check(lib().hf_pure_unroll_adjoint(ptr(sn), ptr(tg), ptr(w), float(scale), ptr(grad_delta_next),
                                            ptr(gnf_next), B, nx, ptr(gd), stream_of(dev)))
@@ -1074,16 +1201,38 @@ def _pinn_unroll_args(what, pred, target, weights, state, phys, phys_scale, dx, 
 
 
 def pinn_unroll_loss(pred, target, weights, scale, state=None, phys=None, phys_scale=0.0, dx=None, dt=None, nu=None,
-                     length=None, losses=None, ws=None):
+                     length=None, losses=None, ws=None, cons=None, cons_scale=0.0, cons_ref=None, cons_coef=None,
+                     ex=False):
     """hf_pinn_unroll_loss: one step's term of PINN's K-step loss, losses [5] =
     (total, data, cont, mom, pois) with data = scale sum w_ch (pred - target)^2
     and, with phys = (l_c, l_m, l_p), phys_scale l sum r^2 of hf_pinn_loss's
     residuals at p = pred, (n, u, E) = state; all states contiguous float32
     [B,3,nx] on pred's device.  phys None: entries 2..4 are 0 and state is not
     read.  length: the domain length of the Poisson operator (default nx dx).
-    losses / ws: a preallocated float32 [5] and workspace (pinn_unroll_workspace)."""
+    losses / ws: a preallocated float32 [5] and workspace (pinn_unroll_workspace).
+    cons = (lam_e, lam_q) (or ex=True): hf_pinn_unroll_loss_ex -- losses [7] =
+    (..., energy, charge) with the energy and charge terms against cons_ref [B,2]
+    float64 at cons_scale, the workspace pinn_unroll_workspace_ex's, and cons_coef
+    [B,2] receives (ce, cq) for pinn_unroll_adjoint."""
     p, tg, st, B, nx, dev, w, lam, phys_scale, dt, dx, nu, pc = _pinn_unroll_args(
         "pinn_unroll_loss", pred, target, weights, state, phys, phys_scale, dx, dt, nu, length)
+    if ex or cons is not None:
+        losses = _loss_row("pinn_unroll_loss", losses, 7, dev)
+        if cons is not None:
+            clam, cons_scale, cons_ref, cons_coef = _cons_terms("pinn_unroll_loss", cons, cons_scale, cons_ref,
+                                                                cons_coef, B, dev, tg)
+            ws = pinn_unroll_workspace_ex(B, nx, dev) if ws is None else ws
+        else:
+            clam = cons_ref = cons_coef = None
+            ws = pinn_unroll_workspace(B, nx, dev) if ws is None else ws
+        if ws.device != dev or not ws.is_contiguous():
+            raise ValueError(f"pinn_unroll_loss: the workspace must be contiguous on {dev}")
+        with torch.cuda.device(dev):
+            check(lib().hf_pinn_unroll_loss_ex(ptr(p), ptr(st), ptr(tg), B, nx, ptr(w), float(scale), ptr(lam),
+                                               phys_scale, dt, dx, nu, ptr(pc), ptr(losses), ptr(ws),
+                                               ws.numel() * ws.element_size(), ptr(clam), float(cons_scale),
+                                               ptr(cons_ref), ptr(cons_coef), stream_of(dev)))
+        return losses
     losses = torch.empty(5, device=dev) if losses is None else losses
     if losses.dtype != torch.float32 or losses.numel() != 5 or losses.device != dev or not losses.is_contiguous():
         raise ValueError("pinn_unroll_loss: losses must be five contiguous float32 elements on pred's device")
@@ -1098,12 +1247,14 @@ def pinn_unroll_loss(pred, target, weights, scale, state=None, phys=None, phys_s
 
 
 def pinn_unroll_adjoint(pred, target, weights, scale, state=None, phys=None, phys_scale=0.0, dx=None, dt=None, nu=None,
-                        length=None, pred_next=None, grad_state_next=None):
+                        length=None, pred_next=None, grad_state_next=None, cons_coef=None, ex=False):
     """hf_pinn_unroll_adjoint: step k's incoming gradient [B,3,nx] for
     pinn_backward = d term_k / d pred (pinn_unroll_loss's arguments), + with
     phys and pred_next (s^_{k+1}) d term_{k+1} / d (state slot), +
     grad_state_next (pinn_backward's d state of step k+1); pred_next and
-    grad_state_next None at the last step, or to cut the state gradient."""
+    grad_state_next None at the last step, or to cut the state gradient.
+    cons_coef [B,2] (or ex=True): hf_pinn_unroll_adjoint_ex, d term_k / d pred
+    with the terms' (cq, ce p_u, ce p_E)."""
     p, tg, st, B, nx, dev, w, lam, phys_scale, dt, dx, nu, pc = _pinn_unroll_args(
         "pinn_unroll_adjoint", pred, target, weights, state, phys, phys_scale, dx, dt, nu, length)
     if pred_next is not None:
@@ -1111,6 +1262,14 @@ def pinn_unroll_adjoint(pred, target, weights, scale, state=None, phys=None, phy
     if grad_state_next is not None:
         grad_state_next = _unroll_state(grad_state_next, B, nx, dev, "grad_state_next")
     g = torch.empty(B, 3, nx, device=dev)
+    if ex or cons_coef is not None:
+        if cons_coef is not None:
+            _cons_coef("pinn_unroll_adjoint", cons_coef, B, dev)
+        with torch.cuda.device(dev):
+            check(lib().hf_pinn_unroll_adjoint_ex(ptr(p), ptr(st), ptr(tg), ptr(pred_next), ptr(grad_state_next), B, nx,
+                                                  ptr(w), float(scale), ptr(lam), phys_scale, dt, dx, nu, ptr(pc),
+                                                  ptr(g), ptr(cons_coef), stream_of(dev)))
+        return g
     with torch.cuda.device(dev):
         check(lib().hf_pinn_unroll_adjoint(ptr(p), ptr(st), ptr(tg), ptr(pred_next), ptr(grad_state_next), B, nx, ptr(w),
                                            float(scale), ptr(lam), phys_scale, dt, dx, nu, ptr(pc), ptr(g),

@@ -42,6 +42,12 @@ steps of its own rollout, as the two graph models and on their driver:
 pinn_unrolled_loss / pinn_unrolled_step / train_pinn_unrolled (pinn_unroll.hip),
 with the state loss of the other two and, on request, the physics residuals
 evaluated on the model's own previous state.
+
+All three K-step losses take conservation=(lam_e, lam_q): energy and charge
+terms on the predicted states, which under a K-step loss carry a gradient (the
+reference's never do), formed inside the launches the driver already makes (the
+_ex entry points) from per-IC float64 sums; _Cons, _cons_refs and the
+workspace_ex hook of _Rollout are all the driver needs for them.
 """
 import json
 import os
@@ -778,9 +784,9 @@ def _applied_mean(values, applied):
 # <- state + PureGNN([n, u, E, x]) (evaluate_multi_ic.py:53-64;
 # hf_pure_unroll_update / hf_pure_unroll_adjoint).  One driver runs both; a
 # _Rollout says where they differ.
-def _flux_adjoint(grid, tr, pred, k, weights, scale, direct, gnf, keep):
+def _flux_adjoint(grid, tr, pred, k, weights, scale, direct, gnf, keep, coef=None):
     g_fe, direct = engine.unroll_adjoint(grid, tr[0] if k == 0 else pred[k - 1], pred[k], tr[k + 1], weights, scale,
-                                         direct, gnf, want_direct=keep)
+                                         direct, gnf, want_direct=keep, cons_coef=coef)
     return g_fe.reshape(-1), direct
 
 
@@ -788,10 +794,10 @@ def _pure_update(grid, *args, **kwargs):
     return engine.pure_unroll_update(*args, **kwargs)
 
 
-def _pure_adjoint(grid, tr, pred, k, weights, scale, gd, gnf, keep):
+def _pure_adjoint(grid, tr, pred, k, weights, scale, gd, gnf, keep, coef=None):
     # dL/ds_{k+1} transposed is dL/ddelta_k: the seed of s_{k+1}, what reached s_{k+2} (the
     # residual update is the identity in the state) and step k+1's feature gradient
-    gd = engine.pure_unroll_adjoint(pred[k], tr[k + 1], weights, scale, gd, gnf)
+    gd = engine.pure_unroll_adjoint(pred[k], tr[k + 1], weights, scale, gd, gnf, cons_coef=coef)
     return gd, gd
 
 
@@ -804,8 +810,9 @@ class _Rollout(NamedTuple):
     forward: Callable    # engine.*_forward_train
     backward: Callable   # engine.*_backward
     workspace: Callable  # (B, nx, dev) -> scratch of update
-    update: Callable     # (grid, model output, state, x, target, weights, scale, want_nf=, out=, loss=, ws=)
-    adjoint: Callable    # (grid, tr, pred, k, weights, scale, carry, gnf, keep) -> (the model backward's
+    update: Callable     # (grid, model output, state, x, target, weights, scale, want_nf=, out=, loss=, ws=); with
+    #                      the conservation terms also cons=, cons_scale=, cons_ref=, cons_coef= (the _ex call)
+    adjoint: Callable    # (grid, tr, pred, k, weights, scale, carry, gnf, keep, coef=) -> (the model backward's
     #                      incoming gradient, carry): step k's, from step k+1's carry and feature gradient
     log_label: str
     checkpoint: str      # <checkpoint>_K<K>.pt
@@ -815,19 +822,66 @@ class _Rollout(NamedTuple):
     terms: int = 1       # values of a step's loss row, the first one the step's term of L
     direct_ok: Optional[Callable] = None  # (model, opt) -> the direct step applies (default: FlatAdam on exactly
     #                                       the model's parameters, grad enabled)
+    workspace_ex: Optional[Callable] = None  # the conservation terms' one hook: (B, nx, dev) -> scratch of the _ex
+    #                                          update; its loss row is `terms` values (at least 2) + (energy, charge)
 
 
 _FLUX = _Rollout(FluxGNN, "unrolled_loss", None, lambda st, x: build_chain_graph_batch(st, x)[0],
                  engine.graph_forward_train, engine.graph_backward, engine.unroll_workspace, engine.unroll_update,
-                 _flux_adjoint, "Unrolled loss", "hybrid_unrolled", "history_unrolled")
+                 _flux_adjoint, "Unrolled loss", "hybrid_unrolled", "history_unrolled",
+                 workspace_ex=engine.unroll_workspace_ex)
 _PURE = _Rollout(PureGNN, "pure_unrolled_loss", 4, pure_gnn_features,
                  engine.pure_gnn_forward_train, engine.pure_gnn_backward, engine.pure_unroll_workspace, _pure_update,
-                 _pure_adjoint, "PureGNN unrolled loss", "pure_gnn_unrolled", "history_pure_gnn_unrolled")
+                 _pure_adjoint, "PureGNN unrolled loss", "pure_gnn_unrolled", "history_pure_gnn_unrolled",
+                 workspace_ex=engine.pure_unroll_workspace_ex)
 
 
-def _rollout_forward(m, flat, dims, traj, x, grid, weights):
+class _Cons(NamedTuple):
+    """The energy and charge terms of a K-step loss: lam = (lam_e, lam_q), ref "target", "start" or [B,K,2] float64."""
+    lam: tuple
+    ref: object
+
+
+def _conservation(conservation, conservation_ref, trainer=False):
+    """The public conservation / conservation_ref arguments as a _Cons (None: no terms)."""
+    if conservation is None:
+        if not (isinstance(conservation_ref, str) and conservation_ref == "target"):
+            raise ValueError("conservation_ref belongs to the energy and charge terms: pass conservation with it")
+        return None
+    lam = tuple(float(v) for v in conservation)
+    if len(lam) != 2 or not all(v >= 0 for v in lam):
+        raise ValueError("conservation must be (lam_e, lam_q), both >= 0")
+    if isinstance(conservation_ref, str):
+        if conservation_ref not in ("target", "start"):
+            raise ValueError(f'conservation_ref must be "target", "start" or a [B,K,2] tensor, got {conservation_ref!r}')
+    elif trainer:
+        raise ValueError('a trainer takes conservation_ref "target" or "start"')
+    elif not isinstance(conservation_ref, torch.Tensor):
+        raise ValueError('conservation_ref must be "target", "start" or a float64 [B,K,2] tensor')
+    return _Cons(lam, conservation_ref)
+
+
+def _cons_refs(cons, tr):
+    """The steps' references [K,B,2] float64 (step k's rows contiguous) for the
+    window tr [K+1,B,3,nx]: one hf_state_moments launch over the whole window,
+    every step's reference a view of its output -- "target": (e, q) of s*_k,
+    "start": of s*_0 for every step; a [B,K,2] tensor: as given."""
+    K, B = tr.shape[0] - 1, tr.shape[1]
+    if isinstance(cons.ref, str):
+        mom = engine.state_moments(tr)
+        return mom[1:] if cons.ref == "target" else mom[:1].expand(K, B, 2)
+    ref = cons.ref
+    if ref.dtype != torch.float64 or tuple(ref.shape) != (B, K, 2) or ref.device != tr.device:
+        raise ValueError(f"conservation_ref must be float64 [{B},{K},2] on {tr.device}, got {tuple(ref.shape)} "
+                         f"{ref.dtype}")
+    return ref.detach().transpose(0, 1).contiguous()
+
+
+def _rollout_forward(m, flat, dims, traj, x, grid, weights, cons=None):
     """The K taped forwards and updates.  Returns (loss [] , rec): rec holds
-    what the backward needs and the predicted states `pred` [K,B,3,nx]."""
+    what the backward needs and the predicted states `pred` [K,B,3,nx].  cons
+    (a _Cons): the updates are the _ex calls, which add the energy and charge
+    terms and leave the adjoints' coefficients in rec["coef"] [K,B,2]."""
     B, K1, _, nx = traj.shape
     K = K1 - 1
     dev = traj.device
@@ -835,8 +889,14 @@ def _rollout_forward(m, flat, dims, traj, x, grid, weights):
     ei = shared_chain_edge_index(nx, B, dev) if m.graph else None
     scale = 1.0 / (K * 3 * B * nx)
     pred = torch.empty(K, B, 3, nx, device=dev)
-    terms = torch.empty(K, device=dev) if m.terms == 1 else torch.empty(K, m.terms, device=dev)
-    ws = m.workspace(B, nx, dev)
+    if cons is None:
+        terms = torch.empty(K, device=dev) if m.terms == 1 else torch.empty(K, m.terms, device=dev)
+        ws = m.workspace(B, nx, dev)
+        refs = coef = None
+    else:
+        terms = torch.empty(K, max(m.terms, 2) + 2, device=dev)
+        ws = m.workspace_ex(B, nx, dev)
+        refs, coef = _cons_refs(cons, tr), torch.empty(K, B, 2, device=dev)
     st = tr[0]
     nf = m.features(st, x)
     forward, update = m.forward, m.update
@@ -846,13 +906,15 @@ def _rollout_forward(m, flat, dims, traj, x, grid, weights):
             y, tape, nf_d, ei_d, chain_nx = forward(flat, dims, nf, ei)
         else:
             y, tape, nf_d, ei_d, chain_nx = forward(flat, dims, nf, ei, out=pred[k])
+        ckw = {} if cons is None else dict(cons=cons.lam, cons_scale=1.0 / (K * B), cons_ref=refs[k], cons_coef=coef[k])
         _, nf, _ = update(grid, y, st, x, tr[k + 1], weights, scale, want_nf=k + 1 < K, out=pred[k],
-                          loss=terms[k:k + 1] if m.terms == 1 else terms[k], ws=ws)
+                          loss=terms[k:k + 1] if terms.dim() == 1 else terms[k], ws=ws, **ckw)
         tapes.append(tape)
         nfs.append(nf_d)
         st = pred[k]
-    rec = dict(tr=tr, pred=pred, tapes=tapes, nfs=nfs, ei=ei_d, chain_nx=chain_nx, scale=scale, K=K, terms=terms)
-    return (terms.sum() if m.terms == 1 else terms[:, 0].sum()), rec
+    rec = dict(tr=tr, pred=pred, tapes=tapes, nfs=nfs, ei=ei_d, chain_nx=chain_nx, scale=scale, K=K, terms=terms,
+               coef=coef)
+    return (terms.sum() if terms.dim() == 1 else terms[:, 0].sum()), rec
 
 
 def _rollout_backward(m, flat, dims, rec, grid, weights, through_state):
@@ -861,11 +923,12 @@ def _rollout_backward(m, flat, dims, rec, grid, weights, through_state):
     Returns d loss / d params as one flat buffer."""
     tr, pred, K, scale = rec["tr"], rec["pred"], rec["K"], rec["scale"]
     nfs, ei, chain_nx, tapes = rec["nfs"], rec["ei"], rec["chain_nx"], rec["tapes"]
-    adjoint, backward = m.adjoint, m.backward
+    adjoint, backward, coef = m.adjoint, m.backward, rec["coef"]
     total, carry, gnf = None, None, None
     for k in range(K - 1, -1, -1):
         keep = through_state and k > 0  # step k's state gradient feeds step k-1
-        g, carry = adjoint(grid, tr, pred, k, weights, scale, carry if through_state else None, gnf, keep)
+        ckw = {} if coef is None else dict(coef=coef[k])
+        g, carry = adjoint(grid, tr, pred, k, weights, scale, carry if through_state else None, gnf, keep, **ckw)
         gp, gnf = backward(flat, dims, nfs[k], ei, chain_nx, tapes[k], g, keep)
         total = gp if total is None else total.add_(gp)
     return total
@@ -901,9 +964,9 @@ class _RolloutLoss(torch.autograd.Function):
     updates, backward = K adjoint / model-backward pairs."""
 
     @staticmethod
-    def forward(ctx, m, traj, x, grid, weights, through_state, dims, *params):
+    def forward(ctx, m, traj, x, grid, weights, through_state, dims, cons, *params):
         flat, _ = flat_params(params, traj.device)
-        loss, rec = _rollout_forward(m, flat, dims, traj, x, grid, weights)
+        loss, rec = _rollout_forward(m, flat, dims, traj, x, grid, weights, cons)
         ctx.m, ctx.rec, ctx.flat, ctx.grid, ctx.weights, ctx.through, ctx.dims = \
             m, rec, flat, grid, weights, through_state, dims
         ctx.shapes = [q.shape for q in params]
@@ -917,20 +980,21 @@ class _RolloutLoss(torch.autograd.Function):
         gp = _rollout_backward(ctx.m, ctx.flat, ctx.dims, ctx.rec, ctx.grid, ctx.weights, ctx.through)
         ctx.rec = None  # the tapes are consumed
         gp = gp.mul_(g_loss)  # (exact for autograd's seed 1)
-        return (None, None, None, None, None, None, None, *split_flat(gp, ctx.shapes, ctx.param_devices))
+        return (None, None, None, None, None, None, None, None, *split_flat(gp, ctx.shapes, ctx.param_devices))
 
 
-def _rollout_loss(m, model, traj, x, grid, channel_weights, through_state, return_states=False):
+def _rollout_loss(m, model, traj, x, grid, channel_weights, through_state, return_states=False, cons=None):
     x = _rollout_check(m, model, traj, x, grid)
     dims = (model.input_dim, model.hidden_dim, model.num_layers)
     w = tuple(float(v) for v in channel_weights)
-    loss, pred, terms = _RolloutLoss.apply(m, traj, x, grid, w, bool(through_state), dims, *model.parameters())
+    loss, pred, terms = _RolloutLoss.apply(m, traj, x, grid, w, bool(through_state), dims, cons, *model.parameters())
     if not return_states:
         return loss
-    return (loss, pred) if m.terms == 1 else (loss, pred, terms)
+    return (loss, pred) if terms.dim() == 1 else (loss, pred, terms)
 
 
-def _rollout_step(m, model, opt, traj, x, grid, channel_weights, through_state):
+def _rollout_step(m, model, opt, traj, x, grid, channel_weights, through_state, cons=None, terms_out=None):
+    """terms_out: a list that receives the step's loss rows [K, terms] (the trainers' energy and charge history)."""
     if m.direct_ok is not None:
         if not m.direct_ok(model, opt):
             return None
@@ -945,15 +1009,17 @@ def _rollout_step(m, model, opt, traj, x, grid, channel_weights, through_state):
     x = _rollout_check(m, model, traj, x, grid)
     dims = (model.input_dim, model.hidden_dim, model.num_layers)
     w = tuple(float(v) for v in channel_weights)
-    loss, rec = _rollout_forward(m, flat, dims, traj, x, grid, w)
+    loss, rec = _rollout_forward(m, flat, dims, traj, x, grid, w, cons)
     gp = _rollout_backward(m, flat, dims, rec, grid, w, bool(through_state))
     assign_grads(params, gp)
     opt.step()
+    if terms_out is not None:
+        terms_out.append(rec["terms"])
     return loss.detach()
 
 
 def _train_windows(m, model, data, x, grid, init, epochs, lr, batch_size, seed, channel_weights, through_state,
-                   device, save_dir, log, guard=(0.0, None, False, None)):
+                   device, save_dir, log, guard=(0.0, None, False, None), cons=None):
     """The K-step trainers' loop: Adam(lr) over shuffled batches of batch_size
     windows of data (a WindowDataset), one direct step each (the autograd step
     where that does not apply), one host sync per epoch.  model: the freshly
@@ -961,7 +1027,9 @@ def _train_windows(m, model, data, x, grid, init, epochs, lr, batch_size, seed, 
     (weight_decay, max_grad_norm, skip_nonfinite, scheduler) as train_model's;
     with clipping or skipping on the epoch's loss is the mean over the windows
     of the steps that were applied, and the history gains grad_norm_max and
-    skipped_steps."""
+    skipped_steps.  cons (a _Cons): the energy and charge terms are on, and the
+    history gains energy_loss and charge_loss, the epoch's means of the two
+    terms' values, weighted as loss."""
     K = data.K
     x_dev = torch.as_tensor(np.asarray(x, dtype=np.float32), device=device) if x is not None else None
     if init is not None:
@@ -972,17 +1040,24 @@ def _train_windows(m, model, data, x, grid, init, epochs, lr, batch_size, seed, 
     opt, sched = _guarded_optimizer(model.parameters(), lr, *guard, device)
     gen = torch.Generator().manual_seed(0 if seed is None else seed)
     history = {"epoch": [], "loss": [], "seconds": []}
+    if cons is not None:
+        history["energy_loss"], history["charge_loss"] = [], []
     stats = _StepStats(opt, history)
     model.train()
     for epoch in range(1, epochs + 1):
         order = torch.randperm(len(data), generator=gen).to(device)
         t0 = time.perf_counter()
         losses = []
+        rows = [] if cons is not None else None  # the steps' loss rows [K, terms]
         for b0 in range(0, len(order), batch_size):
             win = data.batch(order[b0:b0 + batch_size])
-            loss = _rollout_step(m, model, opt, win, x_dev, grid, channel_weights, through_state)
+            loss = _rollout_step(m, model, opt, win, x_dev, grid, channel_weights, through_state, cons, rows)
             if loss is None:
-                loss = _rollout_loss(m, model, win, x_dev, grid, channel_weights, through_state)
+                if cons is None:
+                    loss = _rollout_loss(m, model, win, x_dev, grid, channel_weights, through_state)
+                else:
+                    loss, _, terms = _rollout_loss(m, model, win, x_dev, grid, channel_weights, through_state, True, cons)
+                    rows.append(terms)
                 opt.zero_grad()
                 loss.backward()
                 opt.step()
@@ -990,10 +1065,19 @@ def _train_windows(m, model, data, x, grid, init, epochs, lr, batch_size, seed, 
             losses.append((loss, win.shape[0]))
             stats.note(win.shape[0])
         count = len(data)
+        if rows is not None:
+            rows = [(r[:, -2:].sum(0), n) for r, (_, n) in zip(rows, losses)]
         if stats:
-            losses = [row for row, a in zip(losses, stats.read()) if a]
+            applied = stats.read()
+            losses = [row for row, a in zip(losses, applied) if a]
+            if rows is not None:
+                rows = [row for row, a in zip(rows, applied) if a]
             count = stats.weight
         tot = sum(float(l) * n for l, n in losses)  # one host sync per epoch
+        if rows is not None:
+            ec = torch.stack([r for r, _ in rows]).tolist() if rows else []
+            for j, key in enumerate(("energy_loss", "charge_loss")):
+                history[key].append(sum(v[j] * n for v, (_, n) in zip(ec, rows)) / count if count else float("nan"))
         torch.cuda.synchronize(device)
         if sched is not None:
             sched.step()
@@ -1012,7 +1096,8 @@ def _train_windows(m, model, data, x, grid, init, epochs, lr, batch_size, seed, 
     return model, history
 
 
-def unrolled_loss(model, traj, x, grid, channel_weights=(1.0, 1.0, 1.0), through_state=True, return_states=False):
+def unrolled_loss(model, traj, x, grid, channel_weights=(1.0, 1.0, 1.0), through_state=True, return_states=False,
+                  conservation=None, conservation_ref="target"):
     """L = (1/K) sum_{k=1..K} mean_{b,ch,i} w_ch (s^_k - s*_k)^2 of the hybrid
     solver (src/hybrid_solver.py:45-63) unrolled K steps from traj[:, 0], against
     the targets traj[:, 1:] (classical solver states): traj [B,K+1,3,nx] on the
@@ -1024,11 +1109,23 @@ def unrolled_loss(model, traj, x, grid, channel_weights=(1.0, 1.0, 1.0), through
     form): each step's loss reaches only its own FluxGNN call.  Per unrolled step
     the forward is hf_graph_forward_train + one hf_unroll_update launch, the
     backward one hf_unroll_adjoint launch + hf_graph_backward.  return_states:
-    also the predicted states [K,B,3,nx] (no gradient)."""
-    return _rollout_loss(_FLUX, model, traj, x, grid, channel_weights, through_state, return_states)
+    also the predicted states [K,B,3,nx] (no gradient).  conservation = (lam_e, lam_q) adds L_cons = (1/K) sum_k mean_b [ lam_e
+    (e(s^_k)_b - eref_kb)^2 + lam_q (q(s^_k)_b - qref_kb)^2 ] with e = 0.5 (sum
+    u^2 + sum E^2) / nx and q = sum n / nx (the energy and charge the evaluation
+    scores), in float64, inside the same launches (the _ex calls of
+    include/hybridflux.h) plus one hf_state_moments launch; conservation_ref:
+    "target" (the reference of step k is the classical s*_k), "start" (s*_0 for
+    every step: the drift the evaluation reports) or a float64 [B,K,2] tensor of
+    (eref, qref).  None (the default): the calls and bits of the loss without the
+    terms.  With conservation, return_states also returns the steps' rows
+    [K,4] = (total, state, energy, charge).  The charge term has no gradient here
+    (the finite-volume update conserves charge identically); its value is reported."""
+    return _rollout_loss(_FLUX, model, traj, x, grid, channel_weights, through_state, return_states,
+                         _conservation(conservation, conservation_ref))
 
 
-def unrolled_step(model, opt, traj, x, grid, channel_weights=(1.0, 1.0, 1.0), through_state=True):
+def unrolled_step(model, opt, traj, x, grid, channel_weights=(1.0, 1.0, 1.0), through_state=True, conservation=None,
+                  conservation_ref="target"):
     """unrolled_loss -> backward -> opt.step() without autograd, after
     direct_step: FluxGNN with flat parameters (flatten_parameters_), FlatAdam
     over exactly those parameters, grad enabled.  The same forwards, adjoints,
@@ -1036,7 +1133,8 @@ def unrolled_step(model, opt, traj, x, grid, channel_weights=(1.0, 1.0, 1.0), th
     same parameters bit for bit, without autograd's seed, product and
     bookkeeping launches.  Returns the detached loss, or None when the case does
     not apply (the caller then takes the autograd step)."""
-    return _rollout_step(_FLUX, model, opt, traj, x, grid, channel_weights, through_state)
+    return _rollout_step(_FLUX, model, opt, traj, x, grid, channel_weights, through_state,
+                         _conservation(conservation, conservation_ref))
 
 
 def unrolled_train_flop_per_sample(K=4, nx=64, H=128, L=4, F=4):
@@ -1083,7 +1181,8 @@ class WindowDataset:
 
 def train_unrolled(trajectories, x, dt, dx, nu, K=4, epochs=10, lr=1e-3, batch_size=32, seed=None, init=None,
                    channel_weights=(1.0, 1.0, 1.0), through_state=True, device="cuda", save_dir="checkpoints",
-                   log=print, weight_decay=0.0, max_grad_norm=None, skip_nonfinite=False, scheduler=None):
+                   log=print, weight_decay=0.0, max_grad_norm=None, skip_nonfinite=False, scheduler=None,
+                   conservation=None, conservation_ref="target"):
     """Train (or fine-tune) FluxGNN on K-step windows of classical trajectories
     [N,T+1,3,nx] (datagen.generate_trajectories) with the unrolled loss: Adam(lr)
     over shuffled batches of batch_size windows, one unrolled_step each.  init:
@@ -1093,7 +1192,10 @@ def train_unrolled(trajectories, x, dt, dx, nu, K=4, epochs=10, lr=1e-3, batch_s
     and history_unrolled_K<K>.json as train_model writes its files (save_dir=None
     skips).  weight_decay, max_grad_norm, skip_nonfinite, scheduler: as
     train_model's -- the guard that keeps one window whose rollout blows up from
-    turning every parameter into NaN."""
+    turning every parameter into NaN.  conservation = (lam_e, lam_q),
+    conservation_ref "target" or "start": unrolled_loss's energy and charge
+    terms; the history then also holds energy_loss and charge_loss."""
+    cons = _conservation(conservation, conservation_ref, trainer=True)
     engine.require_device(torch.empty(0, device=device), "device")
     if seed is not None:
         torch.manual_seed(seed)
@@ -1104,10 +1206,11 @@ def train_unrolled(trajectories, x, dt, dx, nu, K=4, epochs=10, lr=1e-3, batch_s
     model = FluxGNN(MODEL_CONFIG["input_dim"], MODEL_CONFIG["hidden_dim"], MODEL_CONFIG["num_layers"])
     return _train_windows(_FLUX, model, data, x, grid, init, epochs, lr, batch_size, seed, channel_weights,
                           through_state, device, save_dir, log,
-                          (weight_decay, max_grad_norm, skip_nonfinite, scheduler))
+                          (weight_decay, max_grad_norm, skip_nonfinite, scheduler), cons)
 
 
-def pure_unrolled_loss(model, traj, x, channel_weights=(1.0, 1.0, 1.0), through_state=True, return_states=False):
+def pure_unrolled_loss(model, traj, x, channel_weights=(1.0, 1.0, 1.0), through_state=True, return_states=False,
+                       conservation=None, conservation_ref="target"):
     """L = (1/K) sum_{k=1..K} mean_{b,ch,i} w_ch (s^_k - s*_k)^2 of PureGNN's own
     rollout s^_{k+1} = s^_k + PureGNN([n, u, E, x])^T (evaluate_multi_ic.py:53-64)
     unrolled K steps from traj[:, 0], against the targets traj[:, 1:] (classical
@@ -1120,11 +1223,22 @@ def pure_unrolled_loss(model, traj, x, channel_weights=(1.0, 1.0, 1.0), through_
     the forward is hf_pure_gnn_forward_train + one hf_pure_unroll_update launch,
     the backward one hf_pure_unroll_adjoint launch + hf_pure_gnn_backward.
     model: a PureGNN with input_dim 4.  return_states: also the predicted states
-    [K,B,3,nx] (no gradient)."""
-    return _rollout_loss(_PURE, model, traj, x, None, channel_weights, through_state, return_states)
+    [K,B,3,nx] (no gradient).  conservation = (lam_e, lam_q) adds L_cons = (1/K) sum_k mean_b [ lam_e
+    (e(s^_k)_b - eref_kb)^2 + lam_q (q(s^_k)_b - qref_kb)^2 ] with e = 0.5 (sum
+    u^2 + sum E^2) / nx and q = sum n / nx (the energy and charge the evaluation
+    scores), in float64, inside the same launches (the _ex calls of
+    include/hybridflux.h) plus one hf_state_moments launch; conservation_ref:
+    "target" (the reference of step k is the classical s*_k), "start" (s*_0 for
+    every step: the drift the evaluation reports) or a float64 [B,K,2] tensor of
+    (eref, qref).  None (the default): the calls and bits of the loss without the
+    terms.  With conservation, return_states also returns the steps' rows
+    [K,4] = (total, state, energy, charge)."""
+    return _rollout_loss(_PURE, model, traj, x, None, channel_weights, through_state, return_states,
+                         _conservation(conservation, conservation_ref))
 
 
-def pure_unrolled_step(model, opt, traj, x, channel_weights=(1.0, 1.0, 1.0), through_state=True):
+def pure_unrolled_step(model, opt, traj, x, channel_weights=(1.0, 1.0, 1.0), through_state=True, conservation=None,
+                       conservation_ref="target"):
     """pure_unrolled_loss -> backward -> opt.step() without autograd, after
     unrolled_step: PureGNN with flat parameters (flatten_parameters_), FlatAdam
     over exactly those parameters, grad enabled.  The same forwards, adjoints,
@@ -1132,7 +1246,8 @@ def pure_unrolled_step(model, opt, traj, x, channel_weights=(1.0, 1.0, 1.0), thr
     same parameters bit for bit, without autograd's seed, product and
     bookkeeping launches.  Returns the detached loss, or None when the case does
     not apply (the caller then takes the autograd step)."""
-    return _rollout_step(_PURE, model, opt, traj, x, None, channel_weights, through_state)
+    return _rollout_step(_PURE, model, opt, traj, x, None, channel_weights, through_state,
+                         _conservation(conservation, conservation_ref))
 
 
 def pure_unrolled_train_flop_per_sample(K=4, nx=64, H=128, L=4, F=4):
@@ -1148,7 +1263,7 @@ def pure_unrolled_train_flop_per_sample(K=4, nx=64, H=128, L=4, F=4):
 def train_pure_gnn_unrolled(trajectories, x, K=4, epochs=10, lr=1e-3, batch_size=32, hidden_dim=None, num_layers=None,
                             seed=None, init=None, channel_weights=(1.0, 1.0, 1.0), through_state=True, device="cuda",
                             save_dir="checkpoints", log=print, weight_decay=0.0, max_grad_norm=None,
-                            skip_nonfinite=False, scheduler=None):
+                            skip_nonfinite=False, scheduler=None, conservation=None, conservation_ref="target"):
     """Train (or fine-tune) PureGNN on K-step windows of classical trajectories
     [N,T+1,3,nx] (datagen.generate_trajectories) with the unrolled loss:
     train_unrolled's loop -- Adam(lr) over shuffled batches of batch_size windows
@@ -1160,7 +1275,8 @@ def train_pure_gnn_unrolled(trajectories, x, K=4, epochs=10, lr=1e-3, batch_size
     windows), seconds, and writes checkpoints/pure_gnn_unrolled_K<K>.pt (a state
     dict the reference's PureGNN loads) and history_pure_gnn_unrolled_K<K>.json
     (save_dir=None skips).  weight_decay, max_grad_norm, skip_nonfinite,
-    scheduler: as train_unrolled's."""
+    scheduler, conservation, conservation_ref: as train_unrolled's."""
+    cons = _conservation(conservation, conservation_ref, trainer=True)
     engine.require_device(torch.empty(0, device=device), "device")
     if seed is not None:
         torch.manual_seed(seed)
@@ -1169,7 +1285,7 @@ def train_pure_gnn_unrolled(trajectories, x, K=4, epochs=10, lr=1e-3, batch_size
                     MODEL_CONFIG["num_layers"] if num_layers is None else num_layers)
     return _train_windows(_PURE, model, data, x, None, init, epochs, lr, batch_size, seed, channel_weights,
                           through_state, device, save_dir, log,
-                          (weight_decay, max_grad_norm, skip_nonfinite, scheduler))
+                          (weight_decay, max_grad_norm, skip_nonfinite, scheduler), cons)
 
 
 # --------------------------------------------------------------------- PINN
@@ -1418,20 +1534,21 @@ def _pinn_roll_forward(flat, dims, state, ei, out):
     return y, tape, s2, None, 0
 
 
-def _pinn_roll_update(phys, y, st, x, target, weights, scale, want_nf, out, loss, ws):
+def _pinn_roll_update(phys, y, st, x, target, weights, scale, want_nf, out, loss, ws, **cons):
     # the forward wrote s^_k into `out` itself; the next model input is that state
     engine.pinn_unroll_loss(out, target, weights, scale, state=st if phys.lam is not None else None, losses=loss,
-                            ws=ws, **phys.kw(scale))
+                            ws=ws, **phys.kw(scale), **cons)
     return out, out, None
 
 
-def _pinn_roll_adjoint(phys, tr, pred, k, weights, scale, carry, gstate, keep):
+def _pinn_roll_adjoint(phys, tr, pred, k, weights, scale, carry, gstate, keep, coef=None):
     # gstate: hf_pinn_backward's dL/dstate of step k+1, there exactly when the state gradient passes (k < K-1)
     B, _, nx = pred[k].shape
     on = phys.lam is not None
     g = engine.pinn_unroll_adjoint(pred[k], tr[k + 1], weights, scale, state=(tr[0] if k == 0 else pred[k - 1]) if on
                                    else None, pred_next=pred[k + 1] if on and gstate is not None else None,
-                                   grad_state_next=None if gstate is None else gstate.view(B, 3, nx), **phys.kw(scale))
+                                   grad_state_next=None if gstate is None else gstate.view(B, 3, nx), cons_coef=coef,
+                                   **phys.kw(scale))
     return g.view(B, 3 * nx), None
 
 
@@ -1441,7 +1558,8 @@ def _pinn_roll_backward(flat, dims, state, ei, chain_nx, tape, g, keep):
 
 _PINN = _Rollout(PINN, "pinn_unrolled_loss", None, lambda st, x: st, _pinn_roll_forward, _pinn_roll_backward,
                  engine.pinn_unroll_workspace, _pinn_roll_update, _pinn_roll_adjoint, "PINN unrolled loss",
-                 "pinn_unrolled", "history_pinn_unrolled", graph=False, terms=5, direct_ok=_pinn_direct_ok)
+                 "pinn_unrolled", "history_pinn_unrolled", graph=False, terms=5, direct_ok=_pinn_direct_ok,
+                 workspace_ex=engine.pinn_unroll_workspace_ex)
 
 
 def _pinn_phys(physics_weights, dx, dt, nu, length):
@@ -1460,7 +1578,8 @@ def _pinn_phys(physics_weights, dx, dt, nu, length):
 
 
 def pinn_unrolled_loss(model, traj, dx=None, dt=None, nu=None, channel_weights=(1.0, 1.0, 1.0), physics_weights=None,
-                       through_state=True, return_states=False, length=None):
+                       through_state=True, return_states=False, length=None, conservation=None,
+                       conservation_ref="target"):
     """L = (1/K) sum_{k=1..K} [ mean_{b,ch,i} w_ch (s^_k - s*_k)^2 + l_c mean r_c^2 +
     l_m mean r_m^2 + l_p mean r_p^2 ] of PINN's own rollout s^_k = s^_{k-1} +
     net(s^_{k-1}) (evaluate_multi_ic.py:70-83) unrolled K steps from traj[:, 0]
@@ -1478,13 +1597,24 @@ def pinn_unrolled_loss(model, traj, dx=None, dt=None, nu=None, channel_weights=(
     forward is hf_pinn_forward_train + one hf_pinn_unroll_loss launch, the
     backward one hf_pinn_unroll_adjoint launch + hf_pinn_backward.
     return_states: also the predicted states [K,B,3,nx] and the steps' terms
-    [K,5] = (total, data, cont, mom, pois), both without gradient."""
+    [K,5] = (total, data, cont, mom, pois), both without gradient.
+    conservation = (lam_e, lam_q) adds L_cons = (1/K) sum_k mean_b [ lam_e
+    (e(s^_k)_b - eref_kb)^2 + lam_q (q(s^_k)_b - qref_kb)^2 ] with e = 0.5 (sum
+    u^2 + sum E^2) / nx and q = sum n / nx (the energy and charge the evaluation
+    scores), in float64, inside the same launches (the _ex calls of
+    include/hybridflux.h) plus one hf_state_moments launch; conservation_ref:
+    "target" (the reference of step k is the classical s*_k), "start" (s*_0 for
+    every step: the drift the evaluation reports) or a float64 [B,K,2] tensor of
+    (eref, qref).  None (the default): the calls and bits of the loss without the
+    terms.  With conservation the steps' rows are
+    [K,7] = (total, data, cont, mom, pois, energy, charge)."""
     return _rollout_loss(_PINN, model, traj, None, _pinn_phys(physics_weights, dx, dt, nu, length), channel_weights,
-                         through_state, return_states)
+                         through_state, return_states, _conservation(conservation, conservation_ref))
 
 
 def pinn_unrolled_step(model, opt, traj, dx=None, dt=None, nu=None, channel_weights=(1.0, 1.0, 1.0),
-                       physics_weights=None, through_state=True, length=None):
+                       physics_weights=None, through_state=True, length=None, conservation=None,
+                       conservation_ref="target"):
     """pinn_unrolled_loss -> backward -> opt.step() without autograd, after
     pure_unrolled_step: where pinn_step's direct path applies (the optimizer
     drives exactly the model's parameters, no parameter hooks, no anomaly mode)
@@ -1494,7 +1624,7 @@ def pinn_unrolled_step(model, opt, traj, dx=None, dt=None, nu=None, channel_weig
     or None when the case does not apply (the caller then takes the autograd
     step)."""
     return _rollout_step(_PINN, model, opt, traj, None, _pinn_phys(physics_weights, dx, dt, nu, length),
-                         channel_weights, through_state)
+                         channel_weights, through_state, _conservation(conservation, conservation_ref))
 
 
 def pinn_unrolled_train_flop_per_sample(K=4, D=192, H=256, L=4):
@@ -1508,7 +1638,8 @@ def pinn_unrolled_train_flop_per_sample(K=4, D=192, H=256, L=4):
 def train_pinn_unrolled(trajectories, dx, dt, nu, K=4, epochs=10, lr=1e-3, batch_size=32, hidden_dim=256, num_layers=4,
                         physics_weights=None, seed=None, init=None, channel_weights=(1.0, 1.0, 1.0),
                         through_state=True, device="cuda", save_dir="checkpoints", log=print, weight_decay=0.0,
-                        max_grad_norm=None, skip_nonfinite=False, scheduler=None):
+                        max_grad_norm=None, skip_nonfinite=False, scheduler=None, conservation=None,
+                        conservation_ref="target"):
     """Train (or fine-tune) PINN(3 nx, hidden_dim, num_layers) on K-step windows
     of classical trajectories [N,T+1,3,nx] with pinn_unrolled_loss:
     train_unrolled's loop -- Adam(lr) over shuffled batches of batch_size windows
@@ -1519,7 +1650,9 @@ def train_pinn_unrolled(trajectories, dx, dt, nu, K=4, epochs=10, lr=1e-3, batch
     Returns (model, history) with history keys epoch, loss, seconds, and writes
     checkpoints/pinn_unrolled_K<K>.pt (the reference PINN's keys) and
     history_pinn_unrolled_K<K>.json (save_dir=None skips).  weight_decay,
-    max_grad_norm, skip_nonfinite, scheduler: as train_unrolled's."""
+    max_grad_norm, skip_nonfinite, scheduler, conservation, conservation_ref: as
+    train_unrolled's."""
+    cons = _conservation(conservation, conservation_ref, trainer=True)
     engine.require_device(torch.empty(0, device=device), "device")
     if seed is not None:
         torch.manual_seed(seed)
@@ -1529,4 +1662,4 @@ def train_pinn_unrolled(trajectories, dx, dt, nu, K=4, epochs=10, lr=1e-3, batch
     model = PINN(3 * data.nx, hidden_dim, num_layers)
     return _train_windows(_PINN, model, data, None, phys, init, epochs, lr, batch_size, seed, channel_weights,
                           through_state, device, save_dir, log,
-                          (weight_decay, max_grad_norm, skip_nonfinite, scheduler))
+                          (weight_decay, max_grad_norm, skip_nonfinite, scheduler), cons)

@@ -648,6 +648,107 @@ int hf_pinn_unroll_adjoint(const float *dev_pred, const float *dev_state, const 
                            double dt, double dx, double nu, const double *dev_plan, float *dev_grad_out, void *stream);
 
 /*
+ * Unrolled training: energy and charge terms with live gradients, for all
+ * three rollout trainers.  Replaces: nothing the reference trains on -- its
+ * charge, energy_one and energy_multi terms carry no gradient (see
+ * hf_ablation_loss_ex above); under a K-step loss they do, because u_{k+1}
+ * depends on the parameters through E_k and E_{k+1} through n_{k+1}, and for
+ * PureGNN and PINN, which conserve nothing by construction, so does charge.
+ *
+ * With e(s)_b = 0.5 (sum_i u_i^2 + sum_i E_i^2) / nx and q(s)_b = (sum_i n_i) /
+ * nx (HF_NUM_METRICS [0] and [1]), a reference (eref_b, qref_b) per IC of the
+ * step, r_e = e(s^_k)_b - eref_b and r_q = q(s^_k)_b - qref_b, a step adds
+ *   cons_scale sum_b [ lam_e r_e^2 + lam_q r_q^2 ]      (cons_scale = 1 / (K B))
+ * to its term of L.  The sums and the residuals are float64 from the float32
+ * state, the squares taken in float64; e is never rounded to float32.  Its
+ * gradient with respect to s^_k is rank one per IC: d/du_i = ce_b u_i, d/dE_i =
+ * ce_b E_i, d/dn_i = cq_b with ce_b = 2 lam_e cons_scale r_e / nx and cq_b = 2
+ * lam_q cons_scale r_q / nx, which the forward call leaves in dev_cons_coef
+ * [B][2] = (ce, cq), computed in float64 and rounded to float32 once.
+ *
+ * hf_state_moments: dev_moments [rows][2] = (e, q) of dev_states [rows][3][nx],
+ * float64, one wave per row in a fixed order (a lane's cells ascending, the
+ * lanes in a fixed tree): two calls give the same bits.  Any nx >= 1.  One call
+ * on a whole window [K+1][B] gives every step's reference as a pointer into
+ * its output.
+ *
+ * hf_unroll_update_ex, hf_pure_unroll_update_ex, hf_pinn_unroll_loss_ex: the
+ * plain calls' arguments, with the loss row dev_losses in place of the single
+ * float -- (total, state, energy, charge) for the two GNNs, (total, data, cont,
+ * mom, pois, energy, charge) for PINN -- and cons (2 HOST floats lam_e, lam_q,
+ * or NULL), cons_scale, dev_cons_ref [B][2] float64 and dev_cons_coef [B][2].
+ * The per-IC sums of u^2, E^2 and n ride the reduction the kernel makes for its
+ * loss partial, float64 per workgroup through the workspace
+ * (hf_*_workspace_bytes_ex(B, nx)), no float atomics.  Whoever holds an IC's
+ * complete sums writes its coefficients: the IC's own workgroup (or wave, at the
+ * FFT sizes) in the hybrid and PINN kernels; in PureGNN's kernel, which cuts an
+ * IC into 1024-cell tiles, the last workgroup to arrive, adding the tiles in
+ * tile order.  The last arriver adds the ICs' values in IC order: two calls
+ * give the same bits.  State, node features and the state (data, residual)
+ * values are the plain calls' bit for bit.  With cons == NULL (then
+ * dev_cons_ref and dev_cons_coef must be NULL, and the plain workspace size
+ * is enough) total equals the plain call's loss and energy = charge = 0.  cons
+ * needs dev_target.
+ *
+ * hf_unroll_adjoint_ex, hf_pure_unroll_adjoint_ex, hf_pinn_unroll_adjoint_ex:
+ * the plain calls' arguments and dev_cons_coef ([B][2] or NULL: the plain
+ * call's bits).  The seed of s^_{k+1} gains (cq_b, ce_b u, ce_b E) on its three
+ * channels: one float32 product (none for cq) and one add per value, and the
+ * order of the sum is
+ *   ((2 w_ch loss_scale (s^ - s*) + new part) + ...the plain call's further terms in their order)
+ * -- hybrid: then grad_nf_next, then direct_next; PureGNN: then
+ * grad_delta_next, then grad_nf_next; PINN (whose sum is float64, the product
+ * float32): then the residual terms, part 2 and the carry.  The hybrid adjoint
+ * does not add cq: the finite-volume update conserves sum n identically (the
+ * face fluxes telescope), so the charge term's parameter gradient is
+ * identically 0 there and adding it would only inject rounding noise; the
+ * charge value is still reported.
+ *
+ * HF_EINVAL before any device call: cons without dev_target, dev_cons_ref,
+ * dev_cons_coef or a workspace; dev_cons_ref or dev_cons_coef without cons; a
+ * lam that is negative or NaN; a workspace smaller than the _ex query with
+ * cons; and everything the plain calls refuse (nx limits unchanged).  The size
+ * queries return -1 as the plain ones do.
+ */
+int hf_state_moments(const float *dev_states, int64_t rows, int nx, double *dev_moments, void *stream);
+int64_t hf_unroll_workspace_bytes_ex(int B, int nx);
+int hf_unroll_update_ex(const float *dev_flux_edge, const float *dev_state, const float *dev_x, const double *dev_plan,
+                        int poisson_mode, int B, int nx, float c, float dt, float *dev_state_next,
+                        float *dev_node_features_next /* or NULL */, const float *dev_target /* or NULL */,
+                        const float *weights, float loss_scale, float *dev_losses /* [4] */, void *dev_workspace,
+                        int64_t workspace_bytes, const float *cons /* 2 host: lam_e, lam_q; or NULL */,
+                        float cons_scale, const double *dev_cons_ref, float *dev_cons_coef, void *stream);
+int hf_unroll_adjoint_ex(const float *dev_state, const float *dev_state_next, const float *dev_target,
+                         const float *weights, float loss_scale, const float *dev_direct_next /* or NULL */,
+                         const float *dev_grad_nf_next /* or NULL */, const double *dev_plan, int poisson_mode, int B,
+                         int nx, float c, float dt, float *dev_grad_flux_edge, float *dev_direct /* or NULL */,
+                         const float *dev_cons_coef /* or NULL */, void *stream);
+int64_t hf_pure_unroll_workspace_bytes_ex(int B, int nx);
+int hf_pure_unroll_update_ex(const float *dev_delta, const float *dev_state, const float *dev_x, int B, int nx,
+                             float *dev_state_next, float *dev_node_features_next /* or NULL */,
+                             const float *dev_target /* or NULL */, const float *weights, float loss_scale,
+                             float *dev_losses /* [4] */, void *dev_workspace, int64_t workspace_bytes,
+                             const float *cons /* 2 host; or NULL */, float cons_scale, const double *dev_cons_ref,
+                             float *dev_cons_coef, void *stream);
+int hf_pure_unroll_adjoint_ex(const float *dev_state_next, const float *dev_target, const float *weights,
+                              float loss_scale, const float *dev_grad_delta_next /* or NULL */,
+                              const float *dev_grad_nf_next /* or NULL */, int B, int nx, float *dev_grad_delta,
+                              const float *dev_cons_coef /* or NULL */, void *stream);
+int64_t hf_pinn_unroll_workspace_bytes_ex(int B, int nx);
+int hf_pinn_unroll_loss_ex(const float *dev_pred, const float *dev_state, const float *dev_target, int B, int nx,
+                           const float *weights /* 3 host */, float loss_scale,
+                           const float *phys /* 3 host: l_c, l_m, l_p; or NULL */, float phys_scale, double dt,
+                           double dx, double nu, const double *dev_plan /* required iff phys */,
+                           float *dev_losses /* [7] */, void *dev_workspace, int64_t workspace_bytes,
+                           const float *cons /* 2 host; or NULL */, float cons_scale, const double *dev_cons_ref,
+                           float *dev_cons_coef, void *stream);
+int hf_pinn_unroll_adjoint_ex(const float *dev_pred, const float *dev_state, const float *dev_target,
+                              const float *dev_pred_next /* or NULL */, const float *dev_grad_state_next /* or NULL */,
+                              int B, int nx, const float *weights, float loss_scale, const float *phys,
+                              float phys_scale, double dt, double dx, double nu, const double *dev_plan,
+                              float *dev_grad_out, const float *dev_cons_coef /* or NULL */, void *stream);
+
+/*
  * Host helper (no device work): the Poisson "plan" for nx cells, length
  * hf_poisson_plan_len(nx) doubles.  plan[0..nx) is the first column c of the
  * real circulant matrix equal to the reference's spectral Poisson operator
