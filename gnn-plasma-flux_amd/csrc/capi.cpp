@@ -1563,6 +1563,128 @@ int hf_run(hf_model_t m, const float *state0, float *state_final, const float *x
                    metrics, ws, ws_bytes, stream);
 }
 
+namespace {
+
+// refine / substeps of the coarse-grained rollouts: r a power of two in 1..64 that divides nx_f, S >= 1.
+bool coarse_rs_ok(int nx_f, int r, int S) {
+  return nx_f >= 1 && r >= 1 && r <= 64 && (r & (r - 1)) == 0 && nx_f % r == 0 && S >= 1;
+}
+
+// hf_run_coarse keeps the fine states in registers where hf_run is one launch.
+bool coarse_fused(int nx_f) { return hf::fv_run_fused(nx_f) && fv_run_persistent(); }
+
+// Scratch of the chunked path for chunks of n coarse steps: the running fine
+// state, the chunk's fine trajectory (n S + 1 rows) and its fine flux (n S
+// rows).  -1: more than int64 holds.
+int64_t coarse_chunk_bytes(int B, int nx_f, int64_t n, int S) {
+  const __int128 cells = (__int128)B * nx_f, steps = (__int128)n * S;
+  const __int128 total = 12 * cells + 12 * cells * (steps + 1) + 4 * cells * steps + 3 * 256;
+  return total > (__int128)INT64_MAX ? -1 : up256(12LL * B * nx_f) + up256((int64_t)(12 * cells * (steps + 1))) +
+                                                up256((int64_t)(4 * cells * steps));
+}
+
+// Without a caller's workspace the chunked path allocates at most this much (but always one coarse step's worth).
+constexpr int64_t kCoarseOwnScratch = 256LL << 20;
+
+}  // namespace
+
+int64_t hf_run_coarse_workspace_bytes(int B, int nx_f, int T_c, int r, int S) {
+  if (B < 0 || T_c < 0 || !coarse_rs_ok(nx_f, r, S) || (int64_t)T_c * S > INT32_MAX) return -1;
+  if (B == 0 || T_c == 0 || coarse_fused(nx_f)) return 0;
+  return coarse_chunk_bytes(B, nx_f, T_c, S);
+}
+
+int hf_coarsen_traj(const float *traj_f, const float *flux_f, int B, int nx_f, int T_f, int r, int S, float *traj_c,
+                    float *flux_c, void *stream) {
+  if (B < 0 || nx_f < 1 || T_f < 0) return fail(HF_EINVAL, "hf_coarsen_traj: need B >= 0, nx_f >= 1, T_f >= 0");
+  if (!coarse_rs_ok(nx_f, r, S))
+    return fail(HF_EINVAL, "hf_coarsen_traj: refine must be a power of two in 1..64 that divides nx_f, substeps >= 1");
+  if (T_f % S) return fail(HF_EINVAL, "hf_coarsen_traj: T_f must be a multiple of substeps");
+  if ((flux_f == nullptr) != (flux_c == nullptr))
+    return fail(HF_EINVAL, "hf_coarsen_traj: the fine and the coarse flux go together");
+  const int T_c = T_f / S;
+  if ((int64_t)B * ((int64_t)T_c + 1) * 3 > INT32_MAX)
+    return fail(HF_EINVAL, "hf_coarsen_traj: more rows than a grid holds");
+  if (B == 0) return HF_OK;
+  if (!traj_f || !traj_c) return fail(HF_EINVAL, "hf_coarsen_traj: NULL trajectory");
+  hipStream_t s = as_stream(stream);
+  const int nx_c = nx_f / r;
+  HF_CHECK_HIP(hf::launch_coarsen_state(traj_f, ((int64_t)T_f + 1) * 3 * nx_f, traj_c, ((int64_t)T_c + 1) * 3 * nx_c, B,
+                                        T_c + 1, nx_f, r, S, 0, 0, s),
+               "hf_coarsen_traj");
+  if (flux_f)
+    HF_CHECK_HIP(hf::launch_coarsen_flux(flux_f, (int64_t)T_f * nx_f, flux_c, (int64_t)T_c * nx_c, B, T_c, nx_f, r, S,
+                                         0, 0, s),
+                 "hf_coarsen_traj(flux)");
+  return HF_OK;
+}
+
+int hf_run_coarse(const float *state0, float *state_final, const double *pc, int pm, int B, int nx_f, int T_c, int r,
+                  int S, float c, float dt, float nu, float dx2, float *traj, float *flux, void *ws, int64_t ws_bytes,
+                  void *stream) {
+  if (B < 0 || nx_f < 1 || T_c < 0) return fail(HF_EINVAL, "hf_run_coarse: need B >= 0, nx_f >= 1, T_c >= 0");
+  if (!coarse_rs_ok(nx_f, r, S))
+    return fail(HF_EINVAL, "hf_run_coarse: refine must be a power of two in 1..64 that divides nx_f, substeps >= 1");
+  if ((int64_t)T_c * S > INT32_MAX) return fail(HF_EINVAL, "hf_run_coarse: T_c * substeps exceeds int");
+  if (int rc = check_mode(pm, nx_f, "hf_run_coarse")) return rc;
+  if (!traj && !flux && !state_final) return fail(HF_EINVAL, "hf_run_coarse: no output requested");
+  if ((int64_t)B * ((int64_t)T_c + 1) * 3 > INT32_MAX) return fail(HF_EINVAL, "hf_run_coarse: more rows than a grid holds");
+  if (B == 0) return HF_OK;
+  if (!state0 || !pc) return fail(HF_EINVAL, "hf_run_coarse: NULL state or Poisson plan");
+  const bool fused = coarse_fused(nx_f);
+  int64_t chunk = T_c;  // coarse steps per chunk of the sequenced path
+  if (!fused && T_c > 0) {
+    const int64_t cap = ws ? ws_bytes : kCoarseOwnScratch;
+    const int64_t one = coarse_chunk_bytes(B, nx_f, 1, S);
+    if (one < 0 || (ws && ws_bytes < one))
+      return fail(HF_EINVAL, "hf_run_coarse: workspace smaller than hf_run_coarse_workspace_bytes(B, nx_f, 1, ...)");
+    // the most coarse steps whose scratch fits (the bytes grow with the steps)
+    int64_t lo = 1, hi = T_c;
+    while (lo < hi) {
+      const int64_t mid = lo + (hi - lo + 1) / 2, need = coarse_chunk_bytes(B, nx_f, mid, S);
+      if (need >= 0 && need <= cap) lo = mid;
+      else hi = mid - 1;
+    }
+    chunk = lo;
+  }
+  hipStream_t s = as_stream(stream);
+  if (fused) {  // row 0 and T_c = 0 included: the kernel writes every output itself
+    HF_CHECK_HIP(hf::launch_fv_run_coarse(state0, state_final, traj, pc, B, nx_f, T_c, r, S, c, dt, nu, dx2, flux, pm, s),
+                 "hf_run_coarse(fused)");
+    return HF_OK;
+  }
+  const int nx_c = nx_f / r;
+  const int64_t Sf = 3LL * nx_f, ldTc = ((int64_t)T_c + 1) * 3 * nx_c, ldFc = (int64_t)T_c * nx_c;
+  if (traj) HF_CHECK_HIP(hf::launch_coarsen_state(state0, Sf, traj, ldTc, B, 1, nx_f, r, S, 0, 0, s), "hf_run_coarse row 0");
+  if (T_c == 0) {
+    if (state_final && state_final != state0)
+      HF_CHECK_HIP(hipMemcpyAsync(state_final, state0, sizeof(float) * B * Sf, hipMemcpyDeviceToDevice, s),
+                   "hf_run_coarse copy");
+    return HF_OK;
+  }
+  Scratch sc;
+  if (int rc = sc.init(ws, ws_bytes, coarse_chunk_bytes(B, nx_f, chunk, S), s, "hf_run_coarse")) return rc;
+  float *own = sc.take(sizeof(float) * B * Sf);
+  float *cur = state_final ? state_final : own;  // the running fine state
+  float *tfb = sc.take(sizeof(float) * B * (chunk * S + 1) * Sf);
+  float *ffb = sc.take(sizeof(float) * B * chunk * S * nx_f);
+  if (cur != state0)
+    HF_CHECK_HIP(hipMemcpyAsync(cur, state0, sizeof(float) * B * Sf, hipMemcpyDeviceToDevice, s), "hf_run_coarse copy");
+  for (int64_t k0 = 0; k0 < T_c; k0 += chunk) {
+    const int64_t n = T_c - k0 < chunk ? T_c - k0 : chunk, nS = n * S;
+    if (int rc = hf_run_ex(nullptr, cur, cur, nullptr, pc, pm, B, nx_f, (int)nS, c, dt, nu, dx2, tfb,
+                           flux ? ffb : nullptr, nullptr, nullptr, 0, stream))
+      return rc;
+    if (traj)
+      HF_CHECK_HIP(hf::launch_coarsen_state(tfb, (nS + 1) * Sf, traj, ldTc, B, (int)n, nx_f, r, S, 1, k0 + 1, s),
+                   "hf_run_coarse(coarsen)");
+    if (flux)
+      HF_CHECK_HIP(hf::launch_coarsen_flux(ffb, nS * nx_f, flux, ldFc, B, (int)n, nx_f, r, S, 0, k0, s),
+                   "hf_run_coarse(coarsen flux)");
+  }
+  return HF_OK;
+}
+
 int hf_run_compare_ex(hf_model_t m, const float *state0, float *state_final, const float *x, const double *pc, int pm,
                       int B, int nx, int T, float c, float dt, float nu, float dx2, float *mse, float *metrics,
                       float *metrics_cl, void *ws, int64_t ws_bytes, void *stream) {

@@ -607,6 +607,279 @@ __global__ __launch_bounds__(kFvThreads) void fv_run_small_kernel(const float *s
   }
 }
 
+// ------------------------------------------ coarse-grained classical rollouts
+// A fine rollout (r fine cells per coarse cell, S fine steps per coarse step)
+// reduced to the coarse grid (include/hybridflux.h, hf_coarsen_traj):
+//   state  f32(tree / r), tree the adjacent pairwise float64 sum of the r
+//          cells r j .. r j + r - 1 of fine row S t;
+//   flux   f32(acc / S), acc the float64 sum, in substep order from 0.0, of the
+//          fine F at cell r j + r - 1 over fine steps S t .. S t + S - 1.
+// Wherever a lane holds a cell with cell = lane (mod r), the r cells of a
+// coarse cell sit in r adjacent lanes, and the xor butterfly over lane
+// distances 1, 2, .., r/2 IS the pairwise tree (float64 addition commutes
+// bit for bit, so every lane of the group ends with the tree's value).  Every
+// lane of the wave runs the shuffles; r is wave-uniform.
+// tree / r as a product with 1 / r: r is a power of two, so both 1 / r and the
+// product are exact and the bits are the division's.
+__device__ __forceinline__ float box_mean(float x, int r) {
+  double d = (double)x;
+  for (int o = 1; o < r; o <<= 1) d += __shfl_xor(d, o, 64);
+  return (float)(d * (1.0 / (double)r));
+}
+
+// hf_coarsen_traj's states: workgroup (b, t_c, channel), thread i owns fine
+// cells i + 256 k (256 = 0 mod r, so cell = lane mod r).  Fine row S (t0 + t_c)
+// of IC b -> coarse row (row0 + t_c).  ld_*: floats per IC.
+__global__ __launch_bounds__(kFvThreads) void coarsen_state_kernel(const float *__restrict__ tf, int64_t ld_f,
+                                                                   float *__restrict__ tc, int64_t ld_c, int rows,
+                                                                   int nx_f, int r, int S, int64_t t0, int64_t row0) {
+  const int64_t blk = blockIdx.x;
+  const int ch = (int)(blk % 3);
+  const int64_t t = (blk / 3) % rows, b = blk / 3 / rows;
+  const int nx_c = nx_f / r;
+  const float *src = tf + b * ld_f + (t0 + t) * S * 3 * nx_f + (int64_t)ch * nx_f;
+  float *dst = tc + b * ld_c + (row0 + t) * 3 * nx_c + (int64_t)ch * nx_c;
+  for (int i0 = 0; i0 < nx_f; i0 += kFvThreads) {  // uniform trip count: every lane shuffles
+    const int i = i0 + threadIdx.x;
+    const bool on = i < nx_f;  // r | nx_f: a group of r lanes is on or off whole
+    const float m = box_mean(on ? src[i] : 0.f, r);
+    if (on && (i & (r - 1)) == 0) dst[i / r] = m;
+  }
+}
+
+// hf_coarsen_traj's flux: one thread per (b, t_c, j).
+__global__ __launch_bounds__(kFvThreads) void coarsen_flux_kernel(const float *__restrict__ ff, int64_t ld_f,
+                                                                  float *__restrict__ fc, int64_t ld_c, int rows,
+                                                                  int nx_f, int r, int S, int64_t t0, int64_t row0) {
+  const int nx_c = nx_f / r;
+  const int64_t b = blockIdx.x / rows, t = blockIdx.x % rows;
+  const float *src = ff + b * ld_f + (t0 + t) * S * nx_f;
+  float *dst = fc + b * ld_c + (row0 + t) * nx_c;
+  for (int j = threadIdx.x; j < nx_c; j += kFvThreads) {
+    double acc = 0.0;
+    for (int s = 0; s < S; ++s) acc += (double)src[(int64_t)s * nx_f + (int64_t)r * j + r - 1];
+    dst[j] = (float)(acc / (double)S);
+  }
+}
+
+// One IC's registers (cells lane + 64 i) -> one coarse trajectory row.  The
+// 3 N/64 values go through `stage` (3 N floats of the wave's transform buffer,
+// free between steps; each lane reads back only what it wrote, so the LDS
+// queue's order is the only ordering needed) and are reduced one at a time in
+// a rolled loop: reduced straight from the register arrays in an unrolled
+// loop, the rows cost the spectral N = 512 and N = 1024 kernels 16 B and 248 B
+// of scratch per lane (a build without the row reduction had none).
+template <int N>
+__device__ __forceinline__ void coarse_row(const float (&n)[N / 64], const float (&u)[N / 64],
+                                           const float (&E)[N / 64], float *stage, float *row, int r, int lane) {
+  constexpr int V = N / 64;
+  const int nx_c = N / r, per = 64 / r;  // per: coarse cells per register slot
+  const bool lead = (lane & (r - 1)) == 0;
+  wave_lds_fence();  // the transform's reads of the buffer are done (and a compiler barrier: the buffer is double2 there, float here)
+#pragma unroll
+  for (int i = 0; i < V; ++i) {
+    stage[lane + 64 * i] = n[i];
+    stage[N + lane + 64 * i] = u[i];
+    stage[2 * N + lane + 64 * i] = E[i];
+  }
+#pragma unroll 1
+  for (int k = 0; k < 3 * V; ++k) {
+    const int ch = k / V, i = k % V;
+    const float m = box_mean(stage[ch * N + lane + 64 * i], r);
+    if (lead) row[ch * nx_c + lane / r + per * i] = m;
+  }
+  wave_lds_fence();  // the staged values are read before the buffer is written again
+}
+
+// fv_run_fft_kernel with the coarse-graining inside: the wave of an IC pair
+// steps T_c * S fine steps with both fine states in registers (every step
+// fv_run_fft_kernel's arithmetic in its order, so the fine states are hf_run's
+// bit for bit) and stores only coarse rows (row 0 = the coarsened IC, then one
+// every S steps) and the substep-averaged flux at the coarse faces.  The flux
+// accumulators are float64, one per register slot and IC, live across the S
+// substeps; only the lanes holding a coarse cell's last fine cell store theirs.
+// traj [B][T_c+1][3][N/r], flux [B][T_c][N/r], state_final [B][3][N] (fine):
+// each may be NULL.  state0 may alias state_final (a wave reads its pair whole
+// before it writes it).
+template <int N, bool TRI>
+__global__ __launch_bounds__(64 * kFftWaves, N >= 1024 ? 1 : 2) void fv_run_coarse_fft_kernel(
+    const float *state0, float *state_final, float *traj, const double *__restrict__ pc, float c, float dt, float nu,
+    float dx2, float *flux, int B, int T_c, int r, int S_sub) {
+  constexpr int V = N / 64;
+  constexpr int64_t S = 3LL * N;
+  __shared__ double2 s_fft[kFftWaves][fft_lds_elems<N>()];
+  __shared__ double2 s_plan[TRI ? 1 : N];  // the plan staged once, as in fv_run_fft_kernel
+  // N >= 512: the accumulators live in wave-private LDS, each lane reading and
+  // writing only its own slots, which leaves the spectral N = 1024 kernel 32 of
+  // its 512 registers (2 ICs x 16 float64 would be 64 more)
+  constexpr bool ACC_LDS = N >= 512;
+  __shared__ double s_acc[ACC_LDS ? kFftWaves : 1][2][ACC_LDS ? N : 1];
+  if constexpr (!TRI) {
+    for (int i = threadIdx.x; i < 2 * N; i += 64 * kFftWaves) reinterpret_cast<double *>(s_plan)[i] = pc[N + i];
+    __syncthreads();
+  }
+  const double h = TRI ? pc[0] : 0.0;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int64_t a = 2 * ((int64_t)blockIdx.x * kFftWaves + wave), b = a + 1;
+  if (a >= B) return;  // a whole wave; nothing below synchronises the workgroup
+  const bool two = b < B;
+  double *acc_a = s_acc[ACC_LDS ? wave : 0][0], *acc_b = s_acc[ACC_LDS ? wave : 0][1];
+  static_assert(sizeof(double2) * fft_lds_elems<N>() >= sizeof(float) * 3 * N, "coarse_row stages 3 N floats");
+  float *stage = reinterpret_cast<float *>(s_fft[wave]);
+  const int nx_c = N / r, per = 64 / r;
+  const int64_t ldT = (int64_t)(T_c + 1) * 3 * nx_c, ldF = (int64_t)T_c * nx_c;
+  const bool last = (lane & (r - 1)) == r - 1;  // this lane's cells are right faces of coarse cells
+  float na[V], ua[V], Ea[V], nb[V], ub[V], Eb[V];
+#pragma unroll
+  for (int i = 0; i < V; ++i) {
+    const int cell = lane + 64 * i;
+    na[i] = state0[a * S + cell];
+    ua[i] = state0[a * S + N + cell];
+    Ea[i] = state0[a * S + 2 * N + cell];
+    nb[i] = two ? state0[b * S + cell] : 0.f;
+    ub[i] = two ? state0[b * S + N + cell] : 0.f;
+    Eb[i] = two ? state0[b * S + 2 * N + cell] : 0.f;
+  }
+  if (traj) {
+    coarse_row<N>(na, ua, Ea, stage, traj + a * ldT, r, lane);
+    if (two) coarse_row<N>(nb, ub, Eb, stage, traj + b * ldT, r, lane);
+  }
+  MetricAcc unused;
+  unused.init();
+  for (int t = 0; t < T_c; ++t) {
+    double fa[ACC_LDS ? 1 : V], fb[ACC_LDS ? 1 : V];
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+      if constexpr (ACC_LDS) acc_a[lane + 64 * i] = acc_b[lane + 64 * i] = 0.0;
+      else fa[i] = fb[i] = 0.0;
+    }
+    for (int s = 0; s < S_sub; ++s) {
+      if (flux) {
+#pragma unroll
+        for (int i = 0; i < V; ++i) {  // F_n = n*u of this step, fv_update_regs' own product
+          const double Fa = (double)__fmul_rn(na[i], ua[i]), Fb = (double)__fmul_rn(nb[i], ub[i]);
+          if constexpr (ACC_LDS) {
+            acc_a[lane + 64 * i] += Fa;
+            acc_b[lane + 64 * i] += Fb;
+          } else {
+            fa[i] += Fa;
+            fb[i] += Fb;
+          }
+        }
+      }
+      double2 v[V];
+      {
+        double rho[V];
+        fv_update_regs<N>(na, ua, Ea, nullptr, nullptr, c, dt, nu, dx2, false, unused, lane, rho);
+#pragma unroll
+        for (int i = 0; i < V; ++i) v[i].x = rho[i];
+      }
+      {
+        double rho[V];
+        if (two) fv_update_regs<N>(nb, ub, Eb, nullptr, nullptr, c, dt, nu, dx2, false, unused, lane, rho);
+#pragma unroll
+        for (int i = 0; i < V; ++i) v[i].y = two ? rho[i] : 0.0;
+      }
+      poisson_pair<N, TRI>(v, s_fft[wave], s_plan, reinterpret_cast<const double *>(s_plan) + N, h, lane);
+      fv_run_E<N>(Ea, v, false, nullptr, unused, nullptr, lane);
+      if (two) fv_run_E<N>(Eb, v, true, nullptr, unused, nullptr, lane);
+    }
+    if (traj) {
+      coarse_row<N>(na, ua, Ea, stage, traj + a * ldT + (int64_t)(t + 1) * 3 * nx_c, r, lane);
+      if (two) coarse_row<N>(nb, ub, Eb, stage, traj + b * ldT + (int64_t)(t + 1) * 3 * nx_c, r, lane);
+    }
+    if (flux && last) {
+#pragma unroll
+      for (int i = 0; i < V; ++i) {
+        const int j = lane / r + per * i;
+        const double sa = ACC_LDS ? acc_a[lane + 64 * i] : fa[i], sb = ACC_LDS ? acc_b[lane + 64 * i] : fb[i];
+        flux[a * ldF + (int64_t)t * nx_c + j] = (float)(sa / (double)S_sub);
+        if (two) flux[b * ldF + (int64_t)t * nx_c + j] = (float)(sb / (double)S_sub);
+      }
+    }
+  }
+  if (!state_final) return;
+#pragma unroll
+  for (int i = 0; i < V; ++i) {
+    const int cell = lane + 64 * i;
+    state_final[a * S + cell] = na[i];
+    state_final[a * S + N + cell] = ua[i];
+    state_final[a * S + 2 * N + cell] = Ea[i];
+    if (two) {
+      state_final[b * S + cell] = nb[i];
+      state_final[b * S + N + cell] = ub[i];
+      state_final[b * S + 2 * N + cell] = Eb[i];
+    }
+  }
+}
+
+// fv_run_small_kernel (nx_f <= 64, lane = cell) with the coarse-graining
+// inside; every step is its arithmetic in its order.  Lanes past nx_f carry
+// zeros through the shuffles (r | nx_f: a group of r lanes is on or off whole).
+__global__ __launch_bounds__(kFvThreads) void fv_run_coarse_small_kernel(const float *state0, float *state_final,
+                                                                         float *traj, const double *__restrict__ pc,
+                                                                         int nx, float c, float dt, float nu, float dx2,
+                                                                         float *flux, int B, int T_c, int r, int S_sub,
+                                                                         int tri) {
+  __shared__ double s_c[kFvSmallMaxNx];
+  __shared__ float s_rho[kFvThreads / 64][kFvSmallMaxNx];
+  __shared__ double s_psi[kFvThreads / 64][kFvSmallMaxNx];  // tri: the wave's cyclic-reduction row
+  if (!tri) {
+    for (int i = threadIdx.x; i < nx; i += kFvThreads) s_c[i] = pc[i];
+    __syncthreads();
+  }
+  const double h = tri ? pc[0] : 0.0;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), i = threadIdx.x & 63;  // wave-uniform
+  const int64_t b = (int64_t)blockIdx.x * (kFvThreads / 64) + wave;
+  if (b >= B) return;  // a whole wave; nothing below synchronises the workgroup
+  const int nx_c = nx / r;
+  const int64_t S = 3LL * nx, ldT = (int64_t)(T_c + 1) * 3 * nx_c, ldF = (int64_t)T_c * nx_c;
+  const bool on = i < nx, lead = on && (i & (r - 1)) == 0, last = on && (i & (r - 1)) == r - 1;
+  const int im = i == 0 ? nx - 1 : i - 1, ip = i >= nx - 1 ? 0 : i + 1;
+  float n = on ? state0[b * S + i] : 0.f, u = on ? state0[b * S + nx + i] : 0.f,
+        E = on ? state0[b * S + 2 * nx + i] : 0.f;
+  float *rho = s_rho[wave];
+  for (int t = 0; t <= T_c; ++t) {
+    if (t > 0) {
+      double acc = 0.0;
+      for (int s = 0; s < S_sub; ++s) {
+        const float F = __fmul_rn(n, u);  // F_n = n*u (:70-71)
+        acc += (double)F;
+        const float um = __shfl(u, im, 64), up = __shfl(u, ip, 64), Fm = __shfl(F, im, 64);
+        const float n_new = continuity(n, F, Fm, c);
+        const float u_new = velocity_classical(u, um, up, E, c, dt, nu, dx2);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the previous step's rho reads are done
+        if (tri) {
+          if (on) s_psi[wave][i] = (double)__fsub_rn(n_new, 1.0f);
+        } else if (on) {
+          rho[i] = __fsub_rn(n_new, 1.0f);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // every lane's rho is in LDS
+        if (tri) tridiag_psi_wave<double>(s_psi[wave], nx, i);
+        const float E_new = !on ? 0.f : tri ? (float)tri_E(s_psi[wave], i, nx, h) : poisson_cell(rho, s_c, i, nx);
+        n = n_new;
+        u = u_new;
+        E = E_new;
+      }
+      if (flux && last) flux[b * ldF + (int64_t)(t - 1) * nx_c + i / r] = (float)(acc / (double)S_sub);
+    }
+    if (traj) {
+      const float mn = box_mean(n, r), mu = box_mean(u, r), mE = box_mean(E, r);
+      if (lead) {
+        float *row = traj + b * ldT + (int64_t)t * 3 * nx_c;
+        row[i / r] = mn;
+        row[nx_c + i / r] = mu;
+        row[2 * nx_c + i / r] = mE;
+      }
+    }
+  }
+  if (on && state_final) {
+    state_final[b * S + i] = n;
+    state_final[b * S + nx + i] = u;
+    state_final[b * S + 2 * nx + i] = E;
+  }
+}
+
 // hf_poisson at FFT sizes: one wave per pair of ICs, as above.
 template <int N>
 __global__ __launch_bounds__(64 * kFftWaves, N >= 2048 ? 1 : 2) void poisson_fft_kernel(const float *__restrict__ n, int ld_n,
@@ -811,6 +1084,61 @@ hipError_t launch_fv_run(const float *state0, int64_t ld_s0, float *state_final,
     case 256: return fv_run_fft_launch_pm<256>(state0, ld_s0, state_final, traj, pc, B, T, c, dt, nu, dx2, flux_traj, metrics, ref, mse, pm, s);
     case 512: return fv_run_fft_launch_pm<512>(state0, ld_s0, state_final, traj, pc, B, T, c, dt, nu, dx2, flux_traj, metrics, ref, mse, pm, s);
     case 1024: return fv_run_fft_launch_pm<1024>(state0, ld_s0, state_final, traj, pc, B, T, c, dt, nu, dx2, flux_traj, metrics, ref, mse, pm, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+hipError_t launch_coarsen_state(const float *tf, int64_t ld_f, float *tc, int64_t ld_c, int B, int rows, int nx_f,
+                                int r, int S, int64_t t0, int64_t row0, hipStream_t s) {
+  const int64_t blocks = (int64_t)B * rows * 3;
+  if (blocks <= 0) return hipSuccess;
+  if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(coarsen_state_kernel, dim3((unsigned)blocks), dim3(kFvThreads), 0, s, tf, ld_f, tc, ld_c, rows,
+                     nx_f, r, S, t0, row0);
+  return hipGetLastError();
+}
+
+hipError_t launch_coarsen_flux(const float *ff, int64_t ld_f, float *fc, int64_t ld_c, int B, int rows, int nx_f, int r,
+                               int S, int64_t t0, int64_t row0, hipStream_t s) {
+  const int64_t blocks = (int64_t)B * rows;
+  if (blocks <= 0) return hipSuccess;
+  if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(coarsen_flux_kernel, dim3((unsigned)blocks), dim3(kFvThreads), 0, s, ff, ld_f, fc, ld_c, rows,
+                     nx_f, r, S, t0, row0);
+  return hipGetLastError();
+}
+
+template <int N>
+hipError_t fv_run_coarse_fft_launch(const float *state0, float *state_final, float *traj, const double *pc, int B,
+                                    int T_c, int r, int S, float c, float dt, float nu, float dx2, float *flux, int pm,
+                                    hipStream_t s) {
+  const unsigned grid = (unsigned)((B + 2 * kFftWaves - 1) / (2 * kFftWaves));
+  if (pm == HF_POISSON_TRIDIAG)
+    hipLaunchKernelGGL((fv_run_coarse_fft_kernel<N, true>), dim3(grid), dim3(64 * kFftWaves), 0, s, state0, state_final,
+                       traj, pc, c, dt, nu, dx2, flux, B, T_c, r, S);
+  else
+    hipLaunchKernelGGL((fv_run_coarse_fft_kernel<N, false>), dim3(grid), dim3(64 * kFftWaves), 0, s, state0,
+                       state_final, traj, pc, c, dt, nu, dx2, flux, B, T_c, r, S);
+  return hipGetLastError();
+}
+
+hipError_t launch_fv_run_coarse(const float *state0, float *state_final, float *traj, const double *pc, int B, int nx_f,
+                                int T_c, int r, int S, float c, float dt, float nu, float dx2, float *flux, int pm,
+                                hipStream_t s) {
+  if (B <= 0) return hipSuccess;
+  if (!poisson_mode_ok(pm, nx_f) || !fv_run_fused(nx_f) || r < 1 || r > 64 || (r & (r - 1)) || nx_f % r || S < 1 ||
+      T_c < 0)
+    return hipErrorInvalidValue;
+  if (nx_f <= kFvSmallMaxNx) {
+    const unsigned grid = (unsigned)((B + kFvThreads / 64 - 1) / (kFvThreads / 64));
+    hipLaunchKernelGGL(fv_run_coarse_small_kernel, dim3(grid), dim3(kFvThreads), 0, s, state0, state_final, traj, pc,
+                       nx_f, c, dt, nu, dx2, flux, B, T_c, r, S, pm == HF_POISSON_TRIDIAG ? 1 : 0);
+    return hipGetLastError();
+  }
+  switch (nx_f) {
+    case 256: return fv_run_coarse_fft_launch<256>(state0, state_final, traj, pc, B, T_c, r, S, c, dt, nu, dx2, flux, pm, s);
+    case 512: return fv_run_coarse_fft_launch<512>(state0, state_final, traj, pc, B, T_c, r, S, c, dt, nu, dx2, flux, pm, s);
+    case 1024: return fv_run_coarse_fft_launch<1024>(state0, state_final, traj, pc, B, T_c, r, S, c, dt, nu, dx2, flux, pm, s);
     default: return hipErrorInvalidValue;
   }
 }

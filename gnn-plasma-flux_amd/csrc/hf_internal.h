@@ -418,6 +418,25 @@ hipError_t launch_fv_run(const float *state0, int64_t ld_s0, float *state_final,
                          int nx, int T, float c, float dt, float nu, float dx2, float *flux_traj, float *metrics,
                          const float *ref, float *mse, int pm, hipStream_t s);
 
+// Coarse-graining of a fine classical rollout (hf_coarsen_traj's definition:
+// r fine cells per coarse cell, S fine steps per coarse step).
+// launch_coarsen_state: fine rows S (t0 + k) of tf (ld_f floats per IC) ->
+// coarse rows row0 + k of tc (ld_c floats per IC), k < rows, 3 channels.
+// launch_coarsen_flux: fine steps S (t0 + k) .. + S - 1 of ff -> coarse flux
+// row row0 + k of fc.  launch_fv_run_coarse: launch_fv_run's classical rollout
+// over T_c * S fine steps at the fused sizes (fv_run_fused(nx_f)) that stores
+// only the coarse rows traj [B][T_c+1][3][nx_f/r], the coarse flux
+// [B][T_c][nx_f/r] and the fine state_final (each may be NULL; state0
+// contiguous [B][3][nx_f], may alias state_final); equal to the two launches
+// above applied to launch_fv_run's trajectory and flux, bit for bit.
+hipError_t launch_coarsen_state(const float *tf, int64_t ld_f, float *tc, int64_t ld_c, int B, int rows, int nx_f,
+                                int r, int S, int64_t t0, int64_t row0, hipStream_t s);
+hipError_t launch_coarsen_flux(const float *ff, int64_t ld_f, float *fc, int64_t ld_c, int B, int rows, int nx_f, int r,
+                               int S, int64_t t0, int64_t row0, hipStream_t s);
+hipError_t launch_fv_run_coarse(const float *state0, float *state_final, float *traj, const double *pc, int B, int nx_f,
+                                int T_c, int r, int S, float c, float dt, float nu, float dx2, float *flux, int pm,
+                                hipStream_t s);
+
 // Metrics of a state batch (used for t=0 of non-fused rollouts).
 hipError_t launch_state_metrics(const float *st, int64_t ld, int B, int nx, float *metrics,
                                 int64_t ld_metrics, hipStream_t s);

@@ -4,17 +4,21 @@ shanedirksen/gnn-plasma-flux.  Same public surface as the reference package
 build_chain_graph and the config dictionaries; plus batched device entry
 points (step_batch / run_batch), HybridEnsemble (a set of checkpoints rolled
 out in one launch), the engine module and the multi-GPU IC-sharded rollout
-driver.
+driver, and FineReference (the classical solver on a refined grid with
+substeps, coarse-grained onto the training grid in one launch: the data and
+the score behind the reference README's fine-baseline claims).
 """
 from .baseline_solver import BaselineSolver
 from .baselines import PINN, PureGNN
 from .config import ABLATION_CONFIGS, DATASET_CONFIG, EVAL_CONFIG, MODEL_CONFIG, STENCIL_RADII, TRAIN_CONFIG
+from .fine_reference import FineReference
 from .flux_gnn import FluxGNN
 from .graph_constructor import build_chain_graph, build_chain_graph_batch, chain_edge_index
 from .hybrid_solver import HybridEnsemble, HybridSolver
 
 __all__ = [
     "BaselineSolver",
+    "FineReference",
     "PureGNN",
     "PINN",
     "FluxGNN",

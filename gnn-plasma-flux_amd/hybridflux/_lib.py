@@ -111,6 +111,10 @@ SIGNATURES = {
     "hf_run_compare": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                c_void_p]),
+    "hf_coarsen_traj": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "hf_run_coarse_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
+    "hf_run_coarse": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                              c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "hf_model_set_create": (c_int, [c_void_p, c_int, POINTER(c_void_p)]),
     "hf_model_set_destroy": (None, [c_void_p]),
     "hf_model_set_size": (c_int, [c_void_p]),

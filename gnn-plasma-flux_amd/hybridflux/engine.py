@@ -296,6 +296,91 @@ def run(model, grid, state0, T, traj=True, flux=False, metrics=False, out=None, 
     return {"final": final, "traj": tr, "flux": fl, "metrics": me}
 
 
+def coarsen_traj(traj_f, flux_f, refine, substeps):
+    """hf_coarsen_traj: a recorded fine trajectory [B,T_f+1,3,nx_f] (and its flux
+    [B,T_f,nx_f] or None) box-averaged over `refine` cells and sampled /
+    time-averaged over `substeps` steps -> (traj_c [B,T_f/S+1,3,nx_f/r], flux_c
+    [B,T_f/S,nx_f/r] or None).  The definition hf_run_coarse equals bit for bit."""
+    require_device(traj_f, "traj")
+    if traj_f.dtype != torch.float32 or traj_f.dim() != 4 or traj_f.shape[2] != 3:
+        raise ValueError(f"traj must be float32 [B,T_f+1,3,nx_f], got {tuple(traj_f.shape)} {traj_f.dtype}")
+    traj_f = traj_f.contiguous()
+    B, T1, _, nx_f = traj_f.shape
+    r, S, T_f, dev = int(refine), int(substeps), T1 - 1, traj_f.device
+    if r < 1 or S < 1 or nx_f % r or T_f % S:
+        raise ValueError(f"refine must divide nx_f = {nx_f} and substeps T_f = {T_f}, got {refine}, {substeps}")
+    if flux_f is not None:
+        require_device(flux_f, "flux")
+        if flux_f.dtype != torch.float32 or tuple(flux_f.shape) != (B, T_f, nx_f) or flux_f.device != dev:
+            raise ValueError(f"flux must be float32 [{B},{T_f},{nx_f}] on {dev}, got {tuple(flux_f.shape)} {flux_f.dtype}")
+        flux_f = flux_f.contiguous()
+    tc = torch.empty(B, T_f // S + 1, 3, nx_f // r, device=dev)
+    fc = torch.empty(B, T_f // S, nx_f // r, device=dev) if flux_f is not None else None
+    with torch.cuda.device(dev):
+        check(lib().hf_coarsen_traj(ptr(traj_f), ptr(flux_f), B, nx_f, T_f, r, S, ptr(tc), ptr(fc), stream_of(dev)))
+    return tc, fc
+
+
+def run_coarse_workspace(B, nx_f, T_c, refine, substeps):
+    """hf_run_coarse_workspace_bytes: the scratch with which T_c coarse steps run
+    as one chunk (0 where the rollout is one launch)."""
+    n = int(lib().hf_run_coarse_workspace_bytes(B, nx_f, T_c, refine, substeps))
+    if n < 0:
+        raise ValueError(f"bad coarse workspace query (B={B}, nx_f={nx_f}, T_c={T_c}, refine={refine}, "
+                         f"substeps={substeps})")
+    return n
+
+
+COARSE_WS_CAP = 256 << 20  # run_coarse's own scratch: chunks of coarse steps that fit this (at least one step)
+
+
+def run_coarse(grid_f, state0, T_c, refine, substeps, traj=True, flux=False, final=False, ws=None):
+    """hf_run_coarse: the classical rollout of the FINE grid `grid_f` over T_c *
+    substeps fine steps from fine states [B,3,nx_f], coarse-grained as it runs.
+    Returns dict(traj [B,T_c+1,3,nx_f/r] | None, flux [B,T_c,nx_f/r] | None,
+    final_fine [B,3,nx_f] | None).  ws: a preallocated uint8 workspace (the
+    sequenced path runs the chunks of coarse steps that fit it)."""
+    state0 = _state(state0, grid_f.nx)
+    B, dev, nx_f = state0.shape[0], state0.device, grid_f.nx
+    T_c, r, S = int(T_c), int(refine), int(substeps)
+    if not (traj or flux or final):
+        raise ValueError("run_coarse: ask for at least one of traj, flux, final")
+    one = run_coarse_workspace(B, nx_f, min(T_c, 1), r, S)  # validates B, nx_f, r, S, T_c >= 0
+    if T_c < 0:
+        raise ValueError("run_coarse: T_c must be >= 0")
+    nx_c = nx_f // r
+    tr = torch.empty(B, T_c + 1, 3, nx_c, device=dev) if traj else None
+    fl = torch.empty(B, T_c, nx_c, device=dev) if flux else None
+    fin = torch.empty_like(state0) if final else None
+    if ws is None and one > 0:
+        ws = torch.empty(max(one, min(run_coarse_workspace(B, nx_f, T_c, r, S), COARSE_WS_CAP)), dtype=torch.uint8,
+                         device=dev)
+    wb = ws.numel() * ws.element_size() if ws is not None else 0
+    _, plan = grid_f.on(dev)
+    with torch.cuda.device(dev):
+        check(lib().hf_run_coarse(ptr(state0), ptr(fin), ptr(plan), grid_f.pmode, B, nx_f, T_c, r, S, grid_f.c32,
+                                  grid_f.dt32, grid_f.nu32, grid_f.dx2_32, ptr(tr), ptr(fl), ptr(ws), wb,
+                                  stream_of(dev)))
+    return {"traj": tr, "flux": fl, "final_fine": fin}
+
+
+def poisson_traj(grid, traj):
+    """Overwrites the E rows of a trajectory [B,T1,3,nx] in place with
+    poisson(grid, its n rows): one strided hf_poisson_ex call over all B*T1 rows."""
+    require_device(traj, "traj")
+    if traj.dtype != torch.float32 or traj.dim() != 4 or traj.shape[2] != 3 or traj.shape[3] != grid.nx \
+            or not traj.is_contiguous():
+        raise ValueError(f"traj must be contiguous float32 [B,T1,3,{grid.nx}], got {tuple(traj.shape)} {traj.dtype}")
+    rows, nx = traj.shape[0] * traj.shape[1], grid.nx
+    if rows:
+        _, pc = grid.on(traj.device)
+        base = traj.data_ptr()
+        with torch.cuda.device(traj.device):
+            check(lib().hf_poisson_ex(c_void_p(base), 3 * nx, c_void_p(base + 8 * nx), 3 * nx, ptr(pc), grid.pmode,
+                                      rows, nx, stream_of(traj.device)))
+    return traj
+
+
 def run_compare(model, grid, state0, T, metrics=True, out=None, ws=None):
     """Hybrid rollout and its classical twin from the same ICs, scored per step
     (scripts/evaluation/evaluate_multi_ic.py:21-94).  Returns dict(final,

@@ -8,6 +8,7 @@ hf_rollout_summary), so a sharded multi-GPU job can gather them.
   multi_ic_mse(solver, states0, n_steps)      scripts/evaluation/evaluate_multi_ic.py:21-94
   long_rollout(solver, states0, n_steps)      scripts/evaluation/evaluate_long_rollout.py:18-81
   compare_models(models, states0, n_steps)    scripts/evaluation/evaluate_multi_ic.py:97-136
+  compare_to_fine(solver, fine_ref, ...)      no counterpart: the score against a fine reference
 
 `solver` is a HybridSolver, a HybridEnsemble (every result then carries a
 leading model axis) or a ModelRollout, the adapter that gives the
@@ -137,6 +138,30 @@ def multi_ic_mse(solver, states0, n_steps):
     summ, _ = engine.rollout_summary(r["metrics"], r["mse"], r["metrics_classical"])
     d = summary_dict(summ)
     return d["mean_mse"], r, d
+
+
+def compare_to_fine(solver, fine_ref, fine_states0, n_steps):
+    """A solver scored against the FINE reference instead of its same-dt/dx
+    classical twin (the reference README's "matches fine-step baseline on
+    coarse grid"): `solver` (anything with run_batch(states [B,3,nx], n_steps,
+    traj=True): HybridSolver, ModelRollout, BaselineSolver) is rolled out from
+    fine_ref.restrict(fine_states0), the FineReference from fine_states0, and
+    the two coarse trajectories are scored with traj_mse / traj_metrics.
+    Returns compare_batch's dict (final, mse [B,T+1,3], metrics,
+    metrics_classical = the fine reference's), so summary_dict and everything
+    downstream take it unchanged.  The solver's nx, length and dt must be the
+    reference's coarse ones (ValueError); a HybridEnsemble is not supported."""
+    if isinstance(solver, HybridEnsemble):
+        raise ValueError("compare_to_fine: a HybridEnsemble is not supported; score its solvers one by one")
+    g, c = solver.grid, fine_ref.coarse.grid
+    for k in ("nx", "length", "dt"):
+        if getattr(g, k) != getattr(c, k):
+            raise ValueError(f"compare_to_fine: the solver's {k} = {getattr(g, k)} is not the fine reference's coarse "
+                             f"{k} = {getattr(c, k)}")
+    r = solver.run_batch(fine_ref.restrict(fine_states0), n_steps, traj=True)
+    ref = fine_ref.run_batch(fine_states0, n_steps, traj=True)["traj"]
+    return {"final": r["final"], "mse": engine.traj_mse(r["traj"], ref), "metrics": engine.traj_metrics(r["traj"]),
+            "metrics_classical": engine.traj_metrics(ref)}
 
 
 def long_rollout(solver, states0, n_steps, drift=True):

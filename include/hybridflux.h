@@ -922,6 +922,67 @@ int hf_run_ex(hf_model_t model, const float *dev_state0, float *dev_state_final,
               void *dev_workspace, int64_t workspace_bytes, void *stream);
 
 /*
+ * Coarse-grained fine classical rollouts: the "fine reference" of the
+ * reference README's claims ("matches fine-step baseline on coarse grid",
+ * "larger time steps (2-5x)"), which neither scripts/training/generate_data.py
+ * nor the evaluation scripts can produce: they run the classical solver on the
+ * training grid at the training step.  Here the classical solver runs on
+ * refine (r) x the cells with substeps (S) x smaller steps, and its states and
+ * face fluxes are reduced to the coarse grid (nx = nx_f / r, dt = S dt_f).
+ *
+ * hf_coarsen_traj is the definition.  From a recorded fine trajectory
+ * dev_traj_f [B][T_f+1][3][nx_f] and (optionally, both or neither) the fine
+ * flux dev_flux_f [B][T_f][nx_f], with T_c = T_f / S (T_f % S == 0):
+ *   dev_traj_c [B][T_c+1][3][nx_f/r]: for each of n, u, E the value
+ *     (float)(tree / r), tree the ADJACENT PAIRWISE float64 sum of the r
+ *     float32 cells r j .. r j + r - 1 of fine row S t_c (level 1 adds cells
+ *     (2m, 2m+1), level 2 adds those sums pairwise, ...);
+ *   dev_flux_c [B][T_c][nx_f/r]: (float)(acc / S), acc the float64 sum, in
+ *     ascending substep order from 0.0, of the fine F at cell r j + r - 1 (the
+ *     right face of coarse cell j; F_i = n_i u_i is the flux through face
+ *     i + 1/2) over fine steps S t_c .. S t_c + S - 1; a float64 division.
+ * r = 1 copies the states bit for bit.  The time-averaged flux is the flux a
+ * coarse finite-volume step needs to be exact:
+ *   nbar_j' = nbar_j - (dt/dx) (Fbar_j - Fbar_{j-1}),  dt = S dt_f, dx = r dx_f,
+ * holds to rounding ((3 S + 4) float32 ulps of max|n| + 2 c_f max|F|).
+ * refine: a power of two in 1..64 that divides nx_f; substeps >= 1.
+ *
+ * hf_run_coarse is hf_coarsen_traj(hf_run_ex(model = NULL, traj, flux)) bit
+ * for bit, without the fine trajectory in HBM.  c, dt, nu, dx2, dev_plan and
+ * poisson_mode are the FINE grid's (c = f32(dt_f/dx_f), ...); dev_state0 is
+ * fine [B][3][nx_f].  Outputs, each may be NULL but not all three:
+ *   dev_traj  [B][T_c+1][3][nx_f/r]  coarse, row 0 = the coarsened IC;
+ *   dev_flux  [B][T_c][nx_f/r]       coarse;
+ *   dev_state_final [B][3][nx_f]     FINE, so a rollout can be continued (may
+ *                                    alias dev_state0).
+ * Where hf_run is one launch (nx_f <= 64 and nx_f in {256, 512, 1024}) so is
+ * this: the fine states stay in registers, a coarse cell's r fine cells sit
+ * in r adjacent lanes, the box sum is an xor butterfly over lane distances
+ * 1 .. r/2 in float64 (exactly the pairwise tree), and only coarse rows and
+ * fluxes are stored, every S steps; no workspace.  Any other nx_f sequences
+ * hf_run_ex over chunks of coarse steps into the workspace and coarsens each
+ * chunk; the result does not depend on the chunking.
+ * hf_run_coarse_workspace_bytes(B, nx_f, T_c, r, S): the bytes with which T_c
+ * coarse steps run as ONE chunk (0 on the one-launch paths, for B = 0 and for
+ * T_c = 0; -1 on bad arguments).  A call given fewer bytes runs chunks of the
+ * most coarse steps whose query fits; fewer than the query at T_c = 1 is
+ * HF_EINVAL.  dev_workspace == NULL: the call allocates stream-ordered, at
+ * most 256 MiB (but always one coarse step's worth).
+ * HF_EINVAL, before any device call: refine not a power of two in 1..64 or
+ * not dividing nx_f, substeps < 1, T_c < 0 (T_f % substeps != 0), no output
+ * requested, a workspace too small.  B = 0 and T_c = 0 are HF_OK (row 0 is
+ * written).  Both Poisson modes, as hf_run_ex.
+ */
+int hf_coarsen_traj(const float *dev_traj_f, const float *dev_flux_f /* or NULL */, int B, int nx_f, int T_f,
+                    int refine, int substeps, float *dev_traj_c, float *dev_flux_c /* or NULL */, void *stream);
+int64_t hf_run_coarse_workspace_bytes(int B, int nx_f, int T_c, int refine, int substeps);
+int hf_run_coarse(const float *dev_state0, float *dev_state_final /* or NULL */, const double *dev_plan,
+                  int poisson_mode, int B, int nx_f, int T_c, int refine, int substeps,
+                  float c, float dt, float nu, float dx2,
+                  float *dev_traj /* or NULL */, float *dev_flux /* or NULL */,
+                  void *dev_workspace, int64_t workspace_bytes, void *stream);
+
+/*
  * Hybrid rollout scored against the classical solver from the same ICs, in
  * one pass (replaces the serial per-IC loop of
  * scripts/evaluation/evaluate_multi_ic.py:21-94: BaselineSolver.step from
