@@ -130,7 +130,10 @@ def test_chain_training_path_vs_oracle(hf, nx, B, layers, hidden, kinkfree):
     gradients of the fused path run on wgrad_stencil_kernel for nx in {32, 64}
     (32-cell stages with the chain's halo rows: nx = 32 wraps at both ends of
     every stage; 301 chains of 64 leave a last split of two stages) and on
-    tgemm_batch for nx in {16, 48}."""
+    tgemm_batch for nx in {16, 48}.  These shapes give every split one stage
+    and every persistent kernel one pass: the multi-stage splits, the later
+    fused passes, the edge kernels' trips and the reductions' slices are in
+    tests/chain_regimes.py and run in test_gpu_chain_regimes.py."""
     rng = np.random.default_rng(nx * 100 + layers)
     if kinkfree:
         u = lambda a, shape: rng.uniform(-a, a, shape)  # noqa: E731
