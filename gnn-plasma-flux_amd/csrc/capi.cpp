@@ -36,10 +36,15 @@ int fail_hip(hipError_t e, const char *what) {
 
 struct hf_model {
   int in_dim = 0, hidden = 0, layers = 0, wdtype = 0;
+  int radius = 1;         // stencil radius of the fused chain kernels' neighbour mean (hf_model_create_ex)
   bool chain_ok = false;  // fused chain kernels need in_dim 4, hidden 128, f32
   float *dev = nullptr;   // single device allocation holding every buffer
   hf::ChainW chain{};
   hf::GraphW graph{};
+  // radius > 1: the model's own radius chain graph on the generic kernels
+  // (hf_graph_flux_radius): w_l with W_b as float32(w / (2R)), the neighbour sum
+  // in place of the mean -- the fused kernels' arithmetic
+  hf::GraphW graph_folded{};
 };
 
 // M models of one wdtype and the device table of their ChainW (hf_run_set's
@@ -121,7 +126,7 @@ void put(std::vector<unsigned char> &out, T v) {
   out.insert(out.end(), b, b + sizeof(T));
 }
 
-void pack_chain(const float *p, int L, int prec, ChainPack &P) {
+void pack_chain(const float *p, int L, int prec, ChainPack &P, int radius = 1) {
   using hf::kH;
   using hf::kKS;
   using hf::kNT;
@@ -141,9 +146,11 @@ void pack_chain(const float *p, int L, int prec, ChainPack &P) {
               const int s = 4 * gi + (j >> 1), nt = 4 * (j & 1) + cc;
               const int k = (s < kKS ? 0 : kH) + kperm(s % kKS, lane);
               v = layer_w(l)[(int64_t)(16 * nt + (lane & 15)) * 2 * kH + k];
-              // the 1/deg = 1/2 of the mean aggregation is folded into W_b (an exact
-              // power-of-two scaling: w*(s/2) == (w/2)*s bit for bit)
-              if (s >= kKS) v *= 0.5f;
+              // the 1/deg = 1/(2R) of the mean aggregation is folded into W_b, a true
+              // division.  R = 1, 2: an exact power-of-two scaling, w*(s/2) == (w/2)*s
+              // bit for bit (and w / 2.0f == w * 0.5f); R = 3 rounds each weight
+              // once instead of each mean
+              if (s >= kKS) v = v / (float)(2 * radius);
             } else {
               const int r = c - 16 * L, ot = r / 2, hh = r % 2;
               const int s = 16 * hh + 2 * j + (cc >> 1), pq = cc & 1;
@@ -229,6 +236,14 @@ int check_device() {
   return HF_OK;
 }
 
+// A radius-R chain graph needs nx >= 2R + 1 cells, or an edge repeats.  (R = 1
+// models take every nx they took before the radius existed.)
+int radius_nx_ok(const hf_model *m, int nx, const char *fn) {
+  if (m->radius > 1 && nx < 2 * m->radius + 1)
+    return fail(HF_EINVAL, std::string(fn) + ": a model of stencil radius R needs nx >= 2R + 1");
+  return HF_OK;
+}
+
 int chain_usable(const hf_model *m) {
   if (!m->chain_ok)
     return fail(HF_EUNSUPPORTED,
@@ -271,6 +286,29 @@ int64_t hf_model_param_count(int in_dim, int hidden, int layers) {
 
 int hf_model_create(const float *host_params, int in_dim, int hidden, int layers, int wdtype,
                     hf_model_t *out) {
+  return hf_model_create_ex(host_params, in_dim, hidden, layers, wdtype, 1, out);
+}
+
+int hf_model_radius(hf_model_t m) { return m ? m->radius : 0; }
+
+int64_t hf_chain_pack_host(const float *host_params, int layers, int wdtype, int radius, void *stream_out,
+                           int64_t stream_bytes) {
+  if (layers < 0 || layers > hf::kMaxChainLayers || radius < 1 || radius > 3) return -1;
+  if (wdtype != HF_WDTYPE_F32 && wdtype != HF_WDTYPE_BF16 && wdtype != HF_WDTYPE_F16X3) return -1;
+  if (radius > 1 && wdtype != HF_WDTYPE_F32) return -1;
+  const int64_t need = (int64_t)hf::chain_chunks(layers, wdtype) * hf::chain_chunk_bytes(wdtype) +
+                       (wdtype == HF_WDTYPE_BF16 ? hf::kBF16StreamTail : 0);
+  if (!stream_out) return need;
+  if (!host_params || stream_bytes < need) return -1;
+  ChainPack pk;
+  pack_chain(host_params, layers, wdtype, pk, radius);
+  if ((int64_t)pk.stream.size() != need) return -1;
+  std::memcpy(stream_out, pk.stream.data(), pk.stream.size());
+  return need;
+}
+
+int hf_model_create_ex(const float *host_params, int in_dim, int hidden, int layers, int wdtype, int radius,
+                       hf_model_t *out) {
   if (!out) return fail(HF_EINVAL, "hf_model_create: out is NULL");
   *out = nullptr;
   if (!host_params) return fail(HF_EINVAL, "hf_model_create: host_params is NULL");
@@ -278,6 +316,14 @@ int hf_model_create(const float *host_params, int in_dim, int hidden, int layers
     return fail(HF_EINVAL, "hf_model_create: dimensions must be positive");
   if (wdtype != HF_WDTYPE_F32 && wdtype != HF_WDTYPE_BF16 && wdtype != HF_WDTYPE_F16X3)
     return fail(HF_EINVAL, "hf_model_create: unknown wdtype");
+  if (radius < 1 || radius > 3) return fail(HF_EINVAL, "hf_model_create: stencil radius must be 1, 2 or 3");
+  const bool chain_ok = in_dim == hf::kIn && hidden == hf::kH && layers <= hf::kMaxChainLayers;
+  if (radius > 1 && wdtype != HF_WDTYPE_F32)
+    return fail(HF_EUNSUPPORTED, "hf_model_create: a stencil radius > 1 runs on the float32 core only");
+  if (radius > 1 && !chain_ok)
+    return fail(HF_EUNSUPPORTED,
+                "hf_model_create: a stencil radius > 1 needs a chain-capable model (FluxGNN input_dim 4, hidden_dim "
+                "128, num_layers <= 8); a wider graph goes through hf_graph_flux");
   if (int rc = check_device()) return rc;
 
   const Layout lay(in_dim, hidden, layers);
@@ -286,11 +332,12 @@ int hf_model_create(const float *host_params, int in_dim, int hidden, int layers
   m->hidden = hidden;
   m->layers = layers;
   m->wdtype = wdtype;
-  m->chain_ok = (in_dim == hf::kIn && hidden == hf::kH && layers <= hf::kMaxChainLayers);
+  m->radius = radius;
+  m->chain_ok = chain_ok;
 
   // natural copy (graph path) followed by the packed copy (chain path)
   ChainPack pk;
-  if (m->chain_ok) pack_chain(host_params, layers, wdtype, pk);
+  if (m->chain_ok) pack_chain(host_params, layers, wdtype, pk, radius);
   // natural layer weights are split into contiguous [L][H][2H] and [L][H]
   std::vector<float> nat((size_t)lay.total);
   {
@@ -310,6 +357,16 @@ int hf_model_create(const float *host_params, int in_dim, int hidden, int layers
     put(lay.b_e, hidden);
     put(lay.w_2, hidden);
     put(lay.b_2, 1);
+    if (radius > 1) {  // + the update layers once more, [L][H][2H], W_b / (2R)
+      nat.resize((size_t)lay.total + (size_t)layers * hidden * 2 * hidden);
+      for (int l = 0; l < layers; ++l) {
+        const float *src = host_params + lay.w_l + (int64_t)l * ((int64_t)hidden * 2 * hidden + hidden);
+        float *dst = nat.data() + lay.total + (int64_t)l * hidden * 2 * hidden;
+        for (int64_t r = 0; r < hidden; ++r)
+          for (int64_t k = 0; k < 2 * hidden; ++k)
+            dst[r * 2 * hidden + k] = k < hidden ? src[r * 2 * hidden + k] : src[r * 2 * hidden + k] / (float)(2 * radius);
+      }
+    }
   }
   const size_t nat_bytes = (sizeof(float) * nat.size() + 255) & ~size_t(255);
   const size_t stream_bytes = (pk.stream.size() + 255) & ~size_t(255);
@@ -349,6 +406,11 @@ int hf_model_create(const float *host_params, int in_dim, int hidden, int layers
     g.b_e = d + o; o += hidden;
     g.w_2 = d + o; o += hidden;
     g.b_2 = d + o;
+    m->graph_folded = g;
+    if (radius > 1) {
+      m->graph_folded.w_l = d + lay.total;
+      m->graph_folded.agg_sum = 1;
+    }
   }
   if (m->chain_ok) {
     const float *d = reinterpret_cast<const float *>(base + nat_bytes + stream_bytes);
@@ -362,6 +424,7 @@ int hf_model_create(const float *host_params, int in_dim, int hidden, int layers
     c.w2 = d + pk.o_w2;
     c.b2 = pk.b2;
     c.layers = layers;
+    c.radius = radius;
   }
   *out = m;
   return HF_OK;
@@ -379,6 +442,7 @@ int hf_chain_flux(hf_model_t m, const float *nf, int B, int nx, float *fe, float
   if (B == 0) return HF_OK;
   if (!nf) return fail(HF_EINVAL, "hf_chain_flux: NULL node features");
   if (int rc = chain_usable(m)) return rc;
+  if (int rc = radius_nx_ok(m, nx, "hf_chain_flux")) return rc;
   if (!fe && !ff) return HF_OK;
   HF_CHECK_HIP(hf::launch_chain_flux(m->chain, nf, nullptr, 0, nullptr, B, nx, fe, ff, as_stream(stream)),
                "hf_chain_flux");
@@ -399,6 +463,20 @@ int hf_graph_flux(hf_model_t m, const float *nf, int64_t N, const int64_t *ei, i
   if (!nf || !ei || !flux || !ws) return fail(HF_EINVAL, "hf_graph_flux: NULL pointer");
   if (N > 0x7fffffffLL || E > 0x7fffffffLL) return fail(HF_EUNSUPPORTED, "hf_graph_flux: > 2^31 nodes/edges");
   HF_CHECK_HIP(hf::launch_graph_flux(m->graph, nf, N, ei, E, flux, ws, as_stream(stream)), "hf_graph_flux");
+  return HF_OK;
+}
+
+int hf_graph_flux_radius(hf_model_t m, const float *nf, int B, int nx, const int64_t *ei, float *flux, void *ws,
+                         void *stream) {
+  if (!m) return fail(HF_EINVAL, "hf_graph_flux_radius: NULL model");
+  if (B < 0 || nx < 1) return fail(HF_EINVAL, "hf_graph_flux_radius: need B >= 0 and nx >= 1");
+  if (int rc = radius_nx_ok(m, nx, "hf_graph_flux_radius")) return rc;
+  if (B == 0) return HF_OK;
+  if (!nf || !ei || !flux || !ws) return fail(HF_EINVAL, "hf_graph_flux_radius: NULL pointer");
+  const int64_t N = (int64_t)B * nx, E = 2 * m->radius * N;
+  if (E > 0x7fffffffLL) return fail(HF_EUNSUPPORTED, "hf_graph_flux_radius: > 2^31 edges");
+  HF_CHECK_HIP(hf::launch_graph_flux(m->graph_folded, nf, N, ei, E, flux, ws, as_stream(stream)),
+               "hf_graph_flux_radius");
   return HF_OK;
 }
 
@@ -1419,6 +1497,7 @@ int hf_step_ex(hf_model_t m, const float *in, float *out, const float *x, const 
   }
   if (!x) return fail(HF_EINVAL, "hf_step: NULL x");
   if (int rc = chain_usable(m)) return rc;
+  if (int rc = radius_nx_ok(m, nx, "hf_step")) return rc;
   if (fused_nx(nx)) {
     hf::RolloutExtras ex;
     ex.poisson = pm;
@@ -1455,6 +1534,7 @@ int hf_run_ex(hf_model_t m, const float *state0, float *state_final, const float
   if (m && !x) return fail(HF_EINVAL, "hf_run: NULL x");
   if (m) {
     if (int rc = chain_usable(m)) return rc;
+    if (int rc = radius_nx_ok(m, nx, "hf_run")) return rc;
   }
   hipStream_t s = as_stream(stream);
   const int64_t S = 3LL * nx;  // floats per state
@@ -1694,6 +1774,7 @@ int hf_run_compare_ex(hf_model_t m, const float *state0, float *state_final, con
   if (B == 0) return HF_OK;
   if (!state0 || !state_final || !pc || !x || !mse) return fail(HF_EINVAL, "hf_run_compare: NULL pointer");
   if (int rc = chain_usable(m)) return rc;
+  if (int rc = radius_nx_ok(m, nx, "hf_run_compare")) return rc;
   hipStream_t s = as_stream(stream);
   if (fused_nx(nx)) {
     hf::RolloutExtras ex;
@@ -1767,6 +1848,8 @@ int hf_model_set_create(const hf_model_t *models, int M, hf_model_set_t *out) {
     if (!models[i]) return fail(HF_EINVAL, "hf_model_set_create: NULL model in the set");
     if (models[i]->wdtype != models[0]->wdtype)
       return fail(HF_EINVAL, "hf_model_set_create: the models of a set share one wdtype");
+    if (models[i]->radius != models[0]->radius)
+      return fail(HF_EUNSUPPORTED, "hf_model_set_create: the models of a set share one stencil radius");
     if (!models[i]->chain_ok)
       return fail(HF_EUNSUPPORTED,
                   "hf_model_set_create: a set takes chain-capable models only (FluxGNN input_dim 4, hidden_dim 128)");
@@ -1827,6 +1910,7 @@ int check_set_call(const char *fn, hf_model_set_t set, const float *state0, int6
   if (model_stride == 0 && state0 && state0 == state_final)
     return fail(HF_EINVAL, f + ": state_final may alias state0 only with ICs per model (model_stride != 0)");
   if (!set) return fail(HF_EINVAL, f + ": NULL model set");
+  if (int rc = radius_nx_ok(set->models[0], nx, fn)) return rc;
   if (int rc = check_mode(pm, nx, fn)) return rc;
   if ((int64_t)set->models.size() * B > std::numeric_limits<int>::max())
     return fail(HF_EINVAL, f + ": M*B exceeds the int range");
@@ -1839,7 +1923,7 @@ int check_set_call(const char *fn, hf_model_set_t set, const float *state0, int6
 }
 
 hf::ChainSet chain_set(const hf_model_set *set, int64_t model_stride) {
-  return hf::ChainSet{set->table, (int)set->models.size(), set->wdtype, model_stride};
+  return hf::ChainSet{set->table, (int)set->models.size(), set->wdtype, model_stride, set->models[0]->radius};
 }
 
 }  // namespace

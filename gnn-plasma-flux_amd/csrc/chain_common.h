@@ -103,6 +103,59 @@ __device__ __forceinline__ void nb_sum(const float (&v)[MT], float (&s)[MT]) {
   }
 }
 
+// Value of cell m+S (S of either sign, |S| < 16) for every lane: left_nb /
+// right_nb generalised to a shift by S.  In the interleaved layout cell
+// MT*j + mt + S is tile t = (mt + S) mod MT of lane column j + q, q =
+// floor((mt + S) / MT): the same lane of tile t (q = 0) or a row rotation of it
+// (row_ror:n moves column j - n to column j, so column j + q is row_ror:(-q mod 16)),
+// which at nx = 16*MT is also exactly the periodic wrap.
+template <int MT, int S, int I = 0>
+__device__ __forceinline__ void shift_nb(const float (&v)[MT], float (&o)[MT]) {
+  if constexpr (I < MT) {
+    constexpr int t = ((I + S) % MT + MT) % MT, q = (I + S - t) / MT;
+    static_assert(q > -16 && q < 16, "one row of 16 lane columns");
+    if constexpr (q == 0) o[I] = v[t];
+    else o[I] = dpp_zero<0x120 + ((16 - q) & 15)>(v[t]);
+    shift_nb<MT, S, I + 1>(v, o);
+  }
+}
+
+// The radius-RAD neighbour sum of every cell (RAD = 2, 3; nb_sum is RAD = 1), in
+// the one order the radius graph's edge list fixes (a sequential index_add_
+// over it): ((((v[i+1] + v[i-1]) + v[i+2]) + v[i-2]) + v[i+3]) + v[i-3].
+// 2 RAD - 1 fp32 adds per value; the / (2 RAD) is folded into W_b.
+template <int MT, int RAD>
+__device__ __forceinline__ void nb_sum_radius(const float (&v)[MT], float (&s)[MT]) {
+  static_assert(RAD == 2 || RAD == 3, "stencil radius of the fused f32 core");
+  float p[MT], m[MT];
+  shift_nb<MT, 1>(v, p);
+  shift_nb<MT, -1>(v, m);
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) s[mt] = __fadd_rn(p[mt], m[mt]);
+  shift_nb<MT, 2>(v, p);
+  shift_nb<MT, -2>(v, m);
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) s[mt] = __fadd_rn(__fadd_rn(s[mt], p[mt]), m[mt]);
+  if constexpr (RAD == 3) {
+    shift_nb<MT, 3>(v, p);
+    shift_nb<MT, -3>(v, m);
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) s[mt] = __fadd_rn(__fadd_rn(s[mt], p[mt]), m[mt]);
+  }
+}
+
+// Stencil radius a core's neighbour sum spans: Core::kRadius where a core has
+// one (the f32 core), 1 otherwise.  A compile-time constant, so the radius-1
+// kernels are the code they were.
+template <class Core, class = void>
+struct core_radius {
+  static constexpr int value = 1;
+};
+template <class Core>
+struct core_radius<Core, std::void_t<decltype(Core::kRadius)>> {
+  static constexpr int value = Core::kRadius;
+};
+
 // Workgroup barrier that also orders this wave's LDS traffic.
 __device__ __forceinline__ void lds_barrier() {
   __builtin_amdgcn_sched_barrier(0);
@@ -587,7 +640,8 @@ __global__ __launch_bounds__(64 * Core::kNW, Core::kWGPerCU) void chain_flux_ker
   // window halo: after L message-passing layers the L cells at each window
   // edge (and the readout of the faces between them) have seen the window's
   // artificial wrap; faces [L, 62 - L] of a 64-cell window are exact
-  const int halo = W.layers, win_faces = win_faces_of(W.layers, 16 * MT);
+  // (a radius-R core: L*R cells per window edge; core_radius is 1 for every other core)
+  const int halo = W.layers * core_radius<Core>::value, win_faces = win_faces_of(halo, 16 * MT);
   const int64_t groups = (items + Core::kNW - 1) / Core::kNW;
   // item (IC b, window w) of this wave in group grp; idle waves mirror a real item and write nothing
   auto locate = [&](int64_t grp, int64_t &b, int &w) {
@@ -1312,7 +1366,8 @@ hipError_t launch_flux_windowed(const ChainW &w, const float *nf, const float *s
                                 const float *x, int B, int nx, float *fe, float *ff, hipStream_t s) {
   if (B <= 0) return hipSuccess;
   constexpr int WMT = Core::kWinMT;
-  const int faces = win_faces_of(w.layers, 16 * WMT);
+  const int faces = win_faces_of(w.layers * core_radius<Core>::value, 16 * WMT);
+  if (faces < 1) return hipErrorInvalidValue;  // (L <= 8, R <= 3 leave 15)
   const int nwin = (nx + faces - 1) / faces;
   return flux_launch<Core, WMT, false>(w, nf, state, ld_state, x, nx, nwin, (int64_t)B * nwin, fe, ff, s);
 }
@@ -1396,6 +1451,7 @@ hipError_t launch_cells_set(const ChainSet &set, const float *state0, float *sta
 // launch's rule on the launch's total (both families give the same bits).
 inline bool set_prefers_cells(const ChainSet &set, int B, int nx, const RolloutExtras &ex) {
   ChainW any{};
+  any.radius = set.radius;  // the cell-split kernels are radius 1 only
   return ex.mse == nullptr && ex.metrics_cl == nullptr && chain_rollout_prefers_cells(any, set.M * B, nx);
 }
 

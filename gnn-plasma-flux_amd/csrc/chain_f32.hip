@@ -25,8 +25,13 @@ using namespace chain;
 // (chain_common.h Ring): 2 in 4 for the IC-per-wave kernels; the cell-split
 // kernels consume a chunk in a quarter of the time (16 cells per wave) and run
 // deeper (kCellsAhead).
-template <int D = 2, int SLOTS = kRingSlots, bool LDR = false, bool DEF = false>
+// RAD = stencil radius of the neighbour mean (1: the reference's ±1 chain;
+// 2, 3: the radius graph, instantiated in chain_f32_radius.hip, which includes
+// this file's core alone).  The RAD = 1 code is the code it was.
+template <int D = 2, int SLOTS = kRingSlots, bool LDR = false, bool DEF = false, int RAD = 1>
 struct CoreF32T {
+  static_assert(RAD >= 1 && RAD <= 3, "stencil radius 1..3");
+  static constexpr int kRadius = RAD;  // window halo = layers * kRadius (chain_common.h core_radius)
   static constexpr int kNW = kWaves;   // waves sharing the weight ring
   static constexpr int kWGPerCU = 1;   // persistent flux kernel: workgroups per CU
   static constexpr int kStreamOffset = 0;  // bytes of the packed stream before chunk 0
@@ -94,14 +99,34 @@ struct CoreF32T {
         for (int mt = 0; mt < MT; ++mt) b[mt] = X.q[mt][s >> 2][s & 3];
       } else if constexpr (H::kOn) {
         static_assert(MT == 1, "cell-split waves hold 16 cells");
+        static_assert(RAD == 1, "cell-split waves trade one boundary column per layer");
         b[0] = nb_sum_halo(b[0], X.l[s >> 2][s & 3], X.r[s >> 2][s & 3]);
-      } else {
+      } else if constexpr (RAD == 1) {
         float sum[MT];
         nb_sum<MT>(b, sum);  // index_add_ of h[i+1], h[i-1]; the / deg 2 is folded into W_b
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) b[mt] = sum[mt];
+      } else {
+        float sum[MT];
+        nb_sum_radius<MT, RAD>(b, sum);  // the 2 RAD neighbours in edge-list order; / deg 2 RAD folded into W_b
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) b[mt] = sum[mt];
       }
     }
+  }
+
+  // Neighbours of a wave's MT values per k-step that are row rotations of a
+  // tile (chain_common.h shift_nb: lane column j + q, q != 0), over S = ±1..±RAD.
+  template <int MT>
+  static constexpr int rotated_nbs() {
+    int n = 0;
+    for (int r = 1; r <= RAD; ++r)
+      for (int sg = -1; sg <= 1; sg += 2)
+        for (int i = 0; i < MT; ++i) {
+          const int c = i + sg * r, t = (c % MT + MT) % MT;
+          n += (c - t) / MT != 0;
+        }
+    return n;
   }
 
   // Update-layer k-step KS (unit KS & 3 of its chunk).  b holds this k-step's
@@ -124,13 +149,28 @@ struct CoreF32T {
       for (int nt = 0; nt < kNT; ++nt) acc[mt][nt] = mfma4(a[nt >> 2][nt & 3], b[mt], acc[mt][nt]);
     __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);  // next unit's ds_reads first
     if constexpr (KS + 1 >= kKS && KS + 1 < 2 * kKS) {
-      // one VALU per m-tile for the next operand, after every other MFMA
+      if constexpr (RAD == 1) {
+        // one VALU per m-tile for the next operand, after every other MFMA
 #pragma unroll
-      for (int i = 0; i < MT; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);
+        for (int i = 0; i < MT; ++i) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+          __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);
+        }
+        __builtin_amdgcn_sched_group_barrier(0x008, MT * kNT - 2 * MT, 0);
+      } else {
+        // 2 RAD - 1 adds per m-tile for the next operand, plus a v_mov_dpp for
+        // each rotated neighbour that does not fold into its add (at most one
+        // of an add's two operands folds): kValu VALU slots, one after each
+        // MFMA, the rest of the k-step's MT * kNT MFMAs behind them
+        constexpr int kNeed = MT * (2 * RAD - 1) + rotated_nbs<MT>();
+        constexpr int kValu = kNeed < MT * kNT ? kNeed : MT * kNT;  // (MT = 1: 8 MFMAs a k-step)
+#pragma unroll
+        for (int i = 0; i < kValu; ++i) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);
+        }
+        __builtin_amdgcn_sched_group_barrier(0x008, MT * kNT - kValu, 0);
       }
-      __builtin_amdgcn_sched_group_barrier(0x008, MT * kNT - 2 * MT, 0);
     } else {
       __builtin_amdgcn_sched_group_barrier(0x008, MT * kNT, 0);
     }
@@ -364,6 +404,14 @@ struct CoreF32T {
 
 using CoreF32 = CoreF32T<2, kRingSlots, false, true>;  // IC-per-wave: deferred ring DMA (DEF)
 
+// chain_f32_radius.hip includes this file for the core above alone (the
+// radius-2 and -3 instantiations are a translation unit of their own): the
+// launchers, the cell-split core and the training kernels below stay here.
+#ifdef HF_CHAIN_F32_CORE_ONLY
+}  // namespace
+}  // namespace hf
+#else
+
 // ---------------------------------------------------------------------------
 // Cell-split small-batch kernels (chain_common.h) on the f32 core at MT = 1.
 constexpr int kCellsAhead = 4;
@@ -378,6 +426,7 @@ using CellCoreLd = CoreF32T<kCellsAhead, kCellsAhead + 1, true>;
 // kernel's time per step (plus the exchanges), against 4 ICs per workgroup.
 bool chain_rollout_prefers_cells(const ChainW &w, int B, int nx) {
   if (B <= 0 || (nx != 32 && nx != 48 && nx != 64)) return false;  // every precision has a cell-split core
+  if (w.radius > 1) return false;  // the cell-split waves trade one boundary column per layer: radius 1 only
   const int wpi = nx / 16, ipw = kWaves / wpi;
   const int64_t cus = chain::resident_groups();
   const int64_t wave_rounds = ((int64_t)B + 4 * cus - 1) / (4 * cus);
@@ -399,6 +448,7 @@ hipError_t launch_chain_rollout_cells(const ChainW &w, const float *state0, floa
 
 hipError_t launch_chain_flux_f32(const ChainW &w, const float *nf, const float *state, int64_t ld_state,
                                  const float *x, int B, int nx, float *fe, float *ff, hipStream_t s) {
+  if (w.radius > 1) return launch_chain_flux_f32_radius(w, nf, state, ld_state, x, B, nx, fe, ff, s);
   // small batches: each chain spread over nx/16 waves, as the rollout
   if (chain_rollout_prefers_cells(w, B, nx)) {
     switch (nx) {
@@ -522,6 +572,7 @@ hipError_t launch_chain_train_bwd_fused(const GraphW &w, int64_t B, int nx, floa
   cw.stream = static_cast<const float *>(bpack);
   cw.layers = w.layers;
   cw.prec = kPrecF32;
+  cw.radius = 1;
   switch (nx) {
     case 16: return train_bwd_launch<1>(cw, B, g0, gstride, mbits, dPQ, s);
     case 32: return train_bwd_launch<2>(cw, B, g0, gstride, mbits, dPQ, s);
@@ -559,6 +610,7 @@ hipError_t launch_chain_train_fwd_fused(const GraphW &w, const float *nf, int64_
   cw.b2 = 0.f;  // read from w.b_2 on the device
   cw.layers = L;
   cw.prec = kPrecF32;
+  cw.radius = 1;
   switch (nx) {
     case 16: return train_fwd_launch<1>(cw, w.b_2, nf, B, fe, h0, hstride, pq, mbits, s);
     case 32: return train_fwd_launch<2>(cw, w.b_2, nf, B, fe, h0, hstride, pq, mbits, s);
@@ -571,6 +623,9 @@ hipError_t launch_chain_train_fwd_fused(const GraphW &w, const float *nf, int64_
 hipError_t launch_chain_rollout_f32(const ChainW &w, const float *state0, float *state_final, const float *x,
                                     const double *pc, int B, int nx, int T, float c, float dt, float *traj,
                                     float *flux_traj, float *metrics, const RolloutExtras &ex, hipStream_t s) {
+  if (w.radius > 1)
+    return launch_chain_rollout_f32_radius(w, state0, state_final, x, pc, B, nx, T, c, dt, traj, flux_traj, metrics,
+                                           ex, s);
   // small batches: each IC spread over nx/16 waves (cell-split kernel)
   if (ex.mse == nullptr && ex.metrics_cl == nullptr && chain_rollout_prefers_cells(w, B, nx))
     return launch_chain_rollout_cells(w, state0, state_final, x, pc, B, nx, T, c, dt, traj, flux_traj, metrics,
@@ -582,6 +637,9 @@ hipError_t launch_chain_rollout_f32(const ChainW &w, const float *state0, float 
 hipError_t launch_chain_rollout_set_f32(const ChainSet &set, const float *state0, float *state_final, const float *x,
                                         const double *pc, int B, int nx, int T, float c, float dt, float *traj,
                                         float *flux_traj, float *metrics, const RolloutExtras &ex, hipStream_t s) {
+  if (set.radius > 1)
+    return launch_chain_rollout_set_f32_radius(set, state0, state_final, x, pc, B, nx, T, c, dt, traj, flux_traj,
+                                               metrics, ex, s);
   if (chain::set_prefers_cells(set, B, nx, ex))
     return chain::launch_cells_set<CellCoreLd>(set, state0, state_final, x, pc, B, nx, T, c, dt, traj, flux_traj,
                                                metrics, ex.poisson, s);
@@ -590,3 +648,4 @@ hipError_t launch_chain_rollout_set_f32(const ChainSet &set, const float *state0
 }
 
 }  // namespace hf
+#endif  // HF_CHAIN_F32_CORE_ONLY

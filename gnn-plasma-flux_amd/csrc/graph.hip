@@ -280,6 +280,8 @@ __global__ void sort_segments_kernel(const int *__restrict__ off, int64_t N, int
   }
 }
 
+// SUM: the neighbour sum itself (GraphW::agg_sum: the 1/deg is in the weights).
+template <bool SUM>
 __global__ void aggregate_kernel(const float *__restrict__ h, const int64_t *__restrict__ col,
                                  const int *__restrict__ off, const int *__restrict__ perm,
                                  int64_t N, int H, float *__restrict__ agg) {
@@ -290,8 +292,12 @@ __global__ void aggregate_kernel(const float *__restrict__ h, const int64_t *__r
   const int a = off[i], z = off[i + 1];
   float s = 0.f;
   for (int p = a; p < z; ++p) s = __fadd_rn(s, h[col[perm[p]] * H + f]);
-  const int deg = z - a;
-  agg[t] = __fdiv_rn(s, (float)(deg > 0 ? deg : 1));
+  if constexpr (SUM) {
+    agg[t] = s;
+  } else {
+    const int deg = z - a;
+    agg[t] = __fdiv_rn(s, (float)(deg > 0 ? deg : 1));
+  }
 }
 
 // ------------------------------------------------------------- backward pieces
@@ -458,7 +464,10 @@ hipError_t forward_core(const GraphW &w, const float *nf, int64_t N, const int64
     const int nxt = keep ? l + 1 : 1 - cur;
     float *a = keep ? agg[l] : agg[0];
     const unsigned ab = (unsigned)((N * H + 255) / 256);
-    hipLaunchKernelGGL(aggregate_kernel, dim3(ab), dim3(256), 0, s, h[cur], col, off, perm, N, H, a);
+    if (w.agg_sum)
+      hipLaunchKernelGGL(aggregate_kernel<true>, dim3(ab), dim3(256), 0, s, h[cur], col, off, perm, N, H, a);
+    else
+      hipLaunchKernelGGL(aggregate_kernel<false>, dim3(ab), dim3(256), 0, s, h[cur], col, off, perm, N, H, a);
     if ((err = linear(h[cur], H, nullptr, a, H, nullptr, wv_rows(w.w_l + l * w.lsw, H, 2 * H), w.b_l + l * w.lsb,
                       h[nxt], N, H, kActRelu, s)))
       return err;

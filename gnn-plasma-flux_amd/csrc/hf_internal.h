@@ -69,6 +69,7 @@ struct ChainW {
   float b2;
   int layers;
   int prec;             // ChainPrec
+  int radius;           // stencil radius R of the neighbour mean (1..3; > 1: f32 only); W_b is packed as w / (2R)
 };
 
 // Natural-layout float32 weights (device) for the generic-graph path.
@@ -78,6 +79,8 @@ struct GraphW {
   const float *w_e, *b_e;          // [H][2H], [H]
   const float *w_2, *b_2;          // [H], [1]
   int in_dim, hidden, layers;
+  int agg_sum;                     // 1: agg is the neighbour SUM, the 1/deg folded into w_l's W_b half by the caller
+                                   // (a radius model's own chain graph, capi.cpp); 0: the mean, sum / max(deg, 1)
   int64_t lsw, lsb;                // per-layer strides (grouped or state-dict order)
 };
 // Strided weight view for the generic MFMA GEMM (graph.hip):
@@ -199,6 +202,9 @@ hipError_t launch_chain_flux_k32(const ChainW &, const float *, const float *, i
                                  float *, float *, hipStream_t);
 hipError_t launch_chain_flux_bf16(const ChainW &, const float *, const float *, int64_t, const float *, int, int,
                                   float *, float *, hipStream_t);
+// The f32 core at stencil radius 2, 3 (chain_f32_radius.hip; launch_chain_*_f32 hand over on ChainW::radius > 1).
+hipError_t launch_chain_flux_f32_radius(const ChainW &, const float *, const float *, int64_t, const float *, int,
+                                        int, float *, float *, hipStream_t);
 // Extra outputs of the persistent rollout: a classical twin of every IC
 // stepped in the same wave (hf_run_compare), all optional.
 struct RolloutExtras {
@@ -210,7 +216,10 @@ struct RolloutExtras {
 hipError_t launch_chain_rollout_f32(const ChainW &, const float *, float *, const float *, const double *, int, int,
                                     int, float, float, float *, float *, float *, const RolloutExtras &,
                                     hipStream_t);
-// Cell-split rollout for small batches (chain_f32.hip; f32, nx in {32,48,64}, no classical twin).
+hipError_t launch_chain_rollout_f32_radius(const ChainW &, const float *, float *, const float *, const double *,
+                                           int, int, int, float, float, float *, float *, float *,
+                                           const RolloutExtras &, hipStream_t);
+// Cell-split rollout for small batches (chain_f32.hip; f32, nx in {32,48,64}, no classical twin, radius 1).
 bool chain_rollout_prefers_cells(const ChainW &, int B, int nx);
 hipError_t launch_chain_rollout_cells(const ChainW &, const float *, float *, const float *, const double *, int,
                                       int, int, float, float, float *, float *, float *, int pm, hipStream_t);
@@ -231,10 +240,14 @@ struct ChainSet {
   int M;
   int prec;
   int64_t stride0;
+  int radius;  // the models' common stencil radius
 };
 hipError_t launch_chain_rollout_set_f32(const ChainSet &, const float *, float *, const float *, const double *, int,
                                         int, int, float, float, float *, float *, float *, const RolloutExtras &,
                                         hipStream_t);
+hipError_t launch_chain_rollout_set_f32_radius(const ChainSet &, const float *, float *, const float *,
+                                               const double *, int, int, int, float, float, float *, float *,
+                                               float *, const RolloutExtras &, hipStream_t);
 hipError_t launch_chain_rollout_set_k32(const ChainSet &, const float *, float *, const float *, const double *, int,
                                         int, int, float, float, float *, float *, float *, const RolloutExtras &,
                                         hipStream_t);

@@ -39,11 +39,15 @@ SIGNATURES = {
     "hf_device_count": (c_int, []),
     "hf_model_param_count": (c_int64, [c_int, c_int, c_int]),
     "hf_model_create": (c_int, [c_void_p, c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
+    "hf_model_create_ex": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
+    "hf_model_radius": (c_int, [c_void_p]),
+    "hf_chain_pack_host": (c_int64, [c_void_p, c_int, c_int, c_int, c_void_p, c_int64]),
     "hf_model_destroy": (None, [c_void_p]),
     "hf_chain_flux": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "hf_graph_workspace_bytes": (c_int64, [c_void_p, c_int64, c_int64]),
     "hf_graph_flux": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
                               c_void_p]),
+    "hf_graph_flux_radius": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hf_graph_tape_bytes": (c_int64, [c_int, c_int, c_int, c_int64, c_int64]),
     "hf_graph_backward_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int64, c_int64]),
     "hf_graph_forward_train": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int,

@@ -1,9 +1,16 @@
 """Configuration dictionaries of the reference (src/config.py:9-79), kept with
 identical keys and values so code written against the reference reads the
 same settings.  Only MODEL_CONFIG is consumed on the hot path
-(src/hybrid_solver.py:21-26); STENCIL_RADII is a checkpoint label only — the
-graph is always the +-1 chain (src/graph_constructor.py:34-38), so every radius
-runs the same kernels with different weights.
+(src/hybrid_solver.py:21-26).  In the reference STENCIL_RADII is a checkpoint
+label only — its graph is always the +-1 chain (src/graph_constructor.py:34-38),
+so every radius is the same architecture with different weights — and that is
+what `radius` / `stencil_radius` stay here: labels.  The real stencil radius is
+the opt-in `graph_radius` of HybridSolver, training.train_model and
+training.ablation_loss (and `radius` of graph_constructor.chain_edge_index and
+engine.DeviceModel): graph_radius=R runs FluxGNN on the radius-R chain graph,
+mean over the 2R neighbours, in the same fused f32 kernels.  A sweep whose
+radii differ in more than the seed is
+`train_model(..., stencil_radius=R, graph_radius=R)` for R in STENCIL_RADII.
 """
 
 DATASET_CONFIG = dict(nx=64, num_initial_conditions=50, steps_per_ic=40, dt=5e-3, t_end=1.0, nu=1e-3)

@@ -88,12 +88,19 @@ class DeviceModel:
               it); past it the split overflows and the flux is reported
               non-finite where f32 would still be finite (tests: test_f16x3_range)
       "bf16"  bf16 weights and activations, f32 accumulate (BASELINE config 4)
-    The generic-graph path always computes in float32."""
+    The generic-graph path always computes in float32.
 
-    def __init__(self, state_dict, device, precision="f32"):
+    radius (1..3) is the stencil radius of the fused chain kernels
+    (hf_model_create_ex): the update layers' mean runs over the 2*radius
+    neighbours of the radius chain graph (graph_constructor.chain_edge_index),
+    "f32" only beyond 1.  The generic-graph path takes its graph from the
+    caller and ignores it."""
+
+    def __init__(self, state_dict, device, precision="f32", radius=1):
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(PRECISIONS)}, got {precision!r}")
         self.precision = precision
+        self.radius = int(radius)
         self.in_dim, self.hidden, self.layers = dims_of(state_dict)
         self.device = torch.device(device)
         flat = flatten_params(state_dict, self.layers)
@@ -102,8 +109,8 @@ class DeviceModel:
             raise ValueError(f"state dict has {flat.size} parameters, expected {want}")
         self.handle = c_void_p()
         with torch.cuda.device(self.device):
-            check(lib().hf_model_create(flat.ctypes.data_as(c_void_p), self.in_dim, self.hidden,
-                                        self.layers, PRECISIONS[precision], self.handle))
+            check(lib().hf_model_create_ex(flat.ctypes.data_as(c_void_p), self.in_dim, self.hidden,
+                                           self.layers, PRECISIONS[precision], self.radius, self.handle))
 
     @property
     def chain_ok(self):
@@ -139,6 +146,9 @@ class DeviceModelSet:
                 raise ValueError(f"DeviceModelSet: model {i} is on {m.device}, model 0 on {models[0].device}")
             if not m.chain_ok:
                 raise ValueError(f"DeviceModelSet: model {i} is not FluxGNN(input_dim=4, hidden_dim=128)")
+            if m.radius != models[0].radius:
+                raise ValueError(f"DeviceModelSet: model {i} has stencil radius {m.radius}, model 0 has "
+                                 f"{models[0].radius}; a set shares one radius")
         self.models = models
         self.device, self.precision = models[0].device, models[0].precision
         self.handle = c_void_p()
@@ -485,16 +495,19 @@ def run_compare_set(mset, grid, state0, T, metrics=True, out=None, ws=None):
     return {"final": final, "mse": mse, "metrics": me, "metrics_classical": mc}
 
 
-def chain_flux(model, node_features, B, nx):
-    """FluxGNN.forward on B disjoint periodic chains of nx cells -> [B*2nx]."""
+def chain_flux(model, node_features, B, nx, flux_face=False):
+    """FluxGNN.forward on B disjoint periodic chains of nx cells -> [B*2nx]
+    (a model of radius R: the first 2nx fluxes of each IC's radius-R block).
+    flux_face: also the face fluxes [B,nx] = 0.5 (fe[i] + fe[nx+i]), as (fe, ff)."""
     require_device(node_features, "node_features")
     nf = node_features.contiguous()
     if nf.dtype != torch.float32 or nf.shape != (B * nx, 4):
         raise ValueError(f"node_features must be float32 [{B * nx},4], got {tuple(nf.shape)} {nf.dtype}")
     fe = torch.empty(B * 2 * nx, device=nf.device)
+    ff = torch.empty(B, nx, device=nf.device) if flux_face else None
     with torch.cuda.device(nf.device):
-        check(lib().hf_chain_flux(model.handle, ptr(nf), B, nx, ptr(fe), None, stream_of(nf.device)))
-    return fe
+        check(lib().hf_chain_flux(model.handle, ptr(nf), B, nx, ptr(fe), ptr(ff), stream_of(nf.device)))
+    return (fe, ff) if flux_face else fe
 
 
 def graph_flux(model, node_features, edge_index):
@@ -516,6 +529,28 @@ def graph_flux(model, node_features, edge_index):
     with torch.cuda.device(nf.device):
         check(lib().hf_graph_flux(model.handle, ptr(nf), N, ptr(ei), E, ptr(flux), ptr(ws),
                                   stream_of(nf.device)))
+    return flux
+
+
+def graph_flux_radius(model, node_features, edge_index, B, nx):
+    """FluxGNN.forward of a radius-R DeviceModel on its own radius-R chain graph
+    (edge_index: graph_constructor.chain_edge_index(nx, B, radius=R), unmodified)
+    -> all [B*2*R*nx] fluxes, on the generic kernels with the fused kernels'
+    arithmetic (hf_graph_flux_radius: neighbour sums times W_b / (2R))."""
+    require_device(node_features, "node_features")
+    nf = node_features.to(torch.float32).contiguous()
+    ei = edge_index.to(device=nf.device, dtype=torch.int64).contiguous()
+    N, E = B * nx, 2 * model.radius * B * nx
+    if tuple(nf.shape) != (N, model.in_dim) or tuple(ei.shape) != (2, E):
+        raise ValueError(f"radius-{model.radius} graph of {B} x {nx} cells: node_features must be [{N},{model.in_dim}] "
+                         f"and edge_index [2,{E}], got {tuple(nf.shape)} and {tuple(ei.shape)}")
+    flux = torch.empty(E, device=nf.device)
+    if E == 0:
+        return flux
+    ws = torch.empty(int(lib().hf_graph_workspace_bytes(model.handle, N, E)), dtype=torch.uint8, device=nf.device)
+    with torch.cuda.device(nf.device):
+        check(lib().hf_graph_flux_radius(model.handle, ptr(nf), B, nx, ptr(ei), ptr(flux), ptr(ws),
+                                         stream_of(nf.device)))
     return flux
 
 

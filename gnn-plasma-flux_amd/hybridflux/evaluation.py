@@ -92,7 +92,8 @@ def ensemble_groups(models):
     """Which entries of `models` (name -> solver) compare_models rolls out
     together: lists of names, in `models`' order, of HybridSolvers that agree
     on HybridEnsemble.SIGNATURE (nx, grid constants, Poisson mode, precision,
-    device).  Groups of one, ModelRollouts and anything else are left out: they
+    device, graph radius: a 12-model sweep over three radii is three launches).
+    Groups of one, ModelRollouts and anything else are left out: they
     run on their own."""
     groups = {}
     for k, m in models.items():

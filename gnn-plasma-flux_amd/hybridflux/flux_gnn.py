@@ -10,7 +10,17 @@ change) into a device weight handle and the edge fluxes come from
     graph_constructor, or recognised by content — and the model has
     MODEL_CONFIG's width (in 4, hidden 128);
   * the generic-graph kernels (graph.hip) for any other edge_index
-    (examples/smoke_test.py:53 passes a random one) or width.
+    (examples/smoke_test.py:53 passes a random one) or width.  A radius-R
+    chain graph (graph_constructor.chain_edge_index(radius=R), R > 1) is such
+    a graph: forward() returns all its 2*R*nx fluxes per IC, the reference's
+    semantics on that edge list.  For a tagged (unmodified) radius graph and a
+    model of MODEL_CONFIG's width in f32 the no-grad forward keeps the fused
+    radius kernels' arithmetic (hf_graph_flux_radius: neighbour sums times
+    W_b / (2R), one rounding per weight) so that the module and the solver
+    share one definition; an untagged copy, and the forward under autograd,
+    form the reference's float32 mean (sum / degree), the same bits for R <= 2
+    and a rounding apart for R = 3.  The fused radius kernels compute only the
+    first 2*nx fluxes and are reached through HybridSolver(graph_radius=R).
 
 Host (CPU) tensors and a CPU-resident module — the reference's own call
 pattern (examples/smoke_test.py:50-56, src/flux_gnn.py:40-67: the flux comes
@@ -32,7 +42,7 @@ import torch.nn as nn
 
 from . import engine
 from .flat import flat_params, flatten_, split_flat
-from .graph_constructor import chain_tag, shared_chain_edge_index
+from .graph_constructor import chain_tag, chain_tag_radius, shared_chain_edge_index
 
 
 class _TrainForward(torch.autograd.Function):
@@ -82,18 +92,20 @@ class FluxGNN(nn.Module):
     def _signature(self):
         return (self.precision,) + tuple((p.data_ptr(), p._version, str(p.device)) for p in self.parameters())
 
-    def device_model(self, device):
+    def device_model(self, device, radius=1):
         """The packed libhybridflux weight handle for `device` (rebuilt when any
-        parameter changes)."""
+        parameter changes).  radius: the stencil radius of the fused chain
+        kernels (engine.DeviceModel); forward() itself always asks for 1, the
+        ±1 chain its tagged graphs are, and HybridSolver(graph_radius=R) for R."""
         device = torch.device(device)
-        key = str(device)
+        key = str(device) if radius == 1 else f"{device}/r{int(radius)}"
         sig = self._signature()
         hit = self._packed.get(key)
         if hit is None or hit[0] != sig:
             if hit is not None:
                 hit[1].close()
             sd = {k: v for k, v in self.state_dict().items()}
-            self._packed[key] = (sig, engine.DeviceModel(sd, device, self.precision))
+            self._packed[key] = (sig, engine.DeviceModel(sd, device, self.precision, radius))
         return self._packed[key][1]
 
     def flatten_parameters_(self):
@@ -141,8 +153,13 @@ class FluxGNN(nn.Module):
         dm = self.device_model(dev)
         geom = self._chain_geometry(node_features, edge_index)
         nf = node_features.to(device=dev, dtype=torch.float32)
+        rtag = chain_tag_radius(edge_index) if geom is None else None
         if geom is not None and dm.chain_ok:
             flux = engine.chain_flux(dm, nf, geom[0], geom[1])
+        elif (rtag is not None and rtag[2] > 1 and rtag[0] * rtag[1] == nf.shape[0] and dm.chain_ok
+              and self.precision == "f32" and self.num_layers <= 8):
+            # a tagged radius graph: every edge's flux, in the fused radius kernels' arithmetic
+            flux = engine.graph_flux_radius(self.device_model(dev, rtag[2]), nf, edge_index, rtag[0], rtag[1])
         else:
             flux = engine.graph_flux(dm, nf, edge_index)
         return flux.to(node_features.device)

@@ -14,19 +14,35 @@ import torch
 CHAIN_TAG = "_hf_chain"
 
 
-_EI_CACHE = {}  # (nx, batch, device) -> (edge_index, its _version when cached)
+_EI_CACHE = {}  # (nx, batch, device, radius) -> (edge_index, its _version when cached)
 _EI_CACHE_MAX = 4
+MAX_RADIUS = 3
 
 
-def chain_edge_index(nx, batch=1, device=None):
+def chain_edge_index(nx, batch=1, device=None, radius=1):
     """Edge list of `batch` disjoint periodic chains of nx cells.  Per IC b the
     2*nx edges are (i -> i+1) for i < nx, then (i+1 -> i) — the order of
     src/graph_constructor.py:34-38 — offset by b*nx nodes.  A fresh tensor per
-    call (the caller may modify it in place, e.g. add a node offset)."""
-    return _chain_edge_index(nx, batch, device)
+    call (the caller may modify it in place, e.g. add a node offset).
+
+    radius = R in 1..3 (nx >= 2R + 1, so that no edge repeats) gives the
+    radius-R chain graph, which the reference names and never builds: per IC a
+    block of 2*R*nx edges, for r = 1..R in order the nx edges i -> (i+r) mod nx,
+    then the nx edges (i+r) mod nx -> i.  Its first 2*nx edges are the
+    reference's, and the only ones the hybrid solver reads."""
+    return _chain_edge_index(nx, batch, device, radius)
 
 
-def shared_chain_edge_index(nx, batch=1, device=None):
+def _check_radius(nx, radius):
+    radius = int(radius)
+    if not 1 <= radius <= MAX_RADIUS:
+        raise ValueError(f"stencil radius must be 1..{MAX_RADIUS}, got {radius}")
+    if radius > 1 and nx < 2 * radius + 1:
+        raise ValueError(f"a radius-{radius} chain needs nx >= {2 * radius + 1} cells (no repeated edge), got {nx}")
+    return radius
+
+
+def shared_chain_edge_index(nx, batch=1, device=None, radius=1):
     """chain_edge_index for the package's own callers (the training loss, the
     chain check of FluxGNN.forward), which never modify it: the tensor of a
     (nx, batch, device) is built once and handed out again while it is
@@ -35,47 +51,64 @@ def shared_chain_edge_index(nx, batch=1, device=None):
     build_chain_graph per sample), saves eight small device launches per step.
     The result is shared: do not modify it in place (an in-place edit drops its
     chain tag and the next call builds a fresh one, but earlier holders see it)."""
-    key = (int(nx), int(batch), str(torch.device(device) if device is not None else torch.device("cpu")))
+    key = (int(nx), int(batch), str(torch.device(device) if device is not None else torch.device("cpu")),
+           int(radius))
     hit = _EI_CACHE.get(key)
     if hit is not None and hit[0]._version == hit[1]:
         return hit[0]
-    ei = _chain_edge_index(nx, batch, device)
+    ei = _chain_edge_index(nx, batch, device, radius)
     if len(_EI_CACHE) >= _EI_CACHE_MAX:
         _EI_CACHE.pop(next(iter(_EI_CACHE)))
     _EI_CACHE[key] = (ei, ei._version)
     return ei
 
 
-def _chain_edge_index(nx, batch, device):
+def _chain_edge_index(nx, batch, device, radius=1):
+    radius = _check_radius(nx, radius)
     src = torch.arange(nx, dtype=torch.long, device=device)
-    dst = (src + 1) % nx
-    row = torch.cat([src, dst])
-    col = torch.cat([dst, src])
+    if radius == 1:
+        dst = (src + 1) % nx
+        row = torch.cat([src, dst])
+        col = torch.cat([dst, src])
+    else:
+        dsts = [(src + r) % nx for r in range(1, radius + 1)]
+        row = torch.cat([t for d in dsts for t in (src, d)])
+        col = torch.cat([t for d in dsts for t in (d, src)])
     if batch > 1:
         off = (torch.arange(batch, dtype=torch.long, device=device) * nx).unsqueeze(1)
         row = (row.unsqueeze(0) + off).reshape(-1)
         col = (col.unsqueeze(0) + off).reshape(-1)
     ei = torch.stack([row, col])
-    tag_chain(ei, batch, nx)
+    tag_chain(ei, batch, nx, radius)
     return ei
 
 
-def tag_chain(edge_index, batch, nx):
-    setattr(edge_index, CHAIN_TAG, (int(batch), int(nx), edge_index._version))
+def tag_chain(edge_index, batch, nx, radius=1):
+    setattr(edge_index, CHAIN_TAG, (int(batch), int(nx), edge_index._version, int(radius)))
     return edge_index
 
 
 def chain_tag(edge_index):
-    """(batch, nx) if edge_index is an unmodified tagged chain, else None."""
-    tag = getattr(edge_index, CHAIN_TAG, None)
-    if tag is None or tag[2] != edge_index._version:
+    """(batch, nx) if edge_index is an unmodified tagged chain of radius 1, else
+    None: what every caller written for the ±1 chain expects.  A radius graph
+    is told by chain_tag_radius."""
+    tag = chain_tag_radius(edge_index)
+    if tag is None or tag[2] != 1:
         return None
     return tag[0], tag[1]
 
 
-def build_chain_graph(full_state, x, device=None):
+def chain_tag_radius(edge_index):
+    """(batch, nx, radius) if edge_index is an unmodified tagged chain of any radius, else None."""
+    tag = getattr(edge_index, CHAIN_TAG, None)
+    if tag is None or tag[2] != edge_index._version:
+        return None
+    return tag[0], tag[1], (tag[3] if len(tag) > 3 else 1)
+
+
+def build_chain_graph(full_state, x, device=None, radius=1):
     """full_state [3,nx] (numpy or torch: n,u,E), x [nx] ->
-    node_features [nx,4] float32 (n,u,E,x) and edge_index [2,2nx] int64."""
+    node_features [nx,4] float32 (n,u,E,x) and edge_index [2,2*radius*nx] int64."""
     if isinstance(full_state, np.ndarray):
         n, u, E = (torch.from_numpy(full_state[i].astype(np.float32)) for i in range(3))
     else:
@@ -86,12 +119,12 @@ def build_chain_graph(full_state, x, device=None):
         n, u, E = n.to(device), u.to(device), E.to(device)
     x_t = torch.as_tensor(x, dtype=torch.float32, device=device)
     node_features = torch.stack([n, u, E, x_t], dim=-1)
-    return node_features, chain_edge_index(n.shape[0], 1, device)
+    return node_features, chain_edge_index(n.shape[0], 1, device, radius)
 
 
-def build_chain_graph_batch(states, x, device=None):
-    """Batched form: states [B,3,nx] -> node_features [B*nx,4], edge_index [2,B*2nx]
-    (IC b owns nodes b*nx.. and edges b*2nx..)."""
+def build_chain_graph_batch(states, x, device=None, radius=1):
+    """Batched form: states [B,3,nx] -> node_features [B*nx,4], edge_index [2,B*2*radius*nx]
+    (IC b owns nodes b*nx.. and edges b*2*radius*nx..)."""
     if isinstance(states, np.ndarray):
         states = torch.from_numpy(np.ascontiguousarray(states, dtype=np.float32))
     if device is not None:
@@ -99,4 +132,4 @@ def build_chain_graph_batch(states, x, device=None):
     B, _, nx = states.shape
     x_t = torch.as_tensor(x, dtype=torch.float32, device=states.device).expand(B, nx)
     nf = torch.stack([states[:, 0], states[:, 1], states[:, 2], x_t], dim=-1).reshape(B * nx, 4)
-    return nf, chain_edge_index(nx, B, states.device)
+    return nf, chain_edge_index(nx, B, states.device, radius)

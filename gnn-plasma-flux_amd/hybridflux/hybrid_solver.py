@@ -10,8 +10,14 @@ windowed / super-window chain kernel + the FV/Poisson kernel per step
 
 `step`/`run` keep the reference's numpy [3,nx] shapes; `step_batch`/`run_batch`
 take [B,3,nx] device tensors (batched independent ICs) and return device
-tensors.  `radius` is stored and unused, exactly as in the reference
-(src/hybrid_solver.py:32): the stencil radius only names the checkpoint.
+tensors.  `radius` is a label: stored and unused, exactly as in the reference
+(src/hybrid_solver.py:32), where the stencil radius only names the checkpoint
+and the graph is always the ±1 chain.  `graph_radius` is the real one, opt-in:
+graph_radius=R (1..3, default 1) runs FluxGNN on the radius-R chain graph
+(graph_constructor.chain_edge_index(radius=R): mean over the 2R neighbours) in
+the same fused f32 kernels, the solver reading that graph's first 2*nx fluxes.
+HybridSolver(path, 3, graph_radius=3) is the intended call for a checkpoint
+trained with train_model(..., graph_radius=3).
 """
 import math
 import os
@@ -41,7 +47,7 @@ def load_state_dict(model_path):
 
 class HybridSolver:
     def __init__(self, model_path, radius, nx=64, length=2 * math.pi, dt=5e-3, t_end=1.0, device="cuda",
-                 precision="f32", poisson="spectral", num_layers=None):
+                 precision="f32", poisson="spectral", num_layers=None, graph_radius=1):
         """precision: chain-kernel arithmetic, "f32" (default, exact float32
         MFMA), "f16x3" (float32-accurate split-fp16 MFMA, ~5x the matrix rate)
         or "bf16" (bf16 weights/activations, BASELINE config 4).
@@ -49,7 +55,17 @@ class HybridSolver:
         "tridiagonal" (opt-in, NOT the reference's: the north star's
         cyclic-reduction solve fused into the same step kernels; engine.Grid).
         num_layers: the checkpoint's update layers (default MODEL_CONFIG's, the
-        reference's only depth)."""
+        reference's only depth).
+        graph_radius: the stencil radius the model's graph really has (1..3;
+        nx >= 2*graph_radius + 1; beyond 1 precision must be "f32").  `radius`
+        stays the checkpoint label it is in the reference."""
+        self.graph_radius = int(graph_radius)
+        if not 1 <= self.graph_radius <= 3:
+            raise ValueError(f"graph_radius must be 1, 2 or 3, got {graph_radius!r}")
+        if self.graph_radius > 1 and precision != "f32":
+            raise ValueError(f"graph_radius > 1 runs on the f32 core only, got precision {precision!r}")
+        if self.graph_radius > 1 and nx < 2 * self.graph_radius + 1:
+            raise ValueError(f"graph_radius {self.graph_radius} needs nx >= {2 * self.graph_radius + 1}, got {nx}")
         self.device = torch.device(device)
         self.baseline = BaselineSolver(nx=nx, length=length, dt=dt, t_end=t_end, device=self.device,
                                        poisson=poisson)
@@ -66,7 +82,7 @@ class HybridSolver:
         return self.baseline.grid
 
     def _dm(self):
-        return self.model.device_model(self.device)
+        return self.model.device_model(self.device, self.graph_radius)
 
     def _upload(self, states):
         return self.baseline._upload(states)
@@ -110,9 +126,9 @@ class HybridEnsemble:
     """M HybridSolvers rolled out together: an ablation sweep's checkpoints, or
     an ensemble's members, as ONE launch at nx 16/32/48/64 (hf_run_set: every
     workgroup picks its model's weights), model after model at any other nx.
-    The solvers share nx, the grid constants, the Poisson mode, the precision
-    and the device (ValueError names the first mismatch); their depths may
-    differ.  run_batch / compare_batch take HybridSolver's arguments and return
+    The solvers share nx, the grid constants, the Poisson mode, the precision,
+    the device and the graph radius (ValueError names the first mismatch); their
+    depths may differ.  run_batch / compare_batch take HybridSolver's arguments and return
     its dicts with a leading model axis, model m's block bit-identical to
     solvers[m]'s own call.  states0 [B,3,nx] is shared by all models;
     [M,B,3,nx] gives each model its own ICs.
@@ -137,13 +153,14 @@ class HybridEnsemble:
         self.device = self.solvers[0].device
         self._set = None
 
-    SIGNATURE = ("nx", "length", "dt", "nu", "poisson", "precision", "device")
+    SIGNATURE = ("nx", "length", "dt", "nu", "poisson", "precision", "device", "graph_radius")
 
     @staticmethod
     def signature(solver):
         """What two HybridSolvers must share to roll out in one launch (SIGNATURE's fields)."""
         g = solver.grid
-        return (g.nx, g.length, g.dt, g.nu, g.poisson, solver.model.precision, str(torch.device(solver.device)))
+        return (g.nx, g.length, g.dt, g.nu, g.poisson, solver.model.precision, str(torch.device(solver.device)),
+                getattr(solver, "graph_radius", 1))
 
     @classmethod
     def from_checkpoints(cls, paths, radius=1, **solver_kw):

@@ -100,7 +100,18 @@ def _has_rollout(cfg):
     return cfg["rollout_steps"] > 0 and cfg["lambda_energy_multi"] > 0  # train_ablation.py:172
 
 
-def ablation_loss(model, st, ft, st_next, x, dt, dx, cfg, grid, n0=1.0, fused=True, nf=None, rollout="reuse"):
+def _solver_edges(flux, B, nx, graph_radius=1):
+    """The [B, 2nx] fluxes the solver reads out of FluxGNN.forward's result on B
+    chains: all of it on the ±1 chain; on a radius-R graph the first 2nx of each
+    IC's 2*R*nx (graph_constructor.chain_edge_index), the long edges' fluxes
+    getting a zero gradient from autograd."""
+    if graph_radius == 1:
+        return flux.reshape(B, 2 * nx)
+    return flux.reshape(B, 2 * graph_radius * nx)[:, :2 * nx].contiguous()
+
+
+def ablation_loss(model, st, ft, st_next, x, dt, dx, cfg, grid, n0=1.0, fused=True, nf=None, rollout="reuse",
+                  graph_radius=1):
     """Loss of train_ablation.py:107-206 for a batch: st, st_next [B,3,nx], ft [B,nx]
     on the device.  Returns (loss, flux_loss); B=1 is the reference formula.
     fused: the terms (:124-170, and the rollout energy term for rollout_steps
@@ -110,15 +121,18 @@ def ablation_loss(model, st, ft, st_next, x, dt, dx, cfg, grid, n0=1.0, fused=Tr
     the caller has them (FluxDataset.batch with x).  rollout (torch form only):
     "reuse" runs no model forward whose result cannot reach the loss
     (_rollout_energies), "literal" the reference's loop of rollout_steps
-    forwards (_rollout_energies_literal); the two give the same loss bit for bit."""
+    forwards (_rollout_energies_literal); the two give the same loss bit for bit.
+    graph_radius: the stencil radius of the model's graph (1..3).  Beyond 1 the
+    model runs on the radius chain graph (FluxGNN's autograd Function on the
+    generic kernels) and the loss reads that graph's first 2nx fluxes per IC."""
     B, _, nx = st.shape
     n_t, u_t = st[:, 0], st[:, 1]
     n_next_true, u_next_true, E_next_true = st_next[:, 0], st_next[:, 1], st_next[:, 2]
     if nf is None:
-        nf, ei = build_chain_graph_batch(st, x)
+        nf, ei = build_chain_graph_batch(st, x, radius=graph_radius)
     else:
-        ei = shared_chain_edge_index(nx, B, st.device)
-    flux_edge = model(nf, ei).reshape(B, 2 * nx)
+        ei = shared_chain_edge_index(nx, B, st.device, graph_radius)
+    flux_edge = _solver_edges(model(nf, ei), B, nx, graph_radius)
     if fused and n0 == 1.0 and abs(dt / dx - grid.dt / grid.dx) <= 1e-12 * abs(dt / dx):
         lam = (cfg["lambda_state"], cfg["lambda_poisson"], cfg["lambda_charge"], cfg["lambda_energy_one"])
         K = cfg["rollout_steps"] if _has_rollout(cfg) else 0
@@ -126,7 +140,8 @@ def ablation_loss(model, st, ft, st_next, x, dt, dx, cfg, grid, n0=1.0, fused=Tr
         roll = (K, cfg["lambda_energy_multi"], dt) if in_kernel else (0, 0.0, dt)
         loss, flux_loss = _StepLoss.apply(flux_edge, st, ft, st_next, grid, lam, roll)
         if not in_kernel:  # later energies need forwards on later states
-            loss = _add_rollout_term(loss, cfg, _rollout_energies(model, st, flux_edge, x, dt, dx, cfg, grid))
+            loss = _add_rollout_term(loss, cfg, _rollout_energies(model, st, flux_edge, x, dt, dx, cfg, grid,
+                                                                  graph_radius))
         return loss, flux_loss
     F_pred = 0.5 * (flux_edge[:, :nx] + flux_edge[:, nx:])                        # :124-126
     flux_loss = _mse(F_pred, ft)                                                   # :129
@@ -149,9 +164,9 @@ def ablation_loss(model, st, ft, st_next, x, dt, dx, cfg, grid, n0=1.0, fused=Tr
         loss = loss + cfg["lambda_energy_one"] * _mse(e_p, e_t)
     if _has_rollout(cfg):
         if rollout == "literal":
-            energies = _rollout_energies_literal(model, st, x, dt, dx, cfg, grid)
+            energies = _rollout_energies_literal(model, st, x, dt, dx, cfg, grid, graph_radius)
         else:
-            energies = _rollout_energies(model, st, flux_edge, x, dt, dx, cfg, grid)
+            energies = _rollout_energies(model, st, flux_edge, x, dt, dx, cfg, grid, graph_radius)
         loss = _add_rollout_term(loss, cfg, energies)
     return loss, flux_loss
 
@@ -161,7 +176,7 @@ def _add_rollout_term(loss, cfg, energies):
     return loss + cfg["lambda_energy_multi"] * torch.mean((energies - energies[0]) ** 2)
 
 
-def _rollout_energies_literal(model, st, x, dt, dx, cfg, grid):
+def _rollout_energies_literal(model, st, x, dt, dx, cfg, grid, graph_radius=1):
     """The rollout energies [K, B] as the reference's loop computes them
     (:173-204): K model forwards, one per rolled state."""
     B, _, nx = st.shape
@@ -170,8 +185,8 @@ def _rollout_energies_literal(model, st, x, dt, dx, cfg, grid):
     for _ in range(cfg["rollout_steps"]):
         n_r, u_r, E_r = state[:, 0], state[:, 1], state[:, 2]
         energies.append(0.5 * torch.mean(u_r ** 2, dim=-1))                         # :181-182
-        nf_r, ei_r = build_chain_graph_batch(state, x)
-        fe_r = model(nf_r, ei_r).reshape(B, 2 * nx)
+        nf_r, ei_r = build_chain_graph_batch(state, x, radius=graph_radius)
+        fe_r = _solver_edges(model(nf_r, ei_r), B, nx, graph_radius)
         F_r = 0.5 * (fe_r[:, :nx] + fe_r[:, nx:])
         n_next_r = n_r - (dt / dx) * (F_r - torch.roll(F_r, 1, dims=-1))
         F_u = 0.5 * u_r * u_r
@@ -180,7 +195,7 @@ def _rollout_energies_literal(model, st, x, dt, dx, cfg, grid):
     return torch.stack(energies)                                                   # [K, B]
 
 
-def _rollout_energies(model, st, flux_edge, x, dt, dx, cfg, grid):
+def _rollout_energies(model, st, flux_edge, x, dt, dx, cfg, grid, graph_radius=1):
     """The same energies [K, B] as _rollout_energies_literal, bit for bit, with
     only the forwards whose results reach them.  The energy of step k is
     0.5 mean(u_k^2) (:181) and u_{k+1} needs E_k (:196), which for k >= 1 is
@@ -204,8 +219,8 @@ def _rollout_energies(model, st, flux_edge, x, dt, dx, cfg, grid):
         if k + 2 <= K - 1:  # E_{k+1} feeds u_{k+2}, the last energy's u at k + 2 = K - 1
             if fe_r is None:
                 with torch.no_grad():
-                    nf_r, ei_r = build_chain_graph_batch(torch.stack([n_r, u_r, E_r], dim=1), x)
-                    fe_r = model(nf_r, ei_r).reshape(B, 2 * nx)
+                    nf_r, ei_r = build_chain_graph_batch(torch.stack([n_r, u_r, E_r], dim=1), x, radius=graph_radius)
+                    fe_r = _solver_edges(model(nf_r, ei_r), B, nx, graph_radius)
             F_r = 0.5 * (fe_r[:, :nx] + fe_r[:, nx:])
             n_next = n_r - (dt / dx) * (F_r - torch.roll(F_r, 1, dims=-1))
             E_next = _poisson_detached(grid, n_next)
@@ -452,7 +467,7 @@ def _guarded_optimizer(params, lr, weight_decay, max_grad_norm, skip_nonfinite, 
     return opt, (scheduler(opt) if scheduler is not None else None)
 
 
-def direct_step(model, opt, st, ft, sn, nf, x, dt, dx, cfg, grid):
+def direct_step(model, opt, st, ft, sn, nf, x, dt, dx, cfg, grid, graph_radius=1):
     """One step of the reference trainer's loop (ablation_loss ->
     loss.backward() -> optimizer.step(), train_ablation.py:107-210) without
     autograd where it reduces to three HIP passes and the optimizer launch:
@@ -466,7 +481,10 @@ def direct_step(model, opt, st, ft, sn, nf, x, dt, dx, cfg, grid):
     same parameters bit for bit as the autograd step, without its seed fill,
     gradient product and bookkeeping launches.  Parameter hooks are not run.
     Returns (loss, flux_loss) detached, or None when the case does not apply
-    (the caller then takes the autograd step)."""
+    (the caller then takes the autograd step).  It declines a graph_radius
+    beyond 1: the radius graph goes through ablation_loss's autograd step."""
+    if graph_radius != 1:
+        return None
     if type(model) is not FluxGNN or not isinstance(opt, FlatAdam) or nf is None or not torch.is_grad_enabled():
         return None
     params = list(model.parameters())
@@ -501,8 +519,9 @@ class GraphedStep:
     The warmup steps that precede the capture are ordinary eager steps on the
     first batches, so a pass makes exactly the eager loop's updates."""
 
-    def __init__(self, model, opt, data, batch_size, x, dt, dx, cfg, grid, direct=True):
+    def __init__(self, model, opt, data, batch_size, x, dt, dx, cfg, grid, direct=True, graph_radius=1):
         self.args = (model, opt, data, x, dt, dx, cfg, grid)
+        self.graph_radius = graph_radius
         self.direct = direct  # direct_step where it applies
         dev = data.state_t.device
         self.idx = torch.zeros(batch_size, dtype=torch.long, device=dev)
@@ -513,10 +532,10 @@ class GraphedStep:
         model, opt, data, x, dt, dx, cfg, grid = self.args
         st, ft, sn, nf = data.batch(self.idx, x, check=False)  # (train_steps checked the order)
         if self.direct:
-            r = direct_step(model, opt, st, ft, sn, nf, x, dt, dx, cfg, grid)
+            r = direct_step(model, opt, st, ft, sn, nf, x, dt, dx, cfg, grid, self.graph_radius)
             if r is not None:
                 return r
-        loss, flux_loss = ablation_loss(model, st, ft, sn, x, dt, dx, cfg, grid, nf=nf)
+        loss, flux_loss = ablation_loss(model, st, ft, sn, x, dt, dx, cfg, grid, nf=nf, graph_radius=self.graph_radius)
         opt.zero_grad(set_to_none=True)
         loss.backward()
         opt.step()
@@ -542,7 +561,7 @@ class GraphedStep:
 
 
 def train_steps(model, opt, data, order, batch_size, x, dt, dx, cfg, grid, graphed=None, warmup=3, direct=True,
-                stats=None):
+                stats=None, graph_radius=1):
     """One pass over `order` (sample indices) in batches; returns (sum of
     losses, sum of flux losses) weighted by batch size, and the step count.
     graphed: a GraphedStep of this batch size (created by the caller and kept
@@ -551,7 +570,7 @@ def train_steps(model, opt, data, order, batch_size, x, dt, dx, cfg, grid, graph
     eager steps take direct_step where it applies (the same parameters bit for
     bit as the autograd step).  stats: the trainer's _StepStats; with a guarded
     FlatAdam the sums then run over the steps that were applied (stats.weight
-    samples)."""
+    samples).  graph_radius: ablation_loss's (a GraphedStep carries its own)."""
     tot, tot_flux, steps = 0.0, 0.0, 0
     losses = []
     data.check_indices(order)  # once per pass; the steps gather with check=False
@@ -572,11 +591,12 @@ def train_steps(model, opt, data, order, batch_size, x, dt, dx, cfg, grid, graph
                 loss, flux_loss = graphed(idx)
         else:
             st, ft, sn, nf = data.batch(idx, x, check=False)
-            r = direct_step(model, opt, st, ft, sn, nf, x, dt, dx, cfg, grid) if direct else None
+            r = direct_step(model, opt, st, ft, sn, nf, x, dt, dx, cfg, grid, graph_radius) if direct else None
             if r is not None:
                 loss, flux_loss = r
             else:
-                loss, flux_loss = ablation_loss(model, st, ft, sn, x, dt, dx, cfg, grid, nf=nf)
+                loss, flux_loss = ablation_loss(model, st, ft, sn, x, dt, dx, cfg, grid, nf=nf,
+                                                graph_radius=graph_radius)
                 opt.zero_grad()
                 loss.backward()
                 opt.step()
@@ -595,7 +615,7 @@ def train_steps(model, opt, data, order, batch_size, x, dt, dx, cfg, grid, graph
 
 def train_model(state_t, flux_t, state_next, x, dt, dx, nu, config_name, stencil_radius, epochs=20, lr=1e-3,
                 device="cuda", batch_size=1, seed=None, save_dir="checkpoints", log=print, weight_decay=0.0,
-                max_grad_norm=None, skip_nonfinite=False, scheduler=None):
+                max_grad_norm=None, skip_nonfinite=False, scheduler=None, graph_radius=1):
     """scripts/training/train_ablation.py:64-237 on the MI355X.  Returns
     (model, history) and writes checkpoints/hybrid_<config>_r<radius>.pt and
     history_<config>_r<radius>.json like the reference (save_dir=None skips).
@@ -603,8 +623,15 @@ def train_model(state_t, flux_t, state_next, x, dt, dx, nu, config_name, stencil
     scheduler: a callable opt -> torch.optim.lr_scheduler.LRScheduler, stepped
     once per epoch.  With max_grad_norm or skip_nonfinite the history gains
     grad_norm_max and skipped_steps per epoch, and the epoch's losses are means
-    over the samples of the steps that were applied."""
+    over the samples of the steps that were applied.
+    stencil_radius names the checkpoint, as in the reference, whose graph is
+    always the ±1 chain.  graph_radius (1..3) is the real one: beyond 1 the
+    model trains on the radius chain graph (ablation_loss), to be rolled out by
+    HybridSolver(path, stencil_radius, graph_radius=graph_radius).  The
+    checkpoint's name, keys and shapes do not depend on it."""
     cfg = ABLATION_CONFIGS[config_name]
+    if int(graph_radius) != graph_radius or not 1 <= graph_radius <= 3:
+        raise ValueError(f"graph_radius must be 1, 2 or 3, got {graph_radius!r}")
     engine.require_device(torch.empty(0, device=device), "device")
     if seed is not None:
         torch.manual_seed(seed)
@@ -623,7 +650,8 @@ def train_model(state_t, flux_t, state_next, x, dt, dx, nu, config_name, stencil
     for epoch in range(1, epochs + 1):
         order = torch.randperm(len(data), generator=gen).to(device)
         t0 = time.perf_counter()
-        tot, tot_flux, _ = train_steps(model, opt, data, order, batch_size, x_dev, dt, dx, cfg, grid, stats=stats)
+        tot, tot_flux, _ = train_steps(model, opt, data, order, batch_size, x_dev, dt, dx, cfg, grid, stats=stats,
+                                       graph_radius=int(graph_radius))
         count = stats.weight if stats else len(data)
         torch.cuda.synchronize(device)
         if sched is not None:
@@ -1096,8 +1124,14 @@ def _train_windows(m, model, data, x, grid, init, epochs, lr, batch_size, seed, 
     return model, history
 
 
+def _radius_one_only(what, graph_radius):
+    if graph_radius != 1:
+        raise ValueError(f"{what}: unrolled training runs on the ±1 chain only (graph_radius = 1), got "
+                         f"graph_radius = {graph_radius!r}; train a radius graph with train_model(graph_radius=...)")
+
+
 def unrolled_loss(model, traj, x, grid, channel_weights=(1.0, 1.0, 1.0), through_state=True, return_states=False,
-                  conservation=None, conservation_ref="target"):
+                  conservation=None, conservation_ref="target", graph_radius=1):
     """L = (1/K) sum_{k=1..K} mean_{b,ch,i} w_ch (s^_k - s*_k)^2 of the hybrid
     solver (src/hybrid_solver.py:45-63) unrolled K steps from traj[:, 0], against
     the targets traj[:, 1:] (classical solver states): traj [B,K+1,3,nx] on the
@@ -1119,20 +1153,24 @@ def unrolled_loss(model, traj, x, grid, channel_weights=(1.0, 1.0, 1.0), through
     (eref, qref).  None (the default): the calls and bits of the loss without the
     terms.  With conservation, return_states also returns the steps' rows
     [K,4] = (total, state, energy, charge).  The charge term has no gradient here
-    (the finite-volume update conserves charge identically); its value is reported."""
+    (the finite-volume update conserves charge identically); its value is reported.
+    graph_radius: 1 only (ValueError otherwise): the unrolled kernels know the ±1 chain."""
+    _radius_one_only("unrolled_loss", graph_radius)
     return _rollout_loss(_FLUX, model, traj, x, grid, channel_weights, through_state, return_states,
                          _conservation(conservation, conservation_ref))
 
 
 def unrolled_step(model, opt, traj, x, grid, channel_weights=(1.0, 1.0, 1.0), through_state=True, conservation=None,
-                  conservation_ref="target"):
+                  conservation_ref="target", graph_radius=1):
     """unrolled_loss -> backward -> opt.step() without autograd, after
     direct_step: FluxGNN with flat parameters (flatten_parameters_), FlatAdam
     over exactly those parameters, grad enabled.  The same forwards, adjoints,
     backwards and gradient sum as the autograd step, in the same order, so the
     same parameters bit for bit, without autograd's seed, product and
     bookkeeping launches.  Returns the detached loss, or None when the case does
-    not apply (the caller then takes the autograd step)."""
+    not apply (the caller then takes the autograd step).  graph_radius: 1 only
+    (ValueError otherwise)."""
+    _radius_one_only("unrolled_step", graph_radius)
     return _rollout_step(_FLUX, model, opt, traj, x, grid, channel_weights, through_state,
                          _conservation(conservation, conservation_ref))
 
@@ -1182,7 +1220,7 @@ class WindowDataset:
 def train_unrolled(trajectories, x, dt, dx, nu, K=4, epochs=10, lr=1e-3, batch_size=32, seed=None, init=None,
                    channel_weights=(1.0, 1.0, 1.0), through_state=True, device="cuda", save_dir="checkpoints",
                    log=print, weight_decay=0.0, max_grad_norm=None, skip_nonfinite=False, scheduler=None,
-                   conservation=None, conservation_ref="target"):
+                   conservation=None, conservation_ref="target", graph_radius=1):
     """Train (or fine-tune) FluxGNN on K-step windows of classical trajectories
     [N,T+1,3,nx] (datagen.generate_trajectories) with the unrolled loss: Adam(lr)
     over shuffled batches of batch_size windows, one unrolled_step each.  init:
@@ -1194,7 +1232,9 @@ def train_unrolled(trajectories, x, dt, dx, nu, K=4, epochs=10, lr=1e-3, batch_s
     train_model's -- the guard that keeps one window whose rollout blows up from
     turning every parameter into NaN.  conservation = (lam_e, lam_q),
     conservation_ref "target" or "start": unrolled_loss's energy and charge
-    terms; the history then also holds energy_loss and charge_loss."""
+    terms; the history then also holds energy_loss and charge_loss.
+    graph_radius: 1 only (ValueError otherwise)."""
+    _radius_one_only("train_unrolled", graph_radius)
     cons = _conservation(conservation, conservation_ref, trainer=True)
     engine.require_device(torch.empty(0, device=device), "device")
     if seed is not None:

@@ -104,6 +104,47 @@ int hf_device_count(void);
  */
 int hf_model_create(const float *host_params, int in_dim, int hidden, int layers,
                     int wdtype, hf_model_t *out);
+/*
+ * hf_model_create with a real stencil radius.  Replaces: nothing the reference
+ * runs: its radius names a checkpoint (src/hybrid_solver.py:32) and its graph
+ * is always the ±1 chain (src/graph_constructor.py:34-38).
+ * A model of radius R (1..3) runs FluxGNN.forward on the radius-R chain graph
+ * in every fused chain entry point (hf_chain_flux, hf_step, hf_run,
+ * hf_run_compare, the model-set calls): per IC a block of 2*R*nx edges, for
+ * r = 1..R in order the nx edges i -> (i+r) mod nx, then the nx edges
+ * (i+r) mod nx -> i; the update layers' mean runs over the 2R neighbours,
+ * summed in the order ((((h[i+1] + h[i-1]) + h[i+2]) + h[i-2]) + h[i+3]) +
+ * h[i-3] (a sequential index_add_ over that edge list).  The parameters are
+ * those of radius 1 (same host_params).  The solver uses only the first 2nx
+ * fluxes of a block (the ±1 edges, F_i = 0.5 (fe[i] + fe[nx+i])), and those
+ * are what hf_chain_flux writes: dev_flux_edge stays [B][2nx].  The 1/deg is
+ * packed into W_b as float32(w / (2R)): exact for R = 1, 2; R = 3 rounds each
+ * weight once instead of each mean.  A model of radius R > 1 needs
+ * nx >= 2R + 1 (no repeated edge): HF_EINVAL from every entry point that
+ * takes it otherwise (radius-1 models take every nx they always took).
+ * hf_model_create is this call with radius 1.  radius outside 1..3:
+ * HF_EINVAL; radius > 1 with wdtype != HF_WDTYPE_F32, or on a model that is
+ * not chain-capable (in_dim 4, hidden 128, layers <= 8): HF_EUNSUPPORTED; all
+ * three before any device call.  Small batches of a radius > 1 model run the
+ * IC-per-wave kernels (the cell-split kernels are radius 1): same values.
+ * hf_graph_flux ignores the radius: the caller's edge list is the graph.
+ */
+int hf_model_create_ex(const float *host_params, int in_dim, int hidden, int layers,
+                       int wdtype, int radius, hf_model_t *out);
+/* The model's stencil radius (1..3); 0 for NULL. */
+int hf_model_radius(hf_model_t model);
+/*
+ * The weight stream hf_model_create_ex packs for the fused chain kernels of a
+ * chain-capable model (in_dim 4, hidden 128, layers <= 8), on the HOST: no
+ * device is touched (what the host-sanitized tests/native/radius_sanitize.cpp
+ * checks).  Returns the stream's size in bytes; with stream_out == NULL that
+ * is all it does, otherwise it writes the stream into stream_out, which must
+ * hold stream_bytes >= that size.  -1: layers outside 0..8, radius outside
+ * 1..3, an unknown wdtype, radius > 1 with wdtype != HF_WDTYPE_F32, NULL
+ * host_params, or a stream_out that is too small.
+ */
+int64_t hf_chain_pack_host(const float *host_params, int layers, int wdtype, int radius,
+                           void *stream_out, int64_t stream_bytes);
 void hf_model_destroy(hf_model_t model);
 /* Total float count host_params must hold for these dimensions. */
 int64_t hf_model_param_count(int in_dim, int hidden, int layers);
@@ -127,6 +168,23 @@ int64_t hf_graph_workspace_bytes(hf_model_t model, int64_t N, int64_t E);
 int hf_graph_flux(hf_model_t model, const float *dev_node_features, int64_t N,
                   const int64_t *dev_edge_index, int64_t E, float *dev_flux,
                   void *dev_workspace, void *stream);
+
+/*
+ * FluxGNN.forward of a radius-R model (hf_model_create_ex) on ITS OWN graph:
+ * dev_edge_index [2][E], E = 2*R*B*nx, is the radius-R chain graph of B chains
+ * of nx cells in the order hf_model_create_ex documents (the caller declares
+ * it; graph_constructor.chain_edge_index(nx, B, radius=R) builds it).  Replaces:
+ * nothing the reference runs (its graph is always the +-1 chain).  Writes all
+ * E fluxes, the long edges' too, through the generic-graph kernels with the
+ * fused kernels' arithmetic: the neighbour SUM in edge-list order times W_b
+ * packed as float32(w / (2R)), where hf_graph_flux forms the reference's mean
+ * (float32 sum / degree, one rounding per mean).  The two agree bit for bit for
+ * R <= 2 and to a rounding for R = 3; this call's first 2nx fluxes per IC are
+ * hf_chain_flux's definition.  For a radius-1 model it is hf_graph_flux.
+ * Workspace: hf_graph_workspace_bytes(model, B*nx, E).  nx < 2R + 1: HF_EINVAL.
+ */
+int hf_graph_flux_radius(hf_model_t model, const float *dev_node_features, int B, int nx,
+                         const int64_t *dev_edge_index, float *dev_flux, void *dev_workspace, void *stream);
 
 /*
  * Training: FluxGNN.forward + autograd backward on any
@@ -154,7 +212,9 @@ int hf_graph_flux(hf_model_t model, const float *dev_node_features, int64_t N,
  * a stencil inside the GEMM operand loads, the edge readout split into
  * per-node P/Q GEMMs, f32 MFMA GEMMs throughout); otherwise the edge buckets
  * are formed arithmetically instead of by the count/scan/fill CSR build.  0
- * for any other graph.
+ * for any other graph.  chain_nx > 0 declares radius-1 chains: a radius-R
+ * chain graph (hf_model_create_ex, E == 2*R*N) passes chain_nx = 0 and runs the
+ * generic kernels, which handle any graph.
  */
 int64_t hf_graph_tape_bytes(int in_dim, int hidden, int layers, int64_t N, int64_t E);
 int64_t hf_graph_backward_workspace_bytes(int in_dim, int hidden, int layers, int64_t N, int64_t E);

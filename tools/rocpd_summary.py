@@ -27,9 +27,9 @@ def main(path):
     # the table: its dispatches in launch order are warmup, TIMED and, under
     # bench.py --full, the next rollout, then the radii lines' warmup + rollout pairs
     head = [(n, d) for n, d in c.execute("select name, duration from kernels order by start")
-            if "chain_rollout_kernel" in n and "CoreF32T<2, 4, false, true>" in n.replace("(anonymous namespace)::", "")]
+            if "chain_rollout_kernel" in n and "CoreF32T<2, 4, false, true, 1>" in n.replace("(anonymous namespace)::", "")]
     if head:
-        print("\nDispatches of the headline kernel `chain_rollout_kernel<CoreF32T<2, 4, false, true>, 4>` "
+        print("\nDispatches of the headline kernel `chain_rollout_kernel<CoreF32T<2, 4, false, true, 1>, 4>` "
               "in launch order (us; bench.py: warmup, timed; with --full also the next rollout, then the radii's "
               "warmup + rollout pairs):",
               ", ".join(f"{d / 1e3:.1f}" for _, d in head))
