@@ -10,6 +10,13 @@ flux = hf_chain_flux on that state); compare_batch = run_batch + classical run
 hf_model_create_ex = hf_model_create; ensembles = single models; gradients
 through the radius graph on an exact case.
 
+The case table holds the regime rows too (radius_cases._regimes: depths 0..8,
+window-count boundaries, the tightest window, a second pass of the persistent
+loop, per-step rollouts at nx = 100 / 1024); hf_chain_flux writes them into
+buffers filled with NaN, and the persistent rows assert their second pass with
+the device's CU count.  The rollout body runs in the tridiagonal Poisson mode
+as well.  What is not a row of the table is in tests/test_gpu_radius_regimes.py.
+
 FluxGNN.forward on a tagged radius graph keeps the fused kernels' arithmetic on
 the generic kernels (hf_graph_flux_radius: the neighbour sum in edge-list order
 times W_b packed as w / (2R)), so the module and the solver share one
@@ -101,12 +108,27 @@ def int_states(case, b, T):
 # --------------------------------------------------------------- 1. hf_chain_flux
 @pytest.mark.parametrize("case", RC.cases("flux"), ids=lambda c: c.name)
 def test_chain_flux_bitwise(hf, case):
-    from hybridflux import engine
+    """hf_chain_flux into buffers filled with NaN beforehand: a flux that is never
+    written (a later pass of the persistent loop, a last window) stays NaN."""
+    from hybridflux import _lib, engine
     b = RC.find_case(case)
+    if case.name.startswith("rpersist"):
+        cus = torch.cuda.get_device_properties(0).multi_processor_count
+        r = case.regime(cus)
+        assert r["passes"] >= 2 and r["groups"] > cus * RC.WG_PER_CU, "no second pass of the persistent loop"
     m = device_model(b.sd, case.R)
-    fe, ff = engine.chain_flux(m, torch.from_numpy(b.nf).to(DEV), case.B, case.nx, flux_face=True)
+    dev = torch.device(DEV)
+    nf = torch.from_numpy(b.nf).to(dev)
+    fe = torch.full((case.B * 2 * case.nx,), float("nan"), device=dev)
+    ff = torch.full((case.B, case.nx), float("nan"), device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().hf_chain_flux(m.handle, _lib.ptr(nf), case.B, case.nx, _lib.ptr(fe), _lib.ptr(ff),
+                                            engine.stream_of(dev)))
     same(fe.reshape(case.B, 2 * case.nx), b.flux, case.nx, f"{case.name} edges")
     same(ff, b.faces, case.nx, f"{case.name} faces")
+    fe2, ff2 = engine.chain_flux(m, nf, case.B, case.nx, flux_face=True)
+    bits(fe2, fe, f"{case.name} edges, engine.chain_flux")
+    bits(ff2, ff, f"{case.name} faces, engine.chain_flux")
 
 
 # ------------------------------------------------------------ 2. FluxGNN.forward
@@ -151,15 +173,24 @@ def test_untagged_copy_takes_the_mean(hf):
 # -------------------------------------------------------------------- 3. rollouts
 @pytest.mark.parametrize("case", RC.cases("rollout"), ids=lambda c: c.name)
 def test_rollout_steps_and_face_flux_bitwise(hf, case):
+    rollout_body(case)
+
+
+def rollout_body(case, poisson="spectral"):
+    """T steps = T single steps, every step's face flux = hf_chain_flux on that
+    state, the first one the integer reference's.  nx = 16 MT: the persistent
+    rollout; any other nx the per-step path (T = 6, at nx = 1024 T = 2)."""
     from hybridflux import engine
     b = RC.find_case(case)
     m = device_model(b.sd, case.R)
-    grid = engine.Grid(case.nx)
+    grid = engine.Grid(case.nx, poisson=poisson)
     st = int_states(case, b, 6)
     x = grid.on(torch.device(DEV))[0]
-    T = 6
+    T = 2 if case.nx >= 1024 else 6
     out = engine.run(m, grid, st, T, traj=True, flux=True)
     same(out["flux"][:, 0], b.faces, case.nx, f"{case.name} first face flux")
+    print(f"{case.name} {poisson}: T = {T}, max |state| = {float(out['traj'].abs().max()):.3e}")
+    assert torch.isfinite(out["traj"]).all() and torch.isfinite(out["flux"]).all(), "the states left float32's range"
     cur = st
     for t in range(T):
         bits(out["traj"][:, t], cur, f"{case.name} state {t}")
@@ -171,6 +202,21 @@ def test_rollout_steps_and_face_flux_bitwise(hf, case):
         cur = nxt
     bits(out["traj"][:, T], cur, f"{case.name} state {T}")
     bits(out["final"], cur, f"{case.name} final")
+
+
+@pytest.mark.parametrize("name", ["rrollout_nx64_R2_L4", "rrollout_nx64_R3_L4", "rrollout_nx100_R2_L4",
+                                  "rrollout_nx100_R3_L4"])
+def test_rollout_tridiagonal_bitwise(hf, name):
+    """The same body with the tridiagonal Poisson plan (engine.Grid(poisson=
+    "tridiagonal"), as tests/test_gpu_tridiag.py asks for it): the persistent
+    rollout at nx = 64, the per-step path at nx = 100, a radius model in both."""
+    from hybridflux import engine
+    case = RC.BY_NAME[name]
+    rollout_body(case, poisson="tridiagonal")
+    b = RC.find_case(case)                                         # the mode is really applied: E differs
+    st, m = int_states(case, b, 2), device_model(b.sd, case.R)
+    tri, spec = (engine.run(m, engine.Grid(case.nx, poisson=p), st, 2)["final"] for p in ("tridiagonal", "spectral"))
+    assert not torch.equal(tri[:, 2], spec[:, 2])
 
 
 # ------------------------------------------------------------------ 4. the oracle
