@@ -616,68 +616,35 @@ int hf_adam_flat_ex(float *params, const float *grads, float *exp_avg, float *ex
 }
 
 // ------------------------------------------------------- unrolled training
-int64_t hf_unroll_workspace_bytes(int B, int nx) {
-  if (B < 1 || nx < 1) return -1;
-  return hf::unroll_ws_bytes(B, nx);
-}
+// Each of the six operations (update / adjoint of FluxGNN and PureGNN, loss /
+// adjoint of PINN) has one body, *_impl(name, ex, ...): name is the called
+// entry point's, for messages; ex == false is the plain entry point (its kernel
+// instantiation, no conservation arguments), ex == true the _ex one.
 
-// the shape and Poisson-mode checks shared by hf_unroll_update / hf_unroll_adjoint (after the pointer checks)
-static int unroll_mode_args(const char *fn, int pm, int nx) {
-  if (pm != HF_POISSON_SPECTRAL && pm != HF_POISSON_TRIDIAG)
-    return fail(HF_EINVAL, std::string(fn) + ": unknown Poisson mode");
-  if (pm == HF_POISSON_TRIDIAG)
-    return fail(HF_EUNSUPPORTED, std::string(fn) + ": the tridiagonal Poisson mode has no adjoint here (spectral only)");
-  if (!hf::unroll_nx_ok(nx))
-    return fail(HF_EUNSUPPORTED, std::string(fn) + ": nx > 6144 (the tiled global-memory regime) is not supported");
-  return HF_OK;
-}
+// The _ex update / loss calls' conservation arguments as given; the plain calls pass none.
+struct ConsIn {
+  const float *lam;  // cons = (lam_e, lam_q), or NULL
+  float scale;
+  const double *ref;
+  float *coef;
+};
 
-int hf_unroll_update(const float *fe, const float *st, const float *x, const double *pc, int pm, int B, int nx, float c,
-                     float dt, float *st_next, float *nf_next, const float *target, const float *weights, float scale,
-                     float *loss, void *ws, int64_t ws_bytes, void *stream) {
-  if (B < 1 || nx < 1) return fail(HF_EINVAL, "hf_unroll_update: need B >= 1, nx >= 1");
-  if (!fe || !st || !x || !pc || !st_next || !ws) return fail(HF_EINVAL, "hf_unroll_update: NULL pointer");
-  if (target && (!weights || !loss))
-    return fail(HF_EINVAL, "hf_unroll_update: NULL weights or loss with a target");
-  if (st == st_next) return fail(HF_EINVAL, "hf_unroll_update: state and state_next must not alias");
-  if (ws_bytes < hf::unroll_ws_bytes(B, nx))
-    return fail(HF_EINVAL, "hf_unroll_update: workspace smaller than hf_unroll_workspace_bytes");
-  if (int rc = unroll_mode_args("hf_unroll_update", pm, nx)) return rc;
-  HF_CHECK_HIP(hf::launch_unroll_update(fe, st, x, pc, B, nx, c, dt, st_next, nf_next, target, weights, scale, loss, ws,
-                                        as_stream(stream)),
-               "hf_unroll_update");
-  return HF_OK;
-}
-
-int hf_unroll_adjoint(const float *st, const float *st_next, const float *target, const float *weights, float scale,
-                      const float *direct_next, const float *gnf_next, const double *pc, int pm, int B, int nx, float c,
-                      float dt, float *g_fe, float *direct, void *stream) {
-  if (B < 1 || nx < 1) return fail(HF_EINVAL, "hf_unroll_adjoint: need B >= 1, nx >= 1");
-  if (!st || !st_next || !target || !weights || !pc || !g_fe) return fail(HF_EINVAL, "hf_unroll_adjoint: NULL pointer");
-  if (int rc = unroll_mode_args("hf_unroll_adjoint", pm, nx)) return rc;
-  HF_CHECK_HIP(hf::launch_unroll_adjoint(st, st_next, target, weights, scale, direct_next, gnf_next, pc, B, nx, c, dt,
-                                         g_fe, direct, as_stream(stream)),
-               "hf_unroll_adjoint");
-  return HF_OK;
-}
-
-// The _ex calls' conservation arguments, checked alike (before any device call).  cons NULL: the
-// reference and coefficient buffers must be NULL too, and *out stays NULL (the plain call's work).
-static int cons_args(const char *name, const float *cons, float cons_scale, const double *ref, float *coef,
-                     const float *target, const void *ws, int64_t ws_bytes, int64_t need_ex, hf::ConsTerms *store,
-                     const hf::ConsTerms **out) {
+// ConsIn checked (before any device call).  cons NULL: the reference and coefficient buffers must
+// be NULL too, and *out stays NULL (the plain call's work).
+static int cons_args(const char *name, const ConsIn &in, const float *target, const void *ws, int64_t ws_bytes,
+                     int64_t need_ex, hf::ConsTerms *store, const hf::ConsTerms **out) {
   const std::string fn = name;
   *out = nullptr;
-  if (!cons) {
-    if (ref || coef) return fail(HF_EINVAL, fn + ": dev_cons_ref / dev_cons_coef given without cons");
+  if (!in.lam) {
+    if (in.ref || in.coef) return fail(HF_EINVAL, fn + ": dev_cons_ref / dev_cons_coef given without cons");
     return HF_OK;
   }
-  if (!(cons[0] >= 0.f) || !(cons[1] >= 0.f)) return fail(HF_EINVAL, fn + ": cons (lam_e, lam_q) must be >= 0");
-  if (!ref || !coef || !ws || !target)
+  if (!(in.lam[0] >= 0.f) || !(in.lam[1] >= 0.f)) return fail(HF_EINVAL, fn + ": cons (lam_e, lam_q) must be >= 0");
+  if (!in.ref || !in.coef || !ws || !target)
     return fail(HF_EINVAL, fn + ": cons needs dev_target, dev_cons_ref, dev_cons_coef and a workspace (NULL pointer)");
   if (ws_bytes < need_ex) return fail(HF_EINVAL, fn + ": workspace smaller than the _ex workspace query");
-  store->lam_e = cons[0], store->lam_q = cons[1], store->scale = cons_scale;
-  store->ref = ref, store->coef = coef;
+  store->lam_e = in.lam[0], store->lam_q = in.lam[1], store->scale = in.scale;
+  store->ref = in.ref, store->coef = in.coef;
   *out = store;
   return HF_OK;
 }
@@ -690,46 +657,92 @@ int hf_state_moments(const float *states, int64_t rows, int nx, double *moments,
   return HF_OK;
 }
 
+int64_t hf_unroll_workspace_bytes(int B, int nx) {
+  if (B < 1 || nx < 1) return -1;
+  return hf::unroll_ws_bytes(B, nx);
+}
+
 int64_t hf_unroll_workspace_bytes_ex(int B, int nx) {
   if (B < 1 || nx < 1) return -1;
   return hf::unroll_ws_bytes_ex(B, nx);
+}
+
+// the shape and Poisson-mode checks shared by the update and the adjoint (after the pointer checks)
+static int unroll_mode_args(const std::string &fn, int pm, int nx) {
+  if (pm != HF_POISSON_SPECTRAL && pm != HF_POISSON_TRIDIAG) return fail(HF_EINVAL, fn + ": unknown Poisson mode");
+  if (pm == HF_POISSON_TRIDIAG)
+    return fail(HF_EUNSUPPORTED, fn + ": the tridiagonal Poisson mode has no adjoint here (spectral only)");
+  if (!hf::unroll_nx_ok(nx))
+    return fail(HF_EUNSUPPORTED, fn + ": nx > 6144 (the tiled global-memory regime) is not supported");
+  return HF_OK;
+}
+
+static int unroll_update_impl(const char *name, bool ex, const float *fe, const float *st, const float *x,
+                              const double *pc, int pm, int B, int nx, float c, float dt, float *st_next,
+                              float *nf_next, const float *target, const float *weights, float scale, float *loss,
+                              void *ws, int64_t ws_bytes, const ConsIn &cons, void *stream) {
+  const std::string fn = name;
+  if (B < 1 || nx < 1) return fail(HF_EINVAL, fn + ": need B >= 1, nx >= 1");
+  if (!fe || !st || !x || !pc || !st_next || !ws) return fail(HF_EINVAL, fn + ": NULL pointer");
+  if (target && (!weights || !loss))
+    return fail(HF_EINVAL, fn + (ex ? ": NULL weights or losses with a target"
+                                    : ": NULL weights or loss with a target"));
+  if (st == st_next) return fail(HF_EINVAL, fn + ": state and state_next must not alias");
+  if (ws_bytes < hf::unroll_ws_bytes(B, nx))
+    return fail(HF_EINVAL, fn + ": workspace smaller than hf_unroll_workspace_bytes");
+  hf::ConsTerms ct{};
+  const hf::ConsTerms *cp = nullptr;
+  if (ex)
+    if (int rc = cons_args(name, cons, target, ws, ws_bytes, hf::unroll_ws_bytes_ex(B, nx), &ct, &cp)) return rc;
+  if (int rc = unroll_mode_args(fn, pm, nx)) return rc;
+  HF_CHECK_HIP(hf::launch_unroll_update(ex, fe, st, x, pc, B, nx, c, dt, st_next, nf_next, target, weights, scale, loss,
+                                        ws, cp, as_stream(stream)),
+               name);
+  return HF_OK;
+}
+
+int hf_unroll_update(const float *fe, const float *st, const float *x, const double *pc, int pm, int B, int nx, float c,
+                     float dt, float *st_next, float *nf_next, const float *target, const float *weights, float scale,
+                     float *loss, void *ws, int64_t ws_bytes, void *stream) {
+  return unroll_update_impl("hf_unroll_update", false, fe, st, x, pc, pm, B, nx, c, dt, st_next, nf_next, target,
+                            weights, scale, loss, ws, ws_bytes, ConsIn{}, stream);
 }
 
 int hf_unroll_update_ex(const float *fe, const float *st, const float *x, const double *pc, int pm, int B, int nx,
                         float c, float dt, float *st_next, float *nf_next, const float *target, const float *weights,
                         float scale, float *losses, void *ws, int64_t ws_bytes, const float *cons, float cons_scale,
                         const double *cons_ref, float *cons_coef, void *stream) {
-  const char *fn = "hf_unroll_update_ex";
-  if (B < 1 || nx < 1) return fail(HF_EINVAL, "hf_unroll_update_ex: need B >= 1, nx >= 1");
-  if (!fe || !st || !x || !pc || !st_next || !ws) return fail(HF_EINVAL, "hf_unroll_update_ex: NULL pointer");
-  if (target && (!weights || !losses))
-    return fail(HF_EINVAL, "hf_unroll_update_ex: NULL weights or losses with a target");
-  if (st == st_next) return fail(HF_EINVAL, "hf_unroll_update_ex: state and state_next must not alias");
-  if (ws_bytes < hf::unroll_ws_bytes(B, nx))
-    return fail(HF_EINVAL, "hf_unroll_update_ex: workspace smaller than hf_unroll_workspace_bytes");
-  hf::ConsTerms ct{};
-  const hf::ConsTerms *cp = nullptr;
-  if (int rc = cons_args(fn, cons, cons_scale, cons_ref, cons_coef, target, ws, ws_bytes, hf::unroll_ws_bytes_ex(B, nx),
-                         &ct, &cp))
-    return rc;
+  return unroll_update_impl("hf_unroll_update_ex", true, fe, st, x, pc, pm, B, nx, c, dt, st_next, nf_next, target,
+                            weights, scale, losses, ws, ws_bytes, ConsIn{cons, cons_scale, cons_ref, cons_coef},
+                            stream);
+}
+
+static int unroll_adjoint_impl(const char *name, bool ex, const float *st, const float *st_next, const float *target,
+                               const float *weights, float scale, const float *direct_next, const float *gnf_next,
+                               const double *pc, int pm, int B, int nx, float c, float dt, float *g_fe, float *direct,
+                               const float *cons_coef, void *stream) {
+  const std::string fn = name;
+  if (B < 1 || nx < 1) return fail(HF_EINVAL, fn + ": need B >= 1, nx >= 1");
+  if (!st || !st_next || !target || !weights || !pc || !g_fe) return fail(HF_EINVAL, fn + ": NULL pointer");
   if (int rc = unroll_mode_args(fn, pm, nx)) return rc;
-  HF_CHECK_HIP(hf::launch_unroll_update_ex(fe, st, x, pc, B, nx, c, dt, st_next, nf_next, target, weights, scale, losses,
-                                           ws, cp, as_stream(stream)),
-               fn);
+  HF_CHECK_HIP(hf::launch_unroll_adjoint(ex, st, st_next, target, weights, scale, direct_next, gnf_next, pc, B, nx, c,
+                                         dt, g_fe, direct, cons_coef, as_stream(stream)),
+               name);
   return HF_OK;
+}
+
+int hf_unroll_adjoint(const float *st, const float *st_next, const float *target, const float *weights, float scale,
+                      const float *direct_next, const float *gnf_next, const double *pc, int pm, int B, int nx, float c,
+                      float dt, float *g_fe, float *direct, void *stream) {
+  return unroll_adjoint_impl("hf_unroll_adjoint", false, st, st_next, target, weights, scale, direct_next, gnf_next, pc,
+                             pm, B, nx, c, dt, g_fe, direct, nullptr, stream);
 }
 
 int hf_unroll_adjoint_ex(const float *st, const float *st_next, const float *target, const float *weights, float scale,
                          const float *direct_next, const float *gnf_next, const double *pc, int pm, int B, int nx,
                          float c, float dt, float *g_fe, float *direct, const float *cons_coef, void *stream) {
-  if (B < 1 || nx < 1) return fail(HF_EINVAL, "hf_unroll_adjoint_ex: need B >= 1, nx >= 1");
-  if (!st || !st_next || !target || !weights || !pc || !g_fe)
-    return fail(HF_EINVAL, "hf_unroll_adjoint_ex: NULL pointer");
-  if (int rc = unroll_mode_args("hf_unroll_adjoint_ex", pm, nx)) return rc;
-  HF_CHECK_HIP(hf::launch_unroll_adjoint_ex(st, st_next, target, weights, scale, direct_next, gnf_next, pc, B, nx, c, dt,
-                                            g_fe, direct, cons_coef, as_stream(stream)),
-               "hf_unroll_adjoint_ex");
-  return HF_OK;
+  return unroll_adjoint_impl("hf_unroll_adjoint_ex", true, st, st_next, target, weights, scale, direct_next, gnf_next,
+                             pc, pm, B, nx, c, dt, g_fe, direct, cons_coef, stream);
 }
 
 // ------------------------------------------------------- unrolled training, PureGNN
@@ -738,79 +751,77 @@ int64_t hf_pure_unroll_workspace_bytes(int B, int nx) {
   return hf::pure_unroll_ws_bytes(B, nx);
 }
 
-int hf_pure_unroll_update(const float *delta, const float *st, const float *x, int B, int nx, float *st_next,
-                          float *nf_next, const float *target, const float *weights, float scale, float *loss, void *ws,
-                          int64_t ws_bytes, void *stream) {
-  if (B < 1 || nx < 1) return fail(HF_EINVAL, "hf_pure_unroll_update: need B >= 1, nx >= 1");
-  if (!delta || !st || !x || !st_next) return fail(HF_EINVAL, "hf_pure_unroll_update: NULL pointer");
-  if (st == st_next) return fail(HF_EINVAL, "hf_pure_unroll_update: state and state_next must not alias");
-  if (!hf::pure_unroll_shape_ok(B, nx)) return fail(HF_EINVAL, "hf_pure_unroll_update: B * ceil(nx / 1024) >= 2^31");
-  if (target) {
-    if (!weights || !loss || !ws)
-      return fail(HF_EINVAL, "hf_pure_unroll_update: NULL weights, loss or workspace with a target");
-    if (ws_bytes < hf::pure_unroll_ws_bytes(B, nx))
-      return fail(HF_EINVAL, "hf_pure_unroll_update: workspace smaller than hf_pure_unroll_workspace_bytes");
-  }
-  HF_CHECK_HIP(hf::launch_pure_unroll_update(delta, st, x, B, nx, st_next, nf_next, target, weights, scale, loss, ws,
-                                             as_stream(stream)),
-               "hf_pure_unroll_update");
-  return HF_OK;
-}
-
-int hf_pure_unroll_adjoint(const float *st_next, const float *target, const float *weights, float scale,
-                           const float *gd_next, const float *gnf_next, int B, int nx, float *gd, void *stream) {
-  if (B < 1 || nx < 1) return fail(HF_EINVAL, "hf_pure_unroll_adjoint: need B >= 1, nx >= 1");
-  if (!st_next || !target || !weights || !gd) return fail(HF_EINVAL, "hf_pure_unroll_adjoint: NULL pointer");
-  if (!hf::pure_unroll_shape_ok(B, nx)) return fail(HF_EINVAL, "hf_pure_unroll_adjoint: B * ceil(nx / 1024) >= 2^31");
-  HF_CHECK_HIP(hf::launch_pure_unroll_adjoint(st_next, target, weights, scale, gd_next, gnf_next, B, nx, gd,
-                                              as_stream(stream)),
-               "hf_pure_unroll_adjoint");
-  return HF_OK;
-}
-
 int64_t hf_pure_unroll_workspace_bytes_ex(int B, int nx) {
   if (!hf::pure_unroll_shape_ok(B, nx)) return -1;
   return hf::pure_unroll_ws_bytes_ex(B, nx);
+}
+
+static int pure_unroll_update_impl(const char *name, bool ex, const float *delta, const float *st, const float *x,
+                                   int B, int nx, float *st_next, float *nf_next, const float *target,
+                                   const float *weights, float scale, float *loss, void *ws, int64_t ws_bytes,
+                                   const ConsIn &cons, void *stream) {
+  const std::string fn = name;
+  if (B < 1 || nx < 1) return fail(HF_EINVAL, fn + ": need B >= 1, nx >= 1");
+  if (!delta || !st || !x || !st_next) return fail(HF_EINVAL, fn + ": NULL pointer");
+  if (st == st_next) return fail(HF_EINVAL, fn + ": state and state_next must not alias");
+  if (!hf::pure_unroll_shape_ok(B, nx)) return fail(HF_EINVAL, fn + ": B * ceil(nx / 1024) >= 2^31");
+  if (target) {
+    if (!weights || !loss || !ws)
+      return fail(HF_EINVAL, fn + (ex ? ": NULL weights, losses or workspace with a target"
+                                      : ": NULL weights, loss or workspace with a target"));
+    if (ws_bytes < hf::pure_unroll_ws_bytes(B, nx))
+      return fail(HF_EINVAL, fn + ": workspace smaller than hf_pure_unroll_workspace_bytes");
+  }
+  hf::ConsTerms ct{};
+  const hf::ConsTerms *cp = nullptr;
+  if (ex)
+    if (int rc = cons_args(name, cons, target, ws, ws_bytes, hf::pure_unroll_ws_bytes_ex(B, nx), &ct, &cp)) return rc;
+  HF_CHECK_HIP(hf::launch_pure_unroll_update(ex, delta, st, x, B, nx, st_next, nf_next, target, weights, scale, loss,
+                                             ws, cp, as_stream(stream)),
+               name);
+  return HF_OK;
+}
+
+int hf_pure_unroll_update(const float *delta, const float *st, const float *x, int B, int nx, float *st_next,
+                          float *nf_next, const float *target, const float *weights, float scale, float *loss, void *ws,
+                          int64_t ws_bytes, void *stream) {
+  return pure_unroll_update_impl("hf_pure_unroll_update", false, delta, st, x, B, nx, st_next, nf_next, target, weights,
+                                 scale, loss, ws, ws_bytes, ConsIn{}, stream);
 }
 
 int hf_pure_unroll_update_ex(const float *delta, const float *st, const float *x, int B, int nx, float *st_next,
                              float *nf_next, const float *target, const float *weights, float scale, float *losses,
                              void *ws, int64_t ws_bytes, const float *cons, float cons_scale, const double *cons_ref,
                              float *cons_coef, void *stream) {
-  const char *fn = "hf_pure_unroll_update_ex";
-  if (B < 1 || nx < 1) return fail(HF_EINVAL, "hf_pure_unroll_update_ex: need B >= 1, nx >= 1");
-  if (!delta || !st || !x || !st_next) return fail(HF_EINVAL, "hf_pure_unroll_update_ex: NULL pointer");
-  if (st == st_next) return fail(HF_EINVAL, "hf_pure_unroll_update_ex: state and state_next must not alias");
-  if (!hf::pure_unroll_shape_ok(B, nx))
-    return fail(HF_EINVAL, "hf_pure_unroll_update_ex: B * ceil(nx / 1024) >= 2^31");
-  if (target) {
-    if (!weights || !losses || !ws)
-      return fail(HF_EINVAL, "hf_pure_unroll_update_ex: NULL weights, losses or workspace with a target");
-    if (ws_bytes < hf::pure_unroll_ws_bytes(B, nx))
-      return fail(HF_EINVAL, "hf_pure_unroll_update_ex: workspace smaller than hf_pure_unroll_workspace_bytes");
-  }
-  hf::ConsTerms ct{};
-  const hf::ConsTerms *cp = nullptr;
-  if (int rc = cons_args(fn, cons, cons_scale, cons_ref, cons_coef, target, ws, ws_bytes,
-                         hf::pure_unroll_ws_bytes_ex(B, nx), &ct, &cp))
-    return rc;
-  HF_CHECK_HIP(hf::launch_pure_unroll_update_ex(delta, st, x, B, nx, st_next, nf_next, target, weights, scale, losses, ws,
-                                                cp, as_stream(stream)),
-               fn);
+  return pure_unroll_update_impl("hf_pure_unroll_update_ex", true, delta, st, x, B, nx, st_next, nf_next, target,
+                                 weights, scale, losses, ws, ws_bytes, ConsIn{cons, cons_scale, cons_ref, cons_coef},
+                                 stream);
+}
+
+static int pure_unroll_adjoint_impl(const char *name, bool ex, const float *st_next, const float *target,
+                                    const float *weights, float scale, const float *gd_next, const float *gnf_next,
+                                    int B, int nx, float *gd, const float *cons_coef, void *stream) {
+  const std::string fn = name;
+  if (B < 1 || nx < 1) return fail(HF_EINVAL, fn + ": need B >= 1, nx >= 1");
+  if (!st_next || !target || !weights || !gd) return fail(HF_EINVAL, fn + ": NULL pointer");
+  if (!hf::pure_unroll_shape_ok(B, nx)) return fail(HF_EINVAL, fn + ": B * ceil(nx / 1024) >= 2^31");
+  HF_CHECK_HIP(hf::launch_pure_unroll_adjoint(ex, st_next, target, weights, scale, gd_next, gnf_next, B, nx, gd,
+                                              cons_coef, as_stream(stream)),
+               name);
   return HF_OK;
+}
+
+int hf_pure_unroll_adjoint(const float *st_next, const float *target, const float *weights, float scale,
+                           const float *gd_next, const float *gnf_next, int B, int nx, float *gd, void *stream) {
+  return pure_unroll_adjoint_impl("hf_pure_unroll_adjoint", false, st_next, target, weights, scale, gd_next, gnf_next,
+                                  B, nx, gd, nullptr, stream);
 }
 
 int hf_pure_unroll_adjoint_ex(const float *st_next, const float *target, const float *weights, float scale,
                               const float *gd_next, const float *gnf_next, int B, int nx, float *gd,
                               const float *cons_coef, void *stream) {
-  if (B < 1 || nx < 1) return fail(HF_EINVAL, "hf_pure_unroll_adjoint_ex: need B >= 1, nx >= 1");
-  if (!st_next || !target || !weights || !gd) return fail(HF_EINVAL, "hf_pure_unroll_adjoint_ex: NULL pointer");
-  if (!hf::pure_unroll_shape_ok(B, nx))
-    return fail(HF_EINVAL, "hf_pure_unroll_adjoint_ex: B * ceil(nx / 1024) >= 2^31");
-  HF_CHECK_HIP(hf::launch_pure_unroll_adjoint_ex(st_next, target, weights, scale, gd_next, gnf_next, B, nx, gd, cons_coef,
-                                                 as_stream(stream)),
-               "hf_pure_unroll_adjoint_ex");
-  return HF_OK;
+  return pure_unroll_adjoint_impl("hf_pure_unroll_adjoint_ex", true, st_next, target, weights, scale, gd_next, gnf_next,
+                                  B, nx, gd, cons_coef, stream);
 }
 
 // ------------------------------------------------------- PureGNN / PINN
@@ -1055,16 +1066,60 @@ static int pinn_unroll_args(const char *name, const float *pred, const float *st
   return HF_OK;
 }
 
-int hf_pinn_unroll_loss(const float *pred, const float *state, const float *target, int B, int nx, const float *weights,
-                        float loss_scale, const float *phys, float phys_scale, double dt, double dx, double nu,
-                        const double *plan, float *losses, void *ws, int64_t ws_bytes, void *stream) {
-  const char *fn = "hf_pinn_unroll_loss";
+int64_t hf_pinn_unroll_workspace_bytes_ex(int B, int nx) {
+  if (B < 1 || nx < 1) return -1;
+  return hf::pinn_unroll_ws_bytes_ex(B, nx);
+}
+
+static int pinn_unroll_loss_impl(const char *fn, bool ex, const float *pred, const float *state, const float *target,
+                                 int B, int nx, const float *weights, float loss_scale, const float *phys,
+                                 float phys_scale, double dt, double dx, double nu, const double *plan, float *losses,
+                                 void *ws, int64_t ws_bytes, const ConsIn &cons, void *stream) {
   if (int rc = pinn_unroll_args(fn, pred, state, target, B, nx, weights, phys, dt, dx, plan)) return rc;
   if (!losses || !ws) return fail(HF_EINVAL, std::string(fn) + ": NULL pointer");
   if (ws_bytes < hf::pinn_unroll_ws_bytes(B, nx))
     return fail(HF_EINVAL, std::string(fn) + ": workspace smaller than hf_pinn_unroll_workspace_bytes");
-  HF_CHECK_HIP(hf::launch_pinn_unroll_loss(pred, state, target, B, nx, weights, loss_scale, phys, phys_scale, dt, dx, nu,
-                                           plan, losses, ws, as_stream(stream)),
+  hf::ConsTerms ct{};
+  const hf::ConsTerms *cp = nullptr;
+  if (ex)
+    if (int rc = cons_args(fn, cons, target, ws, ws_bytes, hf::pinn_unroll_ws_bytes_ex(B, nx), &ct, &cp)) return rc;
+  HF_CHECK_HIP(hf::launch_pinn_unroll_loss(ex, pred, state, target, B, nx, weights, loss_scale, phys, phys_scale, dt,
+                                           dx, nu, plan, losses, ws, cp, as_stream(stream)),
+               fn);
+  return HF_OK;
+}
+
+int hf_pinn_unroll_loss(const float *pred, const float *state, const float *target, int B, int nx, const float *weights,
+                        float loss_scale, const float *phys, float phys_scale, double dt, double dx, double nu,
+                        const double *plan, float *losses, void *ws, int64_t ws_bytes, void *stream) {
+  return pinn_unroll_loss_impl("hf_pinn_unroll_loss", false, pred, state, target, B, nx, weights, loss_scale, phys,
+                               phys_scale, dt, dx, nu, plan, losses, ws, ws_bytes, ConsIn{}, stream);
+}
+
+int hf_pinn_unroll_loss_ex(const float *pred, const float *state, const float *target, int B, int nx,
+                           const float *weights, float loss_scale, const float *phys, float phys_scale, double dt,
+                           double dx, double nu, const double *plan, float *losses, void *ws, int64_t ws_bytes,
+                           const float *cons, float cons_scale, const double *cons_ref, float *cons_coef,
+                           void *stream) {
+  return pinn_unroll_loss_impl("hf_pinn_unroll_loss_ex", true, pred, state, target, B, nx, weights, loss_scale, phys,
+                               phys_scale, dt, dx, nu, plan, losses, ws, ws_bytes,
+                               ConsIn{cons, cons_scale, cons_ref, cons_coef}, stream);
+}
+
+static int pinn_unroll_adjoint_impl(const char *fn, bool ex, const float *pred, const float *state, const float *target,
+                                    const float *pred_next, const float *grad_state_next, int B, int nx,
+                                    const float *weights, float loss_scale, const float *phys, float phys_scale,
+                                    double dt, double dx, double nu, const double *plan, float *grad_out,
+                                    const float *cons_coef, void *stream) {
+  if (int rc = pinn_unroll_args(fn, pred, state, target, B, nx, weights, phys, dt, dx, plan)) return rc;
+  if (!grad_out) return fail(HF_EINVAL, std::string(fn) + ": NULL pointer");
+  // every phase reads the inputs after the first values of dev_grad_out are written
+  // (cons_coef is NULL from the plain entry point, and grad_out is not)
+  for (const float *in : {pred, state, target, pred_next, grad_state_next, cons_coef})
+    if (in == grad_out) return fail(HF_EINVAL, std::string(fn) + ": dev_grad_out must not alias an input");
+  HF_CHECK_HIP(hf::launch_pinn_unroll_adjoint(ex, pred, state, target, pred_next, grad_state_next, B, nx, weights,
+                                              loss_scale, phys, phys_scale, dt, dx, nu, plan, grad_out, cons_coef,
+                                              as_stream(stream)),
                fn);
   return HF_OK;
 }
@@ -1073,60 +1128,18 @@ int hf_pinn_unroll_adjoint(const float *pred, const float *state, const float *t
                            const float *grad_state_next, int B, int nx, const float *weights, float loss_scale,
                            const float *phys, float phys_scale, double dt, double dx, double nu, const double *plan,
                            float *grad_out, void *stream) {
-  const char *fn = "hf_pinn_unroll_adjoint";
-  if (int rc = pinn_unroll_args(fn, pred, state, target, B, nx, weights, phys, dt, dx, plan)) return rc;
-  if (!grad_out) return fail(HF_EINVAL, std::string(fn) + ": NULL pointer");
-  // every phase reads the inputs after the first values of dev_grad_out are written
-  for (const float *in : {pred, state, target, pred_next, grad_state_next})
-    if (in == grad_out) return fail(HF_EINVAL, std::string(fn) + ": dev_grad_out must not alias an input");
-  HF_CHECK_HIP(hf::launch_pinn_unroll_adjoint(pred, state, target, pred_next, grad_state_next, B, nx, weights,
-                                              loss_scale, phys, phys_scale, dt, dx, nu, plan, grad_out,
-                                              as_stream(stream)),
-               fn);
-  return HF_OK;
-}
-
-int64_t hf_pinn_unroll_workspace_bytes_ex(int B, int nx) {
-  if (B < 1 || nx < 1) return -1;
-  return hf::pinn_unroll_ws_bytes_ex(B, nx);
-}
-
-int hf_pinn_unroll_loss_ex(const float *pred, const float *state, const float *target, int B, int nx,
-                           const float *weights, float loss_scale, const float *phys, float phys_scale, double dt,
-                           double dx, double nu, const double *plan, float *losses, void *ws, int64_t ws_bytes,
-                           const float *cons, float cons_scale, const double *cons_ref, float *cons_coef,
-                           void *stream) {
-  const char *fn = "hf_pinn_unroll_loss_ex";
-  if (int rc = pinn_unroll_args(fn, pred, state, target, B, nx, weights, phys, dt, dx, plan)) return rc;
-  if (!losses || !ws) return fail(HF_EINVAL, std::string(fn) + ": NULL pointer");
-  if (ws_bytes < hf::pinn_unroll_ws_bytes(B, nx))
-    return fail(HF_EINVAL, std::string(fn) + ": workspace smaller than hf_pinn_unroll_workspace_bytes");
-  hf::ConsTerms ct{};
-  const hf::ConsTerms *cp = nullptr;
-  if (int rc = cons_args(fn, cons, cons_scale, cons_ref, cons_coef, target, ws, ws_bytes,
-                         hf::pinn_unroll_ws_bytes_ex(B, nx), &ct, &cp))
-    return rc;
-  HF_CHECK_HIP(hf::launch_pinn_unroll_loss_ex(pred, state, target, B, nx, weights, loss_scale, phys, phys_scale, dt, dx,
-                                              nu, plan, losses, ws, cp, as_stream(stream)),
-               fn);
-  return HF_OK;
+  return pinn_unroll_adjoint_impl("hf_pinn_unroll_adjoint", false, pred, state, target, pred_next, grad_state_next, B,
+                                  nx, weights, loss_scale, phys, phys_scale, dt, dx, nu, plan, grad_out, nullptr,
+                                  stream);
 }
 
 int hf_pinn_unroll_adjoint_ex(const float *pred, const float *state, const float *target, const float *pred_next,
                               const float *grad_state_next, int B, int nx, const float *weights, float loss_scale,
                               const float *phys, float phys_scale, double dt, double dx, double nu, const double *plan,
                               float *grad_out, const float *cons_coef, void *stream) {
-  const char *fn = "hf_pinn_unroll_adjoint_ex";
-  if (int rc = pinn_unroll_args(fn, pred, state, target, B, nx, weights, phys, dt, dx, plan)) return rc;
-  if (!grad_out) return fail(HF_EINVAL, std::string(fn) + ": NULL pointer");
-  // every phase reads the inputs after the first values of dev_grad_out are written
-  for (const float *in : {pred, state, target, pred_next, grad_state_next, cons_coef})
-    if (in == grad_out) return fail(HF_EINVAL, std::string(fn) + ": dev_grad_out must not alias an input");
-  HF_CHECK_HIP(hf::launch_pinn_unroll_adjoint_ex(pred, state, target, pred_next, grad_state_next, B, nx, weights,
-                                                 loss_scale, phys, phys_scale, dt, dx, nu, plan, grad_out, cons_coef,
-                                                 as_stream(stream)),
-               fn);
-  return HF_OK;
+  return pinn_unroll_adjoint_impl("hf_pinn_unroll_adjoint_ex", true, pred, state, target, pred_next, grad_state_next, B,
+                                  nx, weights, loss_scale, phys, phys_scale, dt, dx, nu, plan, grad_out, cons_coef,
+                                  stream);
 }
 
 int hf_poisson_plan_len(int nx) { return nx < 1 ? -1 : hf::poisson_plan_len(nx); }

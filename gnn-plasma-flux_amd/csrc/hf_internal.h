@@ -327,6 +327,12 @@ struct ConsTerms {
   float *coef;
 };
 
+// The six unrolled-training launchers below all take `bool ex` first: false is
+// the plain entry points' kernel instantiation (cons / coef not read), true the
+// _ex entry points' (the wider loss row; the energy and charge terms when cons
+// / coef is given, and with it NULL the plain instantiation's bits from the
+// other kernel).  The shared device helpers are unroll_common.h's.
+//
 // Unrolled training (unroll.hip): one hybrid step from the FluxGNN's edge flux
 // fe [B][2nx] with the step's extras, and its adjoint; spectral Poisson,
 // nx <= kFvLdsMaxNx (unroll_nx_ok).  Contiguous [B][3][nx] states.
@@ -334,30 +340,25 @@ struct ConsTerms {
 //           for bit; nf_next [B*nx][4] = [n', u', E', x] (or NULL); with target
 //           [B][3][nx]: loss[0] = scale * sum w_ch (st_next - target)^2, summed
 //           in a fixed order through ws (unroll_ws_bytes; w: 3 host floats).
+//           ex: loss[4] = (total, state, energy, charge), ws of
+//           unroll_ws_bytes_ex with cons.
 //  adjoint: g = direct_next + gnf_next[:, 0:3]^T (each or NULL) + 2 w scale
 //           (st_next - target) is dL/d st_next; writes g_fe [B][2nx] = dL/d fe
 //           and direct [B][3][nx] (or NULL) = the part of dL/d st that does not
-//           pass through the FluxGNN.
+//           pass through the FluxGNN.  ex with coef: the seed of u', E' gains
+//           coef[b][0] u', coef[b][0] E' (cq is not added: no gradient through
+//           the conservative update).
 bool unroll_nx_ok(int nx);
 int64_t unroll_ws_bytes(int B, int nx);
-hipError_t launch_unroll_update(const float *fe, const float *st, const float *x, const double *pc, int B, int nx,
-                                float c, float dt, float *st_next, float *nf_next, const float *target, const float *w,
-                                float scale, float *loss, void *ws, hipStream_t s);
-hipError_t launch_unroll_adjoint(const float *st, const float *st_next, const float *target, const float *w, float scale,
-                                 const float *direct_next, const float *gnf_next, const double *pc, int B, int nx,
-                                 float c, float dt, float *g_fe, float *direct, hipStream_t s);
-//  _ex:     losses[4] = (total, state, energy, charge), ws of unroll_ws_bytes_ex
-//           with cons; the adjoint's seed of u', E' gains coef[b][0] u', coef[b][0] E'
-//           (cq is not added: no gradient through the conservative update).  cons /
-//           coef NULL: the plain calls' bits.
 int64_t unroll_ws_bytes_ex(int B, int nx);
-hipError_t launch_unroll_update_ex(const float *fe, const float *st, const float *x, const double *pc, int B, int nx,
-                                   float c, float dt, float *st_next, float *nf_next, const float *target, const float *w,
-                                   float scale, float *losses, void *ws, const ConsTerms *cons, hipStream_t s);
-hipError_t launch_unroll_adjoint_ex(const float *st, const float *st_next, const float *target, const float *w,
-                                    float scale, const float *direct_next, const float *gnf_next, const double *pc, int B,
-                                    int nx, float c, float dt, float *g_fe, float *direct, const float *coef,
-                                    hipStream_t s);
+hipError_t launch_unroll_update(bool ex, const float *fe, const float *st, const float *x, const double *pc, int B,
+                                int nx, float c, float dt, float *st_next, float *nf_next, const float *target,
+                                const float *w, float scale, float *loss, void *ws, const ConsTerms *cons,
+                                hipStream_t s);
+hipError_t launch_unroll_adjoint(bool ex, const float *st, const float *st_next, const float *target, const float *w,
+                                 float scale, const float *direct_next, const float *gnf_next, const double *pc, int B,
+                                 int nx, float c, float dt, float *g_fe, float *direct, const float *coef,
+                                 hipStream_t s);
 
 // Unrolled training of PureGNN (pure_unroll.hip): the residual update of one
 // rollout step from PureGNN's delta [B*nx][3] with the step's extras, and its
@@ -366,58 +367,44 @@ hipError_t launch_unroll_adjoint_ex(const float *st, const float *st_next, const
 //           add); nf_next [B*nx][4] = [n', u', E', x] (or NULL); with target
 //           [B][3][nx]: loss[0] = scale * sum w_ch (st_next - target)^2, summed
 //           in a fixed order through ws (pure_unroll_ws_bytes; w: 3 host floats).
+//           ex: loss[4] = (total, state, energy, charge), ws of
+//           pure_unroll_ws_bytes_ex with cons.
 //  adjoint: gd[b*nx+i][ch] = (2 w_ch scale (st_next - target)[b][ch][i] +
 //           gd_next[b*nx+i][ch]) + gnf_next[b*nx+i][ch] (gd_next [B*nx][3],
-//           gnf_next [B*nx][4], each or NULL: the term is left out).
+//           gnf_next [B*nx][4], each or NULL: the term is left out).  ex with
+//           coef: the seed gains (cq, ce u', ce E').
 bool pure_unroll_shape_ok(int B, int nx);  // B, nx >= 1 and at most 2^31 - 1 tiles of 1024 cells
 int64_t pure_unroll_ws_bytes(int B, int nx);
-hipError_t launch_pure_unroll_update(const float *delta, const float *st, const float *x, int B, int nx, float *st_next,
-                                     float *nf_next, const float *target, const float *w, float scale, float *loss,
-                                     void *ws, hipStream_t s);
-hipError_t launch_pure_unroll_adjoint(const float *st_next, const float *target, const float *w, float scale,
-                                      const float *gd_next, const float *gnf_next, int B, int nx, float *gd,
-                                      hipStream_t s);
-//  _ex:     losses[4] = (total, state, energy, charge), ws of
-//           pure_unroll_ws_bytes_ex with cons; the adjoint's seed gains (cq, ce u',
-//           ce E').  cons / coef NULL: the plain calls' bits.
 int64_t pure_unroll_ws_bytes_ex(int B, int nx);
-hipError_t launch_pure_unroll_update_ex(const float *delta, const float *st, const float *x, int B, int nx,
-                                        float *st_next, float *nf_next, const float *target, const float *w, float scale,
-                                        float *losses, void *ws, const ConsTerms *cons, hipStream_t s);
-hipError_t launch_pure_unroll_adjoint_ex(const float *st_next, const float *target, const float *w, float scale,
-                                         const float *gd_next, const float *gnf_next, int B, int nx, float *gd,
-                                         const float *coef, hipStream_t s);
+hipError_t launch_pure_unroll_update(bool ex, const float *delta, const float *st, const float *x, int B, int nx,
+                                     float *st_next, float *nf_next, const float *target, const float *w, float scale,
+                                     float *loss, void *ws, const ConsTerms *cons, hipStream_t s);
+hipError_t launch_pure_unroll_adjoint(bool ex, const float *st_next, const float *target, const float *w, float scale,
+                                      const float *gd_next, const float *gnf_next, int B, int nx, float *gd,
+                                      const float *coef, hipStream_t s);
 
 // Unrolled training of PINN (pinn_unroll.hip): the loss term of one rollout
 // step and the gradient its hf_pinn_backward takes in; include/hybridflux.h has
 // the formulas.  Contiguous [B][3][nx] states, nx <= kFvLdsMaxNx, B >= 1.
 //  loss:    losses[5] = (total, data, cont, mom, pois) of pred against target,
 //           residuals on (pred, state); phys (3 host floats) NULL: data only,
-//           state and pc not read.  ws: pinn_unroll_ws_bytes.
+//           state and pc not read.  ws: pinn_unroll_ws_bytes.  ex: losses[7] =
+//           (..., energy, charge), ws of pinn_unroll_ws_bytes_ex with cons.
 //  adjoint: grad_out = d term / d pred + d next term / d (state slot) (with
-//           phys and pred_next) + grad_state_next (or NULL: left out).
+//           phys and pred_next) + grad_state_next (or NULL: left out).  ex with
+//           coef: d term / d pred gains (cq, ce p_u, ce p_E).
 bool pinn_unroll_nx_ok(int nx);
 int64_t pinn_unroll_ws_bytes(int B, int nx);
-hipError_t launch_pinn_unroll_loss(const float *pred, const float *state, const float *target, int B, int nx,
-                                   const float *w, float scale, const float *phys, float phys_scale, double dt,
-                                   double dx, double nu, const double *pc, float *losses, void *ws, hipStream_t s);
-hipError_t launch_pinn_unroll_adjoint(const float *pred, const float *state, const float *target, const float *pred_next,
-                                      const float *grad_state_next, int B, int nx, const float *w, float scale,
-                                      const float *phys, float phys_scale, double dt, double dx, double nu,
-                                      const double *pc, float *grad_out, hipStream_t s);
-//  _ex:     losses[7] = (total, data, cont, mom, pois, energy, charge), ws of
-//           pinn_unroll_ws_bytes_ex with cons; d term / d pred gains (cq, ce p_u,
-//           ce p_E).  cons / coef NULL: the plain calls' bits.
 int64_t pinn_unroll_ws_bytes_ex(int B, int nx);
-hipError_t launch_pinn_unroll_loss_ex(const float *pred, const float *state, const float *target, int B, int nx,
+hipError_t launch_pinn_unroll_loss(bool ex, const float *pred, const float *state, const float *target, int B, int nx,
+                                   const float *w, float scale, const float *phys, float phys_scale, double dt,
+                                   double dx, double nu, const double *pc, float *losses, void *ws,
+                                   const ConsTerms *cons, hipStream_t s);
+hipError_t launch_pinn_unroll_adjoint(bool ex, const float *pred, const float *state, const float *target,
+                                      const float *pred_next, const float *grad_state_next, int B, int nx,
                                       const float *w, float scale, const float *phys, float phys_scale, double dt,
-                                      double dx, double nu, const double *pc, float *losses, void *ws,
-                                      const ConsTerms *cons, hipStream_t s);
-hipError_t launch_pinn_unroll_adjoint_ex(const float *pred, const float *state, const float *target,
-                                         const float *pred_next, const float *grad_state_next, int B, int nx,
-                                         const float *w, float scale, const float *phys, float phys_scale, double dt,
-                                         double dx, double nu, const double *pc, float *grad_out, const float *coef,
-                                         hipStream_t s);
+                                      double dx, double nu, const double *pc, float *grad_out, const float *coef,
+                                      hipStream_t s);
 
 // The whole classical rollout (T steps of launch_fv_step's classical update)
 // in one launch, states held in registers: FFT nx up to 1024 (fv_run_fused).

@@ -32,6 +32,7 @@
 #include "hf_device.h"
 #include "hf_internal.h"
 #include "tgemm.h"
+#include "unroll_common.h"
 
 namespace hf {
 namespace {
@@ -195,12 +196,6 @@ struct PinnLossArgs {
   float *losses, *g;
 };
 
-__device__ __forceinline__ double wave_sum_f64(double a) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) a += __shfl_xor(a, o, 64);
-  return a;
-}
-
 // LDS: c[nx] (double) | p_n - 1, r~ (float)
 inline size_t pinn_loss_lds_bytes(int nx) { return (size_t)nx * (sizeof(double) + 2 * sizeof(float)); }
 
@@ -243,34 +238,27 @@ __global__ __launch_bounds__(kLossThreads) void pinn_loss_kernel(PinnLossArgs a)
   // dL/dp_n -= (2 w_p / N1) (P r~)   (P^T = -P; this thread's own store above)
   for (int i = threadIdx.x; i < nx; i += kLossThreads)
     G[i] = (float)((double)G[i] - a.gp * (double)poisson_cell(Lrt, Lc, i, nx));
-  sd = wave_sum_f64(sd);
-  sc = wave_sum_f64(sc);
-  sm = wave_sum_f64(sm);
-  sp = wave_sum_f64(sp);
+  sd = wave_sum(sd);
+  sc = wave_sum(sc);
+  sm = wave_sum(sm);
+  sp = wave_sum(sp);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) red[wave][0] = sd, red[wave][1] = sc, red[wave][2] = sm, red[wave][3] = sp;
   __syncthreads();
   if (threadIdx.x >= 64) return;
   if (lane < 4) a.part[b * 4 + lane] = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
-  // The last workgroup to arrive sums the partials: agent-scope release before
-  // the ticket, agent-scope acquire after the last one (the per-XCD L2s are not
-  // coherent).  Each lane sums its ICs in ascending order, then the lanes in a
-  // fixed tree: the value does not depend on which workgroup arrives last.
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  unsigned t = 0;
-  if (lane == 0) t = __hip_atomic_fetch_add(a.cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  t = __shfl(t, 0, 64);
-  if (t != gridDim.x - 1) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  // The last workgroup to arrive sums the partials.  Each lane sums its ICs in
+  // ascending order, then the lanes in a fixed tree: the value does not depend
+  // on which workgroup arrives last.
+  if (arrival_ticket(a.cnt, lane) != gridDim.x - 1) return;
+  acquire_partials();
   double q[4] = {0.0, 0.0, 0.0, 0.0};
   for (int i = lane; i < a.B; i += 64) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) q[k] += a.part[(int64_t)i * 4 + k];
   }
 #pragma unroll
-  for (int k = 0; k < 4; ++k) q[k] = wave_sum_f64(q[k]);
+  for (int k = 0; k < 4; ++k) q[k] = wave_sum(q[k]);
   if (lane == 0) {
     const double ld = q[0] * a.inv_n3, lc = q[1] * a.inv_n1, lm = q[2] * a.inv_n1, lp = q[3] * a.inv_n1;
     a.losses[0] = (float)(a.w[0] * ld + a.w[1] * lc + a.w[2] * lm + a.w[3] * lp);

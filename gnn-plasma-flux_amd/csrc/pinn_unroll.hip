@@ -19,30 +19,16 @@
 // output value is written by one thread in a fixed order.
 #include "hf_device.h"
 #include "hf_internal.h"
+#include "unroll_common.h"
 
 namespace hf {
 namespace {
 
 constexpr int kPuThreads = 256;
-// Workspace: [0, 256) the arrival counter (zeroed by the launcher's memset
-// node before every launch), then four float64 partials per IC (data, cont, mom, pois);
-// the _ex call with the conservation terms adds two per IC behind them
-// (lam_e r_e^2, lam_q r_q^2).
-constexpr size_t kPuCounterBytes = 256;
-
-inline size_t al256(size_t b) { return (b + 255) / 256 * 256; }
-
-__device__ __forceinline__ double wave_sum(double a) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) a += __shfl_xor(a, o, 64);
-  return a;
-}
-
-// w (pred - target)^2 of one value, the difference rounded to float32 (pure_unroll.hip's sq_err)
-__device__ __forceinline__ double sq_err(float pred, float tgt, float w) {
-  const double d = (double)__fsub_rn(pred, tgt);
-  return (double)w * (d * d);
-}
+// Workspace: [0, kCounterBytes) the arrival counter, then four float64
+// partials per IC (data, cont, mom, pois); the _ex call with the conservation
+// terms adds two per IC behind them (lam_e r_e^2, lam_q r_q^2).  The data
+// term is pure_unroll.hip's (sq_err).
 
 // The residuals' constants; phys == false: only the data term.
 struct Phys {
@@ -73,12 +59,7 @@ struct LossArgs {
   double *part;         // [B][4]
   unsigned *cnt;
   float *losses;
-  // the _ex call's energy and charge terms (include/hybridflux.h); cons == false: the wider row only
-  bool cons;
-  double lam_e, lam_q, cscale;  // cscale = cons_scale
-  const double *cref;           // [B][2] (eref, qref)
-  float *coef;                  // [B][2] (ce, cq)
-  double *cpart;                // [B][2]
+  StateConsArgs c;      // the _ex call's energy and charge terms, part [B][2]; off: the wider row only
 };
 
 template <bool EX>
@@ -98,7 +79,7 @@ __global__ __launch_bounds__(kPuThreads) void pinn_unroll_loss_kernel(LossArgs a
     }
     __syncthreads();
   }
-  const bool cons = EX && a.cons;
+  const bool cons = EX && a.c.on;
   double sd = 0.0, sc = 0.0, sm = 0.0, sp = 0.0, su2 = 0.0, sE2 = 0.0, sn = 0.0;
   for (int i = threadIdx.x; i < nx; i += kPuThreads) {
     const float pn = P[i], pu = P[nx + i], pE = P[2 * nx + i];
@@ -142,29 +123,21 @@ __global__ __launch_bounds__(kPuThreads) void pinn_unroll_loss_kernel(LossArgs a
       const double tu = ((redc[0][0] + redc[1][0]) + redc[2][0]) + redc[3][0];
       const double tE = ((redc[0][1] + redc[1][1]) + redc[2][1]) + redc[3][1];
       const double tn = ((redc[0][2] + redc[1][2]) + redc[2][2]) + redc[3][2];
-      const double re = 0.5 * (tu + tE) / (double)nx - a.cref[2 * b], rq = tn / (double)nx - a.cref[2 * b + 1];
-      a.coef[2 * b] = (float)(2.0 * a.lam_e * a.cscale * re / (double)nx);
-      a.coef[2 * b + 1] = (float)(2.0 * a.lam_q * a.cscale * rq / (double)nx);
-      a.cpart[2 * b] = a.lam_e * (re * re);
-      a.cpart[2 * b + 1] = a.lam_q * (rq * rq);
+      double pe, pq;
+      cons_terms(a.c, b, tu, tE, tn, nx, pe, pq);
+      a.c.part[2 * b] = pe;
+      a.c.part[2 * b + 1] = pq;
     }
   } else {
     __syncthreads();
     if (threadIdx.x >= 64) return;
   }
   if (lane < 4) a.part[b * 4 + lane] = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
-  // The last workgroup to arrive sums the partials: agent-scope release before
-  // the ticket, agent-scope acquire after the last one (the per-XCD L2s are not
-  // coherent).  Each lane sums its ICs in ascending order, then the lanes in a
-  // fixed tree: the value does not depend on which workgroup arrives last.
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  unsigned t = 0;
-  if (lane == 0) t = __hip_atomic_fetch_add(a.cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  t = __shfl(t, 0, 64);
-  if (t != gridDim.x - 1) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  // The last workgroup to arrive sums the partials.  Each lane sums its ICs in
+  // ascending order, then the lanes in a fixed tree: the value does not depend
+  // on which workgroup arrives last.
+  if (arrival_ticket(a.cnt, lane) != gridDim.x - 1) return;
+  acquire_partials();
   double q[4] = {0.0, 0.0, 0.0, 0.0};
   for (int i = lane; i < a.B; i += 64) {
 #pragma unroll
@@ -174,7 +147,7 @@ __global__ __launch_bounds__(kPuThreads) void pinn_unroll_loss_kernel(LossArgs a
   for (int k = 0; k < 4; ++k) q[k] = wave_sum(q[k]);
   double qe = 0.0, qq = 0.0;
   if (cons) {  // (uniform)
-    for (int i = lane; i < a.B; i += 64) qe += a.cpart[2 * (int64_t)i], qq += a.cpart[2 * (int64_t)i + 1];
+    for (int i = lane; i < a.B; i += 64) qe += a.c.part[2 * (int64_t)i], qq += a.c.part[2 * (int64_t)i + 1];
     qe = wave_sum(qe);
     qq = wave_sum(qq);
   }
@@ -182,7 +155,7 @@ __global__ __launch_bounds__(kPuThreads) void pinn_unroll_loss_kernel(LossArgs a
     const double ld = q[0] * a.scale, lc = q[1] * a.sc, lm = q[2] * a.sm, lp = q[3] * a.sp;
     if constexpr (EX) {
       // (total, data, cont, mom, pois, energy, charge): entries 1..4 are the plain call's, and so is 0 without the terms
-      const double le = qe * a.cscale, lq = qq * a.cscale;
+      const double le = qe * a.c.scale, lq = qq * a.c.scale;
       a.losses[0] = cons ? (float)(((((ld + lc) + lm) + lp) + le) + lq) : (float)(((ld + lc) + lm) + lp);
       a.losses[1] = (float)ld;
       a.losses[2] = (float)lc;
@@ -327,7 +300,7 @@ bool pinn_unroll_nx_ok(int nx) { return nx >= 1 && nx <= kFvLdsMaxNx; }
 
 int64_t pinn_unroll_ws_bytes(int B, int nx) {
   (void)nx;
-  return (int64_t)(kPuCounterBytes + al256(sizeof(double) * 4 * (size_t)B));
+  return (int64_t)(kCounterBytes + al256(sizeof(double) * 4 * (size_t)B));
 }
 
 int64_t pinn_unroll_ws_bytes_ex(int B, int nx) {
@@ -337,10 +310,9 @@ int64_t pinn_unroll_ws_bytes_ex(int B, int nx) {
 namespace {
 
 template <bool EX>
-hipError_t loss_any(const float *pred, const float *state, const float *target, int B, int nx, const float *w,
-                    float scale, const float *phys, float phys_scale, double dt, double dx, double nu, const double *pc,
-                    float *losses, void *ws, const ConsTerms *cons, hipStream_t s) {
-  if (!pinn_unroll_nx_ok(nx) || B < 1) return hipErrorInvalidValue;
+hipError_t loss_launch(const float *pred, const float *state, const float *target, int B, int nx, const float *w,
+                       float scale, const float *phys, float phys_scale, double dt, double dx, double nu,
+                       const double *pc, float *losses, void *ws, const ConsTerms *cons, hipStream_t s) {
   LossArgs a{};
   a.p = pred, a.t = target;
   a.f = phys_of(state, phys, dt, dx, nu, pc);
@@ -353,14 +325,9 @@ hipError_t loss_any(const float *pred, const float *state, const float *target, 
     a.sp = (double)phys_scale * (double)phys[2];
   }
   a.cnt = static_cast<unsigned *>(ws);
-  a.part = reinterpret_cast<double *>(static_cast<char *>(ws) + kPuCounterBytes);
+  a.part = reinterpret_cast<double *>(static_cast<char *>(ws) + kCounterBytes);
   a.losses = losses;
-  if (EX && cons) {
-    a.cons = true;
-    a.lam_e = (double)cons->lam_e, a.lam_q = (double)cons->lam_q, a.cscale = (double)cons->scale;
-    a.cref = cons->ref, a.coef = cons->coef;
-    a.cpart = reinterpret_cast<double *>(static_cast<char *>(ws) + pinn_unroll_ws_bytes(B, nx));
-  }
+  if (cons) cons_setup(a.c, *cons, ws, pinn_unroll_ws_bytes(B, nx));
   // the arrival counter starts every launch at 0 (a memset node, not a kernel)
   if (hipError_t e = hipMemsetAsync(ws, 0, 16, s)) return e;
   hipLaunchKernelGGL(pinn_unroll_loss_kernel<EX>, dim3((unsigned)B), dim3(kPuThreads), lds_bytes(a.f, nx), s, a);
@@ -368,11 +335,10 @@ hipError_t loss_any(const float *pred, const float *state, const float *target, 
 }
 
 template <bool EX>
-hipError_t adjoint_any(const float *pred, const float *state, const float *target, const float *pred_next,
-                       const float *grad_state_next, int B, int nx, const float *w, float scale, const float *phys,
-                       float phys_scale, double dt, double dx, double nu, const double *pc, float *grad_out,
-                       const float *coef, hipStream_t s) {
-  if (!pinn_unroll_nx_ok(nx) || B < 1) return hipErrorInvalidValue;
+hipError_t adjoint_launch(const float *pred, const float *state, const float *target, const float *pred_next,
+                          const float *grad_state_next, int B, int nx, const float *w, float scale, const float *phys,
+                          float phys_scale, double dt, double dx, double nu, const double *pc, float *grad_out,
+                          const float *coef, hipStream_t s) {
   AdjArgs a{};
   a.p = pred, a.t = target;
   a.f = phys_of(state, phys, dt, dx, nu, pc);
@@ -397,32 +363,25 @@ hipError_t adjoint_any(const float *pred, const float *state, const float *targe
 
 }  // namespace
 
-hipError_t launch_pinn_unroll_loss(const float *pred, const float *state, const float *target, int B, int nx,
+// ex picks the instantiation; the plain entry points pass cons / coef NULL
+hipError_t launch_pinn_unroll_loss(bool ex, const float *pred, const float *state, const float *target, int B, int nx,
                                    const float *w, float scale, const float *phys, float phys_scale, double dt,
-                                   double dx, double nu, const double *pc, float *losses, void *ws, hipStream_t s) {
-  return loss_any<false>(pred, state, target, B, nx, w, scale, phys, phys_scale, dt, dx, nu, pc, losses, ws, nullptr, s);
-}
-hipError_t launch_pinn_unroll_loss_ex(const float *pred, const float *state, const float *target, int B, int nx,
-                                      const float *w, float scale, const float *phys, float phys_scale, double dt,
-                                      double dx, double nu, const double *pc, float *losses, void *ws,
-                                      const ConsTerms *cons, hipStream_t s) {
-  return loss_any<true>(pred, state, target, B, nx, w, scale, phys, phys_scale, dt, dx, nu, pc, losses, ws, cons, s);
+                                   double dx, double nu, const double *pc, float *losses, void *ws,
+                                   const ConsTerms *cons, hipStream_t s) {
+  if (!pinn_unroll_nx_ok(nx) || B < 1) return hipErrorInvalidValue;
+  return (ex ? loss_launch<true> : loss_launch<false>)(pred, state, target, B, nx, w, scale, phys, phys_scale, dt, dx,
+                                                        nu, pc, losses, ws, ex ? cons : nullptr, s);
 }
 
-hipError_t launch_pinn_unroll_adjoint(const float *pred, const float *state, const float *target, const float *pred_next,
-                                      const float *grad_state_next, int B, int nx, const float *w, float scale,
-                                      const float *phys, float phys_scale, double dt, double dx, double nu,
-                                      const double *pc, float *grad_out, hipStream_t s) {
-  return adjoint_any<false>(pred, state, target, pred_next, grad_state_next, B, nx, w, scale, phys, phys_scale, dt, dx,
-                            nu, pc, grad_out, nullptr, s);
-}
-hipError_t launch_pinn_unroll_adjoint_ex(const float *pred, const float *state, const float *target,
-                                         const float *pred_next, const float *grad_state_next, int B, int nx,
-                                         const float *w, float scale, const float *phys, float phys_scale, double dt,
-                                         double dx, double nu, const double *pc, float *grad_out, const float *coef,
-                                         hipStream_t s) {
-  return adjoint_any<true>(pred, state, target, pred_next, grad_state_next, B, nx, w, scale, phys, phys_scale, dt, dx,
-                           nu, pc, grad_out, coef, s);
+hipError_t launch_pinn_unroll_adjoint(bool ex, const float *pred, const float *state, const float *target,
+                                      const float *pred_next, const float *grad_state_next, int B, int nx,
+                                      const float *w, float scale, const float *phys, float phys_scale, double dt,
+                                      double dx, double nu, const double *pc, float *grad_out, const float *coef,
+                                      hipStream_t s) {
+  if (!pinn_unroll_nx_ok(nx) || B < 1) return hipErrorInvalidValue;
+  return (ex ? adjoint_launch<true> : adjoint_launch<false>)(pred, state, target, pred_next, grad_state_next, B, nx, w,
+                                                              scale, phys, phys_scale, dt, dx, nu, pc, grad_out, coef,
+                                                              s);
 }
 
 }  // namespace hf

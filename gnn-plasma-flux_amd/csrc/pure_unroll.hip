@@ -14,6 +14,7 @@
 // The loss follows unroll.hip: float64 partials, one per workgroup, summed in
 // workgroup order by the last wave to arrive.
 #include "hf_internal.h"
+#include "unroll_common.h"
 
 namespace hf {
 namespace {
@@ -22,61 +23,29 @@ constexpr int kPuThreads = 256;
 constexpr int kPuTile = 1024;  // cells of one IC per workgroup: 12 KiB of LDS per staged block
 typedef float pu_f4 __attribute__((ext_vector_type(4)));
 
-inline size_t al256(size_t b) { return (b + 255) / 256 * 256; }
 inline int64_t tiles_of(int nx) { return ((int64_t)nx + kPuTile - 1) / kPuTile; }
 
-// Workspace: [0, 256) the arrival counter (zeroed by the launcher's memset
-// node before every launch), then one float64 loss partial per workgroup; the
-// _ex calls with the conservation terms add three float64 sums per workgroup
-// behind them (sum u^2, sum E^2, sum n of the tile).
-constexpr size_t kPuCounterBytes = 256;
-
-struct LossArgs {
-  const float *tgt;  // [B][3][nx] or NULL: no loss term
-  float w0, w1, w2;
-  double scale;
-  double *part;      // [B * tiles]
-  unsigned *cnt;
-  float *loss;
-};
-
-__device__ __forceinline__ double wave_sum(double a) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) a += __shfl_xor(a, o, 64);
-  return a;
-}
-
-// The energy and charge terms of the _ex calls (include/hybridflux.h): on ==
-// false leaves the kernel with the state term alone and the wider loss row.
-struct ConsArgs {
-  bool on;
-  double lam_e, lam_q, scale;  // scale = cons_scale
-  const double *ref;           // [B][2] (eref, qref)
-  float *coef;                 // [B][2] (ce, cq)
-  double *part;                // [B * tiles][3]
+// Workspace: [0, kCounterBytes) the arrival counter, then one float64 loss
+// partial per workgroup; the _ex calls with the conservation terms add three
+// float64 sums per workgroup behind them (sum u^2, sum E^2, sum n of the tile).
+struct LossArgs : StateLossArgs {};  // part [B * tiles]
+struct ConsArgs : StateConsArgs {    // part [B * tiles][3]
   int B, nx, tiles;
 };
 
 // The step's loss from the per-workgroup partials, by the wave that arrives
 // last (unroll.hip's scheme).  Called by a whole wave after its partial store;
-// `total` waves call it per launch.  Agent-scope release before the ticket,
-// agent-scope acquire after the last one (the per-XCD L2s are not coherent);
-// the partials are summed in workgroup order per lane and then across the lanes
-// in a fixed tree, so the value does not depend on which wave arrives last.
+// `total` waves call it per launch (arrival_ticket); the partials are summed in
+// workgroup order per lane and then across the lanes in a fixed tree, so the
+// value does not depend on which wave arrives last.
 // EX with the conservation terms: an IC's sums are complete only here, so this
 // wave also adds each IC's tiles in tile order (a lane takes ICs lane, lane +
 // 64, ...), writes the IC's two coefficients (float64, rounded once) and adds
 // the ICs' terms in the same fixed order.
 template <bool EX>
 __device__ __forceinline__ void loss_arrive(const LossArgs &la, const ConsArgs &ca, unsigned total, int lane) {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  unsigned t = 0;
-  if (lane == 0) t = __hip_atomic_fetch_add(la.cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  t = __shfl(t, 0, 64);
-  if (t != total - 1) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (arrival_ticket(la.cnt, lane) != total - 1) return;
+  acquire_partials();
   const double *part = la.part;
   double a = 0.0;
   for (unsigned i = lane; i < total; i += 64) a += part[i];
@@ -91,11 +60,10 @@ __device__ __forceinline__ void loss_arrive(const LossArgs &la, const ConsArgs &
         const double *t = ca.part + (int64_t)b * ca.tiles * 3;
         double su2 = 0.0, sE2 = 0.0, sn = 0.0;
         for (int j = 0; j < ca.tiles; ++j) su2 += t[3 * j], sE2 += t[3 * j + 1], sn += t[3 * j + 2];
-        const double re = 0.5 * (su2 + sE2) / nx - ca.ref[2 * b], rq = sn / nx - ca.ref[2 * b + 1];
-        ca.coef[2 * b] = (float)(2.0 * ca.lam_e * ca.scale * re / nx);
-        ca.coef[2 * b + 1] = (float)(2.0 * ca.lam_q * ca.scale * rq / nx);
-        e += ca.lam_e * (re * re);
-        q += ca.lam_q * (rq * rq);
+        double pe, pq;
+        cons_terms(ca, b, su2, sE2, sn, nx, pe, pq);
+        e += pe;
+        q += pq;
       }
       e = wave_sum(e);
       q = wave_sum(q);
@@ -109,12 +77,6 @@ __device__ __forceinline__ void loss_arrive(const LossArgs &la, const ConsArgs &
       la.loss[3] = (float)lq;
     }
   }
-}
-
-// w (pred - target)^2 of one value, the difference rounded to float32
-__device__ __forceinline__ double sq_err(float pred, float tgt, float w) {
-  const double d = (double)__fsub_rn(pred, tgt);
-  return (double)w * (d * d);
 }
 
 // ---------------------------------------------------------------------- forward
@@ -237,30 +199,17 @@ __global__ __launch_bounds__(kPuThreads) void pure_unroll_adjoint_kernel(const f
 }
 
 template <bool EX>
-hipError_t update_any(const float *delta, const float *st, const float *x, int B, int nx, float *st_next, float *nf_next,
-                      const float *target, const float *w, float scale, float *loss, void *ws, const ConsTerms *cons,
-                      hipStream_t s) {
-  if (!pure_unroll_shape_ok(B, nx)) return hipErrorInvalidValue;
+hipError_t update_launch(const float *delta, const float *st, const float *x, int B, int nx, float *st_next,
+                         float *nf_next, const float *target, const float *w, float scale, float *loss, void *ws,
+                         const ConsTerms *cons, hipStream_t s) {
   const int tiles = (int)tiles_of(nx);
   const unsigned grid = (unsigned)((int64_t)B * tiles);
   LossArgs la{};
   ConsArgs ca{};
   if (target) {
-    la.tgt = target;
-    la.w0 = w[0], la.w1 = w[1], la.w2 = w[2];
-    la.scale = (double)scale;
-    la.cnt = static_cast<unsigned *>(ws);
-    la.part = reinterpret_cast<double *>(static_cast<char *>(ws) + kPuCounterBytes);
-    la.loss = loss;
-    if (EX && cons) {
-      ca.on = true;
-      ca.lam_e = (double)cons->lam_e, ca.lam_q = (double)cons->lam_q, ca.scale = (double)cons->scale;
-      ca.ref = cons->ref, ca.coef = cons->coef;
-      ca.part = reinterpret_cast<double *>(static_cast<char *>(ws) + pure_unroll_ws_bytes(B, nx));
-      ca.B = B, ca.nx = nx, ca.tiles = tiles;
-    }
-    // the arrival counter starts every launch at 0 (a memset node, not a kernel)
-    if (hipError_t e = hipMemsetAsync(ws, 0, 16, s)) return e;
+    const hipError_t e = state_loss_setup(la, ca, target, w, scale, loss, ws, cons, pure_unroll_ws_bytes(B, nx), s);
+    if (e) return e;
+    if (ca.on) ca.B = B, ca.nx = nx, ca.tiles = tiles;
   }
   hipLaunchKernelGGL(pure_unroll_update_kernel<EX>, dim3(grid), dim3(kPuThreads), 0, s, delta, st, x, nx, tiles, st_next,
                      nf_next, la, ca);
@@ -268,9 +217,8 @@ hipError_t update_any(const float *delta, const float *st, const float *x, int B
 }
 
 template <bool EX>
-hipError_t adjoint_any(const float *st_next, const float *target, const float *w, float scale, const float *gd_next,
-                       const float *gnf_next, int B, int nx, float *gd, const float *coef, hipStream_t s) {
-  if (!pure_unroll_shape_ok(B, nx)) return hipErrorInvalidValue;
+hipError_t adjoint_launch(const float *st_next, const float *target, const float *w, float scale, const float *gd_next,
+                          const float *gnf_next, int B, int nx, float *gd, const float *coef, hipStream_t s) {
   const int tiles = (int)tiles_of(nx);
   const unsigned grid = (unsigned)((int64_t)B * tiles);
   float gs[3];
@@ -283,7 +231,7 @@ hipError_t adjoint_any(const float *st_next, const float *target, const float *w
 }  // namespace
 
 int64_t pure_unroll_ws_bytes(int B, int nx) {
-  return (int64_t)(kPuCounterBytes + al256(sizeof(double) * (size_t)((int64_t)B * tiles_of(nx))));
+  return (int64_t)(kCounterBytes + al256(sizeof(double) * (size_t)((int64_t)B * tiles_of(nx))));
 }
 int64_t pure_unroll_ws_bytes_ex(int B, int nx) {
   return pure_unroll_ws_bytes(B, nx) + (int64_t)al256(3 * sizeof(double) * (size_t)((int64_t)B * tiles_of(nx)));
@@ -292,26 +240,21 @@ int64_t pure_unroll_ws_bytes_ex(int B, int nx) {
 // one workgroup per tile: B * tiles of them must fit a grid
 bool pure_unroll_shape_ok(int B, int nx) { return B >= 1 && nx >= 1 && (int64_t)B * tiles_of(nx) <= 0x7fffffffLL; }
 
-hipError_t launch_pure_unroll_update(const float *delta, const float *st, const float *x, int B, int nx, float *st_next,
-                                     float *nf_next, const float *target, const float *w, float scale, float *loss,
-                                     void *ws, hipStream_t s) {
-  return update_any<false>(delta, st, x, B, nx, st_next, nf_next, target, w, scale, loss, ws, nullptr, s);
-}
-hipError_t launch_pure_unroll_update_ex(const float *delta, const float *st, const float *x, int B, int nx,
-                                        float *st_next, float *nf_next, const float *target, const float *w, float scale,
-                                        float *losses, void *ws, const ConsTerms *cons, hipStream_t s) {
-  return update_any<true>(delta, st, x, B, nx, st_next, nf_next, target, w, scale, losses, ws, cons, s);
+// ex picks the instantiation; the plain entry points pass cons / coef NULL
+hipError_t launch_pure_unroll_update(bool ex, const float *delta, const float *st, const float *x, int B, int nx,
+                                     float *st_next, float *nf_next, const float *target, const float *w, float scale,
+                                     float *loss, void *ws, const ConsTerms *cons, hipStream_t s) {
+  if (!pure_unroll_shape_ok(B, nx)) return hipErrorInvalidValue;
+  return (ex ? update_launch<true> : update_launch<false>)(delta, st, x, B, nx, st_next, nf_next, target, w, scale,
+                                                            loss, ws, ex ? cons : nullptr, s);
 }
 
-hipError_t launch_pure_unroll_adjoint(const float *st_next, const float *target, const float *w, float scale,
+hipError_t launch_pure_unroll_adjoint(bool ex, const float *st_next, const float *target, const float *w, float scale,
                                       const float *gd_next, const float *gnf_next, int B, int nx, float *gd,
-                                      hipStream_t s) {
-  return adjoint_any<false>(st_next, target, w, scale, gd_next, gnf_next, B, nx, gd, nullptr, s);
-}
-hipError_t launch_pure_unroll_adjoint_ex(const float *st_next, const float *target, const float *w, float scale,
-                                         const float *gd_next, const float *gnf_next, int B, int nx, float *gd,
-                                         const float *coef, hipStream_t s) {
-  return adjoint_any<true>(st_next, target, w, scale, gd_next, gnf_next, B, nx, gd, coef, s);
+                                      const float *coef, hipStream_t s) {
+  if (!pure_unroll_shape_ok(B, nx)) return hipErrorInvalidValue;
+  return (ex ? adjoint_launch<true> : adjoint_launch<false>)(st_next, target, w, scale, gd_next, gnf_next, B, nx, gd,
+                                                              coef, s);
 }
 
 }  // namespace hf

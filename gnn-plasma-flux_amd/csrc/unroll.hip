@@ -14,6 +14,7 @@
 // whose rows sum to 0, so P^T e = -P e.
 #include "hf_device.h"
 #include "hf_internal.h"
+#include "unroll_common.h"
 
 namespace hf {
 namespace {
@@ -21,66 +22,27 @@ namespace {
 constexpr int kUnThreads = 256;
 typedef float un_f4 __attribute__((ext_vector_type(4)));
 
-inline size_t al256(size_t b) { return (b + 255) / 256 * 256; }
-
-// Workspace: [0, 256) the arrival counter (zeroed by the launcher's memset
-// node before every launch), then one float64 loss partial per IC; the _ex
-// calls with the conservation terms add two float64 values per IC behind them
-// (lam_e r_e^2, lam_q r_q^2).
-constexpr size_t kUnCounterBytes = 256;
-
-struct LossArgs {
-  const float *tgt;  // [B][3][nx] or NULL: no loss term
-  float w0, w1, w2;
-  double scale;
-  double *part;      // [B]
-  unsigned *cnt;
-  float *loss;
-};
-
-__device__ __forceinline__ double wave_sum(double a) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) a += __shfl_xor(a, o, 64);
-  return a;
-}
-
-// The energy and charge terms of the _ex calls (include/hybridflux.h): on ==
-// false leaves the kernel with the state term alone and the wider loss row.
-struct ConsArgs {
-  bool on;
-  double lam_e, lam_q, scale;  // scale = cons_scale
-  const double *ref;           // [B][2] (eref, qref)
-  float *coef;                 // [B][2] (ce, cq)
-  double *part;                // [B][2] (lam_e r_e^2, lam_q r_q^2)
-};
+// Workspace: [0, kCounterBytes) the arrival counter, then one float64 loss
+// partial per IC; the _ex calls with the conservation terms add two float64
+// values per IC behind them (lam_e r_e^2, lam_q r_q^2).
+struct LossArgs : StateLossArgs {};  // part [B]
+struct ConsArgs : StateConsArgs {};  // part [B][2] (lam_e r_e^2, lam_q r_q^2)
 
 // One IC's complete sums -> its two coefficients and its two term partials, by
-// the one lane that holds them: everything in float64, the coefficients rounded once.
+// the one lane that holds them.
 __device__ __forceinline__ void cons_finish(const ConsArgs &ca, int64_t b, int nx, double su2, double sE2, double sn) {
-  const double e = 0.5 * (su2 + sE2) / (double)nx, q = sn / (double)nx;
-  const double re = e - ca.ref[2 * b], rq = q - ca.ref[2 * b + 1];
-  ca.coef[2 * b] = (float)(2.0 * ca.lam_e * ca.scale * re / (double)nx);
-  ca.coef[2 * b + 1] = (float)(2.0 * ca.lam_q * ca.scale * rq / (double)nx);
-  ca.part[2 * b] = ca.lam_e * (re * re);
-  ca.part[2 * b + 1] = ca.lam_q * (rq * rq);
+  cons_terms(ca, b, su2, sE2, sn, nx, ca.part[2 * b], ca.part[2 * b + 1]);
 }
 
 // The step's loss from the per-IC partials, by the wave that arrives last.
 // Called by a whole wave after its partial stores; `total` waves call it per
-// launch.  Agent-scope release before the ticket, agent-scope acquire after
-// the last one (the per-XCD L2s are not coherent); the partials are summed in
-// IC order per lane and then across the lanes in a fixed tree, so the value
-// does not depend on which wave arrives last.
+// launch (arrival_ticket).  The partials are summed in IC order per lane and
+// then across the lanes in a fixed tree, so the value does not depend on which
+// wave arrives last.
 template <bool EX>
 __device__ __forceinline__ void loss_arrive(const LossArgs &la, const ConsArgs &ca, unsigned total, int B, int lane) {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  unsigned t = 0;
-  if (lane == 0) t = __hip_atomic_fetch_add(la.cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  t = __shfl(t, 0, 64);
-  if (t != total - 1) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (arrival_ticket(la.cnt, lane) != total - 1) return;
+  acquire_partials();
   const double *part = la.part;
   double a = 0.0;
   for (int i = lane; i < B; i += 64) a += part[i];
@@ -103,12 +65,6 @@ __device__ __forceinline__ void loss_arrive(const LossArgs &la, const ConsArgs &
       la.loss[3] = (float)lq;
     }
   }
-}
-
-// w (pred - target)^2 of one value, the difference rounded to float32
-__device__ __forceinline__ double sq_err(float pred, float tgt, float w) {
-  const double d = (double)__fsub_rn(pred, tgt);
-  return (double)w * (d * d);
 }
 
 // ------------------------------------------------------- forward, circulant nx
@@ -422,28 +378,28 @@ hipError_t adjoint_fft_launch(const float *st, const AdjIn &g, const double *pc,
   return hipGetLastError();
 }
 
-hipError_t update_any(bool ex, const float *fe, const float *st, const float *x, const double *pc, int B, int nx, float c, float dt,
-                      float *st_next, float *nf_next, const float *target, const float *w, float scale, float *loss,
-                      void *ws, const ConsTerms *cons, hipStream_t s) {
+}  // namespace
+
+bool unroll_nx_ok(int nx) { return nx >= 1 && nx <= kFvLdsMaxNx; }
+
+int64_t unroll_ws_bytes(int B, int nx) {
+  (void)nx;
+  return (int64_t)(kCounterBytes + al256(sizeof(double) * (size_t)B));
+}
+int64_t unroll_ws_bytes_ex(int B, int nx) { return unroll_ws_bytes(B, nx) + (int64_t)al256(2 * sizeof(double) * (size_t)B); }
+
+hipError_t launch_unroll_update(bool ex, const float *fe, const float *st, const float *x, const double *pc, int B,
+                                int nx, float c, float dt, float *st_next, float *nf_next, const float *target,
+                                const float *w, float scale, float *loss, void *ws, const ConsTerms *cons,
+                                hipStream_t s) {
   if (B <= 0) return hipSuccess;
   if (!unroll_nx_ok(nx)) return hipErrorInvalidValue;
   LossArgs la{};
   ConsArgs ca{};
   if (target) {
-    la.tgt = target;
-    la.w0 = w[0], la.w1 = w[1], la.w2 = w[2];
-    la.scale = (double)scale;
-    la.cnt = static_cast<unsigned *>(ws);
-    la.part = reinterpret_cast<double *>(static_cast<char *>(ws) + kUnCounterBytes);
-    la.loss = loss;
-    if (ex && cons) {
-      ca.on = true;
-      ca.lam_e = (double)cons->lam_e, ca.lam_q = (double)cons->lam_q, ca.scale = (double)cons->scale;
-      ca.ref = cons->ref, ca.coef = cons->coef;
-      ca.part = reinterpret_cast<double *>(static_cast<char *>(ws) + unroll_ws_bytes(B, nx));
-    }
-    // the arrival counter starts every launch at 0 (a memset node, not a kernel)
-    if (hipError_t e = hipMemsetAsync(ws, 0, 16, s)) return e;
+    const hipError_t e =
+        state_loss_setup(la, ca, target, w, scale, loss, ws, ex ? cons : nullptr, unroll_ws_bytes(B, nx), s);
+    if (e) return e;
   }
   switch (poisson_uses_fft(nx) ? nx : 0) {
     case 256: return update_fft_launch<256>(fe, st, x, pc, B, c, dt, st_next, nf_next, la, ca, ex, s);
@@ -461,9 +417,10 @@ hipError_t update_any(bool ex, const float *fe, const float *st, const float *x,
   return hipGetLastError();
 }
 
-hipError_t adjoint_any(bool ex, const float *st, const float *st_next, const float *target, const float *w, float scale,
-                       const float *direct_next, const float *gnf_next, const double *pc, int B, int nx, float c,
-                       float dt, float *g_fe, float *direct, const float *coef, hipStream_t s) {
+hipError_t launch_unroll_adjoint(bool ex, const float *st, const float *st_next, const float *target, const float *w,
+                                 float scale, const float *direct_next, const float *gnf_next, const double *pc, int B,
+                                 int nx, float c, float dt, float *g_fe, float *direct, const float *coef,
+                                 hipStream_t s) {
   if (B <= 0) return hipSuccess;
   if (!unroll_nx_ok(nx)) return hipErrorInvalidValue;
   AdjIn g{};
@@ -487,40 +444,6 @@ hipError_t adjoint_any(bool ex, const float *st, const float *st_next, const flo
     hipLaunchKernelGGL(unroll_adjoint_kernel<false>, dim3((unsigned)B), dim3(kUnThreads), adjoint_lds_bytes(nx), s, st, g,
                        pc, nx, c, dt, g_fe, direct);
   return hipGetLastError();
-}
-
-}  // namespace
-
-bool unroll_nx_ok(int nx) { return nx >= 1 && nx <= kFvLdsMaxNx; }
-
-int64_t unroll_ws_bytes(int B, int nx) {
-  (void)nx;
-  return (int64_t)(kUnCounterBytes + al256(sizeof(double) * (size_t)B));
-}
-int64_t unroll_ws_bytes_ex(int B, int nx) { return unroll_ws_bytes(B, nx) + (int64_t)al256(2 * sizeof(double) * (size_t)B); }
-
-hipError_t launch_unroll_update(const float *fe, const float *st, const float *x, const double *pc, int B, int nx,
-                                float c, float dt, float *st_next, float *nf_next, const float *target, const float *w,
-                                float scale, float *loss, void *ws, hipStream_t s) {
-  return update_any(false, fe, st, x, pc, B, nx, c, dt, st_next, nf_next, target, w, scale, loss, ws, nullptr, s);
-}
-hipError_t launch_unroll_update_ex(const float *fe, const float *st, const float *x, const double *pc, int B, int nx,
-                                   float c, float dt, float *st_next, float *nf_next, const float *target, const float *w,
-                                   float scale, float *losses, void *ws, const ConsTerms *cons, hipStream_t s) {
-  return update_any(true, fe, st, x, pc, B, nx, c, dt, st_next, nf_next, target, w, scale, losses, ws, cons, s);
-}
-
-hipError_t launch_unroll_adjoint(const float *st, const float *st_next, const float *target, const float *w, float scale,
-                                 const float *direct_next, const float *gnf_next, const double *pc, int B, int nx,
-                                 float c, float dt, float *g_fe, float *direct, hipStream_t s) {
-  return adjoint_any(false, st, st_next, target, w, scale, direct_next, gnf_next, pc, B, nx, c, dt, g_fe, direct, nullptr,
-                            s);
-}
-hipError_t launch_unroll_adjoint_ex(const float *st, const float *st_next, const float *target, const float *w,
-                                    float scale, const float *direct_next, const float *gnf_next, const double *pc, int B,
-                                    int nx, float c, float dt, float *g_fe, float *direct, const float *coef,
-                                    hipStream_t s) {
-  return adjoint_any(true, st, st_next, target, w, scale, direct_next, gnf_next, pc, B, nx, c, dt, g_fe, direct, coef, s);
 }
 
 }  // namespace hf

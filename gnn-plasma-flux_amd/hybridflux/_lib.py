@@ -166,25 +166,17 @@ SIGNATURES = {
                                        c_void_p, c_void_p]),
     "hf_state_moments": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "hf_unroll_workspace_bytes_ex": (c_int64, [c_int, c_int]),
-    "hf_unroll_update_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float,
-                                    c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int64,
-                                    c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
-    "hf_unroll_adjoint_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p,
-                                     c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hf_pure_unroll_workspace_bytes_ex": (c_int64, [c_int, c_int]),
-    "hf_pure_unroll_update_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                                         c_void_p, c_float, c_void_p, c_void_p, c_int64, c_void_p, c_float, c_void_p,
-                                         c_void_p, c_void_p]),
-    "hf_pure_unroll_adjoint_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_int,
-                                          c_void_p, c_void_p, c_void_p]),
     "hf_pinn_unroll_workspace_bytes_ex": (c_int64, [c_int, c_int]),
-    "hf_pinn_unroll_loss_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_void_p,
-                                       c_float, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_int64,
-                                       c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
-    "hf_pinn_unroll_adjoint_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
-                                          c_float, c_void_p, c_float, c_double, c_double, c_double, c_void_p, c_void_p,
-                                          c_void_p, c_void_p]),
 }
+# The unrolled-training _ex calls: the plain call's arguments with the conservation ones in front of the stream
+# (cons, cons_scale, dev_cons_ref, dev_cons_coef for an update or loss; dev_cons_coef for an adjoint).
+for _name in ("hf_unroll_update", "hf_pure_unroll_update", "hf_pinn_unroll_loss"):
+    _res, _args = SIGNATURES[_name]
+    SIGNATURES[_name + "_ex"] = (_res, _args[:-1] + [c_void_p, c_float, c_void_p, c_void_p] + _args[-1:])
+for _name in ("hf_unroll_adjoint", "hf_pure_unroll_adjoint", "hf_pinn_unroll_adjoint"):
+    _res, _args = SIGNATURES[_name]
+    SIGNATURES[_name + "_ex"] = (_res, _args[:-1] + [c_void_p] + _args[-1:])
 
 _lib = None
 

@@ -1026,7 +1026,10 @@ def state_moments(states):
 
 def _cons_terms(what, cons, cons_scale, cons_ref, cons_coef, B, dev, target):
     """The conservation arguments of an _ex update: (lam [2] host float32,
-    cons_scale, ref [B,2] float64, coef [B,2] float32 (allocated when None))."""
+    cons_scale, ref [B,2] float64, coef [B,2] float32 (allocated when None));
+    cons None: no terms, (None, cons_scale, None, None)."""
+    if cons is None:
+        return None, float(cons_scale), None, None
     lam = np.ascontiguousarray(np.asarray(cons, dtype=np.float32).reshape(-1))
     if lam.size != 2 or not (lam >= 0).all():
         raise ValueError(f"{what}: cons must be (lam_e, lam_q), both >= 0")
@@ -1046,11 +1049,28 @@ def _cons_coef(what, coef, B, dev):
     return coef
 
 
-def _loss_row(what, loss, n, dev):
+def _loss_row(what, loss, n, dev, text=None):
+    """The loss row of an unrolled-training call, allocated when None.  text:
+    what a plain call says of a wrong one (the _ex calls' message otherwise)."""
     loss = torch.empty(n, device=dev) if loss is None else loss
     if loss.dtype != torch.float32 or loss.numel() != n or loss.device != dev or not loss.is_contiguous():
-        raise ValueError(f"{what}: loss must be {n} contiguous float32 element(s) on the state's device")
+        raise ValueError(f"{what}: "
+                         + (text or f"loss must be {n} contiguous float32 element(s) on the state's device"))
     return loss
+
+
+_ONE_LOSS = "loss must be one float32 element on the state's device"
+
+
+def _adjoint_call(what, plain, ex_call, ex, cons_coef, B, dev):
+    """The entry point of an unrolled-training adjoint and the argument it takes
+    before the stream: the _ex one with cons_coef (checked; may be None) when
+    ex or cons_coef is given, else the plain one with none."""
+    if not ex and cons_coef is None:
+        return plain, ()
+    if cons_coef is not None:
+        _cons_coef(what, cons_coef, B, dev)
+    return ex_call, (ptr(cons_coef),)
 
 
 def _ws_ex(query, B, nx, dev, what):
@@ -1093,6 +1113,7 @@ def unroll_update(grid, flux_edge, state, x=None, target=None, weights=(1.0, 1.0
     dev = state.device
     st = _unroll_state(state, B, nx, dev, "state")
     ex = ex or cons is not None
+    call, nloss = (lib().hf_unroll_update_ex, 4) if ex else (lib().hf_unroll_update, 1)
     fe = flux_edge.detach()
     if fe.dtype != torch.float32 or fe.numel() != B * 2 * nx or fe.device != dev or not fe.is_contiguous() \
             or nx != grid.nx:
@@ -1108,32 +1129,18 @@ def unroll_update(grid, flux_edge, state, x=None, target=None, weights=(1.0, 1.0
     if target is not None:
         target = _unroll_state(target, B, nx, dev, "target")
         w = _weights3(weights)
-        if ex:
-            loss = _loss_row("unroll update", loss, 4, dev)
-        else:
-            loss = torch.empty(1, device=dev) if loss is None else loss
-            if loss.dtype != torch.float32 or loss.numel() != 1 or loss.device != dev:
-                raise ValueError("unroll update: loss must be one float32 element on the state's device")
+        loss = _loss_row("unroll update", loss, nloss, dev, None if ex else _ONE_LOSS)
     else:
         loss = None
-    if cons is not None:
-        lam, cons_scale, cons_ref, cons_coef = _cons_terms("unroll update", cons, cons_scale, cons_ref, cons_coef, B,
-                                                           dev, target)
-        ws = unroll_workspace_ex(B, nx, dev) if ws is None else ws
-    else:
-        lam = cons_ref = cons_coef = None
-    ws = unroll_workspace(B, nx, dev) if ws is None else ws
-    if ex:
-        with torch.cuda.device(dev):
-            check(lib().hf_unroll_update_ex(ptr(fe), ptr(st), ptr(x), ptr(pc), grid.pmode, B, nx, grid.c32, grid.dt32,
-                                            ptr(out), ptr(nf), ptr(target), ptr(w), float(scale), ptr(loss), ptr(ws),
-                                            ws.numel() * ws.element_size(), ptr(lam), float(cons_scale), ptr(cons_ref),
-                                            ptr(cons_coef), stream_of(dev)))
-        return out, nf, loss
+    lam, cons_scale, cons_ref, cons_coef = _cons_terms("unroll update", cons, cons_scale, cons_ref, cons_coef, B, dev,
+                                                       target)
+    if ws is None:
+        ws = unroll_workspace_ex(B, nx, dev) if cons is not None else unroll_workspace(B, nx, dev)
+    extra = (ptr(lam), cons_scale, ptr(cons_ref), ptr(cons_coef)) if ex else ()
     with torch.cuda.device(dev):
-        check(lib().hf_unroll_update(ptr(fe), ptr(st), ptr(x), ptr(pc), grid.pmode, B, nx, grid.c32, grid.dt32, ptr(out),
-                                     ptr(nf), ptr(target), ptr(w), float(scale), ptr(loss), ptr(ws),
-                                     ws.numel() * ws.element_size(), stream_of(dev)))
+        check(call(ptr(fe), ptr(st), ptr(x), ptr(pc), grid.pmode, B, nx, grid.c32, grid.dt32, ptr(out), ptr(nf),
+                   ptr(target), ptr(w), float(scale), ptr(loss), ptr(ws), ws.numel() * ws.element_size(), *extra,
+                   stream_of(dev)))
     return out, nf, loss
 
 
@@ -1163,18 +1170,11 @@ def unroll_adjoint(grid, state, state_next, target, weights, scale, direct_next=
     pc = grid.spectral_plan(dev)
     g_fe = torch.empty(B, 2 * nx, device=dev)
     direct = torch.empty(B, 3, nx, device=dev) if want_direct else None
-    if ex or cons_coef is not None:
-        if cons_coef is not None:
-            _cons_coef("unroll adjoint", cons_coef, B, dev)
-        with torch.cuda.device(dev):
-            check(lib().hf_unroll_adjoint_ex(ptr(st), ptr(sn), ptr(tg), ptr(w), float(scale), ptr(direct_next),
-                                             ptr(gnf_next), ptr(pc), grid.pmode, B, nx, grid.c32, grid.dt32, ptr(g_fe),
-                                             ptr(direct), ptr(cons_coef), stream_of(dev)))
-        return g_fe, direct
+    call, extra = _adjoint_call("unroll adjoint", lib().hf_unroll_adjoint, lib().hf_unroll_adjoint_ex, ex, cons_coef, B,
+                                dev)
     with torch.cuda.device(dev):
-        check(lib().hf_unroll_adjoint(ptr(st), ptr(sn), ptr(tg), ptr(w), float(scale), ptr(direct_next), ptr(gnf_next),
-                                      ptr(pc), grid.pmode, B, nx, grid.c32, grid.dt32, ptr(g_fe), ptr(direct),
-                                      stream_of(dev)))
+        check(call(ptr(st), ptr(sn), ptr(tg), ptr(w), float(scale), ptr(direct_next), ptr(gnf_next), ptr(pc),
+                   grid.pmode, B, nx, grid.c32, grid.dt32, ptr(g_fe), ptr(direct), *extra, stream_of(dev)))
     return g_fe, direct
 
 
@@ -1208,6 +1208,7 @@ def pure_unroll_update(delta, state, x, target=None, weights=(1.0, 1.0, 1.0), sc
     unroll_update's (loss row [4], pure_unroll_workspace_ex, cons_ref, cons_coef)."""
     require_device(state, "state")
     ex = ex or cons is not None
+    call, nloss = (lib().hf_pure_unroll_update_ex, 4) if ex else (lib().hf_pure_unroll_update, 1)
     if state.dim() != 3:
         raise ValueError(f"state must be [B,3,nx], got {tuple(state.shape)}")
     B, _, nx = state.shape
@@ -1223,12 +1224,7 @@ def pure_unroll_update(delta, state, x, target=None, weights=(1.0, 1.0, 1.0), sc
     if target is not None:
         target = _unroll_state(target, B, nx, dev, "target")
         w = _weights3(weights)
-        if ex:
-            loss = _loss_row("pure unroll update", loss, 4, dev)
-        else:
-            loss = torch.empty(1, device=dev) if loss is None else loss
-            if loss.dtype != torch.float32 or loss.numel() != 1 or loss.device != dev:
-                raise ValueError("pure unroll update: loss must be one float32 element on the state's device")
+        loss = _loss_row("pure unroll update", loss, nloss, dev, None if ex else _ONE_LOSS)
         if ws is None:
             ws = pure_unroll_workspace_ex(B, nx, dev) if cons is not None else pure_unroll_workspace(B, nx, dev)
         if ws.device != dev or not ws.is_contiguous():
@@ -1236,20 +1232,12 @@ def pure_unroll_update(delta, state, x, target=None, weights=(1.0, 1.0, 1.0), sc
         nb = ws.numel() * ws.element_size()
     else:
         loss = ws = None
-    if cons is not None:
-        lam, cons_scale, cons_ref, cons_coef = _cons_terms("pure unroll update", cons, cons_scale, cons_ref, cons_coef,
-                                                           B, dev, target)
-    else:
-        lam = cons_ref = cons_coef = None
-    if ex:
-        with torch.cuda.device(dev):
-            check(lib().hf_pure_unroll_update_ex(ptr(d), ptr(st), ptr(x), B, nx, ptr(out), ptr(nf), ptr(target), ptr(w),
-                                                 float(scale), ptr(loss), ptr(ws), nb, ptr(lam), float(cons_scale),
-                                                 ptr(cons_ref), ptr(cons_coef), stream_of(dev)))
-        return out, nf, loss
+    lam, cons_scale, cons_ref, cons_coef = _cons_terms("pure unroll update", cons, cons_scale, cons_ref, cons_coef, B,
+                                                       dev, target)
+    extra = (ptr(lam), cons_scale, ptr(cons_ref), ptr(cons_coef)) if ex else ()
     with torch.cuda.device(dev):
-        check(lib().hf_pure_unroll_update(ptr(d), ptr(st), ptr(x), B, nx, ptr(out), ptr(nf), ptr(target), ptr(w),
-                                          float(scale), ptr(loss), ptr(ws), nb, stream_of(dev)))
+        check(call(ptr(d), ptr(st), ptr(x), B, nx, ptr(out), ptr(nf), ptr(target), ptr(w), float(scale), ptr(loss),
+                   ptr(ws), nb, *extra, stream_of(dev)))
     return out, nf, loss
 
 
@@ -1275,16 +1263,11 @@ def pure_unroll_adjoint(state_next, target, weights, scale, grad_delta_next=None
         gnf_next = _unroll_cells(gnf_next, B, nx, 4, dev, "gnf_next")
     w = _weights3(weights)
     gd = torch.empty(B * nx, 3, device=dev)
-    if ex or cons_coef is not None:
-        if cons_coef is not None:
-            _cons_coef("pure unroll adjoint", cons_coef, B, dev)
-        with torch.cuda.device(dev):
-            check(lib().hf_pure_unroll_adjoint_ex(ptr(sn), ptr(tg), ptr(w), float(scale), ptr(grad_delta_next),
-                                                  ptr(gnf_next), B, nx, ptr(gd), ptr(cons_coef), stream_of(dev)))
-        return gd
+    call, extra = _adjoint_call("pure unroll adjoint", lib().hf_pure_unroll_adjoint, lib().hf_pure_unroll_adjoint_ex,
+                                ex, cons_coef, B, dev)
     with torch.cuda.device(dev):
-        check(lib().hf_pure_unroll_adjoint(ptr(sn), ptr(tg), ptr(w), float(scale), ptr(grad_delta_next),
-                                           ptr(gnf_next), B, nx, ptr(gd), stream_of(dev)))
+        check(call(ptr(sn), ptr(tg), ptr(w), float(scale), ptr(grad_delta_next), ptr(gnf_next), B, nx, ptr(gd), *extra,
+                   stream_of(dev)))
     return gd
 
 
@@ -1336,33 +1319,20 @@ def pinn_unroll_loss(pred, target, weights, scale, state=None, phys=None, phys_s
     [B,2] receives (ce, cq) for pinn_unroll_adjoint."""
     p, tg, st, B, nx, dev, w, lam, phys_scale, dt, dx, nu, pc = _pinn_unroll_args(
         "pinn_unroll_loss", pred, target, weights, state, phys, phys_scale, dx, dt, nu, length)
-    if ex or cons is not None:
-        losses = _loss_row("pinn_unroll_loss", losses, 7, dev)
-        if cons is not None:
-            clam, cons_scale, cons_ref, cons_coef = _cons_terms("pinn_unroll_loss", cons, cons_scale, cons_ref,
-                                                                cons_coef, B, dev, tg)
-            ws = pinn_unroll_workspace_ex(B, nx, dev) if ws is None else ws
-        else:
-            clam = cons_ref = cons_coef = None
-            ws = pinn_unroll_workspace(B, nx, dev) if ws is None else ws
-        if ws.device != dev or not ws.is_contiguous():
-            raise ValueError(f"pinn_unroll_loss: the workspace must be contiguous on {dev}")
-        with torch.cuda.device(dev):
-            check(lib().hf_pinn_unroll_loss_ex(ptr(p), ptr(st), ptr(tg), B, nx, ptr(w), float(scale), ptr(lam),
-                                               phys_scale, dt, dx, nu, ptr(pc), ptr(losses), ptr(ws),
-                                               ws.numel() * ws.element_size(), ptr(clam), float(cons_scale),
-                                               ptr(cons_ref), ptr(cons_coef), stream_of(dev)))
-        return losses
-    losses = torch.empty(5, device=dev) if losses is None else losses
-    if losses.dtype != torch.float32 or losses.numel() != 5 or losses.device != dev or not losses.is_contiguous():
-        raise ValueError("pinn_unroll_loss: losses must be five contiguous float32 elements on pred's device")
-    ws = pinn_unroll_workspace(B, nx, dev) if ws is None else ws
+    ex = ex or cons is not None
+    call, nloss = (lib().hf_pinn_unroll_loss_ex, 7) if ex else (lib().hf_pinn_unroll_loss, 5)
+    losses = _loss_row("pinn_unroll_loss", losses, nloss, dev,
+                       None if ex else "losses must be five contiguous float32 elements on pred's device")
+    clam, cons_scale, cons_ref, cons_coef = _cons_terms("pinn_unroll_loss", cons, cons_scale, cons_ref, cons_coef, B,
+                                                        dev, tg)
+    if ws is None:
+        ws = pinn_unroll_workspace_ex(B, nx, dev) if cons is not None else pinn_unroll_workspace(B, nx, dev)
     if ws.device != dev or not ws.is_contiguous():
         raise ValueError(f"pinn_unroll_loss: the workspace must be contiguous on {dev}")
+    extra = (ptr(clam), cons_scale, ptr(cons_ref), ptr(cons_coef)) if ex else ()
     with torch.cuda.device(dev):
-        check(lib().hf_pinn_unroll_loss(ptr(p), ptr(st), ptr(tg), B, nx, ptr(w), float(scale), ptr(lam), phys_scale, dt,
-                                        dx, nu, ptr(pc), ptr(losses), ptr(ws), ws.numel() * ws.element_size(),
-                                        stream_of(dev)))
+        check(call(ptr(p), ptr(st), ptr(tg), B, nx, ptr(w), float(scale), ptr(lam), phys_scale, dt, dx, nu, ptr(pc),
+                   ptr(losses), ptr(ws), ws.numel() * ws.element_size(), *extra, stream_of(dev)))
     return losses
 
 
@@ -1382,18 +1352,11 @@ def pinn_unroll_adjoint(pred, target, weights, scale, state=None, phys=None, phy
     if grad_state_next is not None:
         grad_state_next = _unroll_state(grad_state_next, B, nx, dev, "grad_state_next")
     g = torch.empty(B, 3, nx, device=dev)
-    if ex or cons_coef is not None:
-        if cons_coef is not None:
-            _cons_coef("pinn_unroll_adjoint", cons_coef, B, dev)
-        with torch.cuda.device(dev):
-            check(lib().hf_pinn_unroll_adjoint_ex(ptr(p), ptr(st), ptr(tg), ptr(pred_next), ptr(grad_state_next), B, nx,
-                                                  ptr(w), float(scale), ptr(lam), phys_scale, dt, dx, nu, ptr(pc),
-                                                  ptr(g), ptr(cons_coef), stream_of(dev)))
-        return g
+    call, extra = _adjoint_call("pinn_unroll_adjoint", lib().hf_pinn_unroll_adjoint, lib().hf_pinn_unroll_adjoint_ex,
+                                ex, cons_coef, B, dev)
     with torch.cuda.device(dev):
-        check(lib().hf_pinn_unroll_adjoint(ptr(p), ptr(st), ptr(tg), ptr(pred_next), ptr(grad_state_next), B, nx, ptr(w),
-                                           float(scale), ptr(lam), phys_scale, dt, dx, nu, ptr(pc), ptr(g),
-                                           stream_of(dev)))
+        check(call(ptr(p), ptr(st), ptr(tg), ptr(pred_next), ptr(grad_state_next), B, nx, ptr(w), float(scale),
+                   ptr(lam), phys_scale, dt, dx, nu, ptr(pc), ptr(g), *extra, stream_of(dev)))
     return g
 
 
