@@ -18,7 +18,6 @@
 namespace hf {
 namespace {
 
-inline size_t a256(size_t v) { return (v + 255) & ~size_t(255); }
 typedef float f4v __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float message(const float *P, int64_t s, int H, int f, float q, float b) {
@@ -97,28 +96,37 @@ PureW pure_view(const float *p, int in_dim, int H, int L) {
 
 namespace {
 
+// PureGNN's workspace.  The region behind delta serves two paths that never
+// run in one call, both from its start: the general-graph forward's CSR
+// buckets, and the two ping-pong states of the sequenced rollout (which runs
+// the forward on chains: no buckets).  Its size counts one after the other.
 struct PureWs {
   float *h0, *h1, *P, *Q, *nf, *delta;
-  void *buckets;
+  EdgeBuckets buckets;  // shares its bytes with st
+  float *st[2];         // [N][3] each
+  size_t bytes;
 };
 
-PureWs carve_pure(void *ws, int H, int64_t N) {
-  char *p = static_cast<char *>(ws);
-  auto take = [&](size_t bytes) {
-    char *r = p;
-    p += a256(bytes);
-    return r;
-  };
+PureWs carve_pure(int H, int64_t N, int64_t E, void *base) {
+  Carve c(base);
   PureWs w{};
-  w.h0 = reinterpret_cast<float *>(take(sizeof(float) * N * H));
-  w.h1 = reinterpret_cast<float *>(take(sizeof(float) * N * H));
-  w.P = reinterpret_cast<float *>(take(sizeof(float) * N * H));
-  w.Q = reinterpret_cast<float *>(take(sizeof(float) * N * H));
-  w.nf = reinterpret_cast<float *>(take(sizeof(float) * N * 4));
-  w.delta = reinterpret_cast<float *>(take(sizeof(float) * N * 3));
-  w.buckets = p;
+  w.h0 = c.take<float>(N * H);
+  w.h1 = c.take<float>(N * H);
+  w.P = c.take<float>(N * H);
+  w.Q = c.take<float>(N * H);
+  w.nf = c.take<float>(N * 4);
+  w.delta = c.take<float>(N * 3);
+  Carve run = c;  // the rollout's view of the shared region, from the same start
+  const size_t shared = c.off;
+  w.buckets = carve_edge_buckets(c, N, E);
+  w.st[0] = run.take<float>(N * 3);
+  w.st[1] = run.take<float>(N * 3);
+  w.bytes = c.off + (run.off - shared);
   return w;
 }
+
+// The one-launch rollouts' workspace is one piece: the packed weight copy.
+OnePiece<float> carve_packed(int64_t floats, void *base) { return carve_one<float>((size_t)floats, base); }
 
 // The chain form of PureGNN's layers (tgemm.h): on chains whose length
 // divides the 128-cell row tile and hidden widths in multiples of 64, a message
@@ -135,7 +143,7 @@ namespace {
 
 // PureGNN.forward (train_pure_gnn.py:57-76) over buckets already built.
 hipError_t pure_forward(const PureW &w, const float *nf, int64_t N, const int64_t *src, const int *off,
-                        const int *perm, int chain_nx, PureWs &b, float *delta, hipStream_t s) {
+                        const int *perm, int chain_nx, const PureWs &b, float *delta, hipStream_t s) {
   const int H = w.H;
   hipError_t e;
   if ((e = gemm_linear(nf, w.in_dim, nullptr, nullptr, 0, nullptr, wv_rows(w.w_in, w.in_dim, w.in_dim), w.b_in, b.h0,
@@ -938,7 +946,7 @@ void pure_score_launch(const PureW &w, const float *state0, float *final_state, 
   }
 }
 
-// ws: the packed copy (pure_packed_floats(H, kMaxChainLayers) floats, hf_pure_gnn_run_workspace_bytes),
+// ws: the packed copy (carve_packed; hf_pure_gnn_run_workspace_bytes sizes it for kMaxChainLayers),
 // made here from the state-dict-order weights; more layers than that run on nn.Linear's rows.
 // sc: the scored form (pure_score_kernel) instead, when given.
 template <int H>
@@ -946,7 +954,7 @@ hipError_t pure_fused_h(const PureW &w0, const float *state0, float *final_state
                         float *traj, void *ws, hipStream_t s, const ScoreArgs *sc = nullptr) {
   PureW w = w0;
   if (ws && w.L <= kMaxChainLayers) {
-    float *packed = static_cast<float *>(ws);
+    float *packed = carve_packed(pure_packed_floats(H, w.L), ws).p;
     const int64_t nl = (int64_t)w.L * 2 * H * H, no = (int64_t)H * H;
     for (int l = 0; l < w.L; ++l)
       hipLaunchKernelGGL(pure_pack_kernel, dim3((unsigned)((2LL * H * H + 255) / 256)), dim3(256), 0, s,
@@ -1007,7 +1015,7 @@ hipError_t pinn_fused(const PinnW &w0, const float *state0, float *final_state, 
   PinnW w = w0;
   PinnPack pk{};
   pk.L = w.L;
-  float *packed = static_cast<float *>(ws);  // >= pinn_packed_floats(D, H, kMaxChainLayers) floats (caller-checked)
+  float *packed = carve_packed(pinn_packed_floats(w.D, w.H, w.L), ws).p;  // (non-NULL: caller-checked)
   for (int l = 0; l < w.L; ++l) {
     pk.w[l] = w.w[l];
     pk.in[l] = l == 0 ? w.D : w.H;
@@ -1026,20 +1034,16 @@ hipError_t pinn_fused(const PinnW &w0, const float *state0, float *final_state, 
 
 }  // namespace
 
-int64_t pure_gnn_ws_bytes(int H, int64_t N, int64_t E) {
-  return (int64_t)(4 * a256(sizeof(float) * N * H) + a256(sizeof(float) * N * 4) + a256(sizeof(float) * N * 3) +
-                   2 * a256(sizeof(float) * N * 3)) +
-         edge_buckets_bytes(N, E);
-}
+int64_t pure_gnn_ws_bytes(int H, int64_t N, int64_t E) { return (int64_t)carve_pure(H, N, E, nullptr).bytes; }
 
 hipError_t launch_pure_gnn_forward(const float *params, int in_dim, int H, int L, const float *nf, int64_t N,
                                    const int64_t *ei, int64_t E, int chain_nx, float *delta, void *ws, hipStream_t s) {
   const PureW w = pure_view(params, in_dim, H, L);
-  PureWs b = carve_pure(ws, H, N);
-  int *off = nullptr, *perm = nullptr;
+  const PureWs b = carve_pure(H, N, E, ws);
   hipError_t e;
-  if (!chain_nx && (e = edge_buckets(ei + E, E, N, 0, true, b.buckets, &off, &perm, s))) return e;  // by dst (:65)
-  return pure_forward(w, nf, N, ei, off, perm, chain_nx, b, delta, s);
+  if (chain_nx) return pure_forward(w, nf, N, ei, nullptr, nullptr, chain_nx, b, delta, s);
+  if ((e = edge_buckets(ei + E, E, N, b.buckets, s, 0, true))) return e;  // by dst (:65)
+  return pure_forward(w, nf, N, ei, b.buckets.off, b.buckets.perm, chain_nx, b, delta, s);
 }
 
 // evaluate_multi_ic.py:45-66 for B ICs at once: traj [B][T+1][3][nx] (optional).
@@ -1056,15 +1060,13 @@ hipError_t launch_pure_gnn_run(const float *params, int H, int L, const float *s
                                     hipMemcpyDeviceToDevice, s)))
     return e;
   if (T == 0) return hipMemcpyAsync(final_state, state0, sizeof(float) * N * 3, hipMemcpyDeviceToDevice, s);
-  PureWs b = carve_pure(ws, H, N);  // (the workspace is non-NULL on this path: hf_pure_gnn_run checks)
-  float *st[2] = {reinterpret_cast<float *>(b.buckets),
-                  reinterpret_cast<float *>(static_cast<char *>(b.buckets) + a256(sizeof(float) * N * 3))};
+  const PureWs b = carve_pure(H, N, 2 * N, ws);  // (the workspace is non-NULL on this path: hf_pure_gnn_run checks)
   const unsigned nb = (unsigned)((N + 255) / 256), sb = (unsigned)((N * 3 + 255) / 256);
   const float *cur = state0;
   for (int t = 0; t < T; ++t) {
     hipLaunchKernelGGL(chain_features_kernel, dim3(nb), dim3(256), 0, s, cur, x, (int64_t)B, nx, b.nf);
     if ((e = pure_forward(w, b.nf, N, nullptr, nullptr, nullptr, nx, b, b.delta, s))) return e;
-    float *nxt = t == T - 1 ? final_state : st[t & 1];
+    float *nxt = t == T - 1 ? final_state : b.st[t & 1];
     hipLaunchKernelGGL(add_delta_kernel, dim3(sb), dim3(256), 0, s, cur, b.delta, (int64_t)B, nx, nxt,
                        traj ? traj + (t + 1) * S : nullptr, ldt);
     cur = nxt;
@@ -1072,14 +1074,28 @@ hipError_t launch_pure_gnn_run(const float *params, int H, int L, const float *s
   return hipGetLastError();
 }
 
-int64_t pinn_ws_bytes(int D, int H, int64_t B) {
-  return (int64_t)(2 * a256(sizeof(float) * B * H) + 2 * a256(sizeof(float) * B * D));
+namespace {
+// PINN's sequenced workspace: the hidden ping-pong of one forward, the state ping-pong of the rollout
+struct PinnWs {
+  float *buf[2];  // [B][H]
+  float *st[2];   // [B][D]
+  size_t bytes;
+};
+PinnWs carve_pinn(int D, int H, int64_t B, void *base) {
+  Carve c(base);
+  PinnWs w{};
+  for (float *&p : w.buf) p = c.take<float>(B * H);
+  for (float *&p : w.st) p = c.take<float>(B * D);
+  w.bytes = c.off;
+  return w;
 }
+}  // namespace
+
 
 int64_t pure_gnn_run_ws_bytes(int H, int B, int nx, int T) {
   if (B == 0 || T == 0) return 0;
   if (pure_fused_ok(H, nx))  // the packed weights, for up to kMaxChainLayers layers
-    return (int64_t)a256(sizeof(float) * pure_packed_floats(H, kMaxChainLayers));
+    return (int64_t)carve_packed(pure_packed_floats(H, kMaxChainLayers), nullptr).bytes;
   return pure_gnn_ws_bytes(H, (int64_t)B * nx, 2LL * B * nx);
 }
 
@@ -1088,22 +1104,21 @@ bool pure_gnn_run_ws_optional(int H, int nx, int T) { return T > 0 && pure_fused
 int64_t pinn_run_ws_bytes(int D, int H, int64_t B) {
   // the one-launch shape: the packed weight copy, sized for the most layers the ABI admits
   if (B == 0) return 0;
-  return pinn_fused_ok(D, H, 2) ? (int64_t)a256(sizeof(float) * pinn_packed_floats(D, H, kMaxChainLayers))
-                                : pinn_ws_bytes(D, H, B);
+  return pinn_fused_ok(D, H, 2) ? (int64_t)carve_packed(pinn_packed_floats(D, H, kMaxChainLayers), nullptr).bytes
+                                : (int64_t)carve_pinn(D, H, B, nullptr).bytes;
 }
 
 hipError_t launch_pinn_forward(const float *params, int D, int H, int L, const float *state, float *out, int64_t B,
                                void *ws, hipStream_t s) {
   const PinnW w = pinn_view(params, D, H, L);
   if (pinn_fused_ok(D, H, L)) return B > 0 ? pinn_fused(w, state, out, B, 1, nullptr, ws, s) : hipSuccess;
-  float *buf[2] = {static_cast<float *>(ws),
-                   reinterpret_cast<float *>(static_cast<char *>(ws) + a256(sizeof(float) * B * H))};
+  const PinnWs pw = carve_pinn(D, H, B, ws);
   const float *in = state;
   hipError_t e;
   for (int l = 0; l < L; ++l) {
     const int K = l == 0 ? D : H;
     const bool last = l == L - 1;
-    float *o = last ? out : buf[l & 1];
+    float *o = last ? out : pw.buf[l & 1];
     if ((e = gemm_linear(in, K, nullptr, nullptr, 0, nullptr, wv_rows(w.w[l], K, K), w.b[l], o, B, last ? D : H,
                          last ? kActNone : kActTanh, last ? state : nullptr, s)))
       return e;
@@ -1122,11 +1137,10 @@ hipError_t launch_pinn_run(const float *params, int D, int H, int L, const float
     return B > 0 ? pinn_fused(pinn_view(params, D, H, L), state0, final_state, B, T, traj, ws, s) : hipSuccess;
   if (traj && (e = hipMemcpy2DAsync(traj, ldt, state0, row, row, B, hipMemcpyDeviceToDevice, s))) return e;
   if (T == 0) return hipMemcpyAsync(final_state, state0, row * B, hipMemcpyDeviceToDevice, s);
-  char *p = static_cast<char *>(ws) + 2 * a256(sizeof(float) * B * H);  // non-NULL here: hf_pinn_run checks
-  float *st[2] = {reinterpret_cast<float *>(p), reinterpret_cast<float *>(p + a256(sizeof(float) * B * D))};
+  const PinnWs pw = carve_pinn(D, H, B, ws);  // non-NULL here: hf_pinn_run checks
   const float *cur = state0;
   for (int t = 0; t < T; ++t) {
-    float *nxt = t == T - 1 ? final_state : st[t & 1];
+    float *nxt = t == T - 1 ? final_state : pw.st[t & 1];
     if ((e = launch_pinn_forward(params, D, H, L, cur, nxt, B, ws, s))) return e;
     if (traj && (e = hipMemcpy2DAsync(reinterpret_cast<char *>(traj) + (t + 1) * row, ldt, nxt, row, row, B,
                                       hipMemcpyDeviceToDevice, s)))
@@ -1139,29 +1153,6 @@ hipError_t launch_pinn_run(const float *params, int D, int H, int L, const float
 // ---- scored rollouts (hf_pure_gnn_run_scored / hf_pinn_run_scored) ----------
 bool pure_score_fused(int H, int nx) { return pure_fused_ok(H, nx); }
 bool pinn_score_fused(int D, int H) { return pinn_fused_ok(D, H, 2); }
-
-int64_t score_traj_bytes(int64_t B, int T, int64_t S) {  // -1: more than 2^60 bytes
-  const unsigned __int128 n = (unsigned __int128)sizeof(float) * (uint64_t)B * (uint64_t)((int64_t)T + 1) * (uint64_t)S;
-  return n > ((unsigned __int128)1 << 60) ? -1 : (int64_t)a256((size_t)n);
-}
-int64_t score_state_bytes(int64_t B, int64_t S) { return (int64_t)a256(sizeof(float) * B * S); }
-
-// fused shapes: the unscored rollout's workspace; otherwise that (rounded up),
-// the model's and the classical trajectory and the classical final state
-int64_t pure_score_ws_bytes(int H, int B, int nx, int T) {
-  const int64_t run = pure_gnn_run_ws_bytes(H, B, nx, T);
-  if (B == 0 || pure_score_fused(H, nx)) return run;
-  const int64_t tb = score_traj_bytes(B, T, 3LL * nx);
-  if (tb < 0 || run < 0 || run > (int64_t(1) << 60)) return -1;
-  return (int64_t)a256(run) + 2 * tb + score_state_bytes(B, 3LL * nx);
-}
-int64_t pinn_score_ws_bytes(int D, int H, int64_t B, int T) {
-  const int64_t run = pinn_run_ws_bytes(D, H, B);
-  if (B == 0 || pinn_score_fused(D, H)) return run;
-  const int64_t tb = score_traj_bytes(B, T, D);
-  if (tb < 0 || run < 0 || run > (int64_t(1) << 60)) return -1;
-  return (int64_t)a256(run) + 2 * tb + score_state_bytes(B, D);
-}
 
 // One launch (pure_score_fused shapes, any T >= 0; ws: the packed weights or NULL).
 hipError_t launch_pure_gnn_score(const float *params, int H, int L, const float *state0, float *final_state,

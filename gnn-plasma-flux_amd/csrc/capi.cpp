@@ -368,9 +368,9 @@ int hf_model_create_ex(const float *host_params, int in_dim, int hidden, int lay
       }
     }
   }
-  const size_t nat_bytes = (sizeof(float) * nat.size() + 255) & ~size_t(255);
-  const size_t stream_bytes = (pk.stream.size() + 255) & ~size_t(255);
-  const size_t small_bytes = (sizeof(float) * pk.small.size() + 255) & ~size_t(255);
+  const size_t nat_bytes = hf::round256(sizeof(float) * nat.size());
+  const size_t stream_bytes = hf::round256(pk.stream.size());
+  const size_t small_bytes = hf::round256(sizeof(float) * pk.small.size());
   const size_t bytes = nat_bytes + stream_bytes + small_bytes;
   hipError_t e = hipMalloc(&m->dev, bytes);
   if (e != hipSuccess) {
@@ -485,14 +485,21 @@ static int train_dims_ok(int in_dim, int hidden, int layers) {
   return in_dim >= 1 && hidden >= 1 && layers >= 0 && layers <= hf::kMaxChainLayers;
 }
 
+// the shape a size query needs of a GraphW (no parameters: no pointer arithmetic on NULL)
+static hf::GraphW graph_dims(int in_dim, int hidden, int layers) {
+  hf::GraphW g{};
+  g.in_dim = in_dim, g.hidden = hidden, g.layers = layers;
+  return g;
+}
+
 int64_t hf_graph_tape_bytes(int in_dim, int hidden, int layers, int64_t N, int64_t E) {
   if (!train_dims_ok(in_dim, hidden, layers) || N < 0 || E < 0) return -1;
-  return hf::graph_tape_bytes(hf::graph_view_state_dict(nullptr, in_dim, hidden, layers), N, E);
+  return hf::graph_tape_bytes(graph_dims(in_dim, hidden, layers), N, E);
 }
 
 int64_t hf_graph_backward_workspace_bytes(int in_dim, int hidden, int layers, int64_t N, int64_t E) {
   if (!train_dims_ok(in_dim, hidden, layers) || N < 0 || E < 0) return -1;
-  return hf::graph_backward_ws_bytes(hf::graph_view_state_dict(nullptr, in_dim, hidden, layers), N, E);
+  return hf::graph_backward_ws_bytes(graph_dims(in_dim, hidden, layers), N, E);
 }
 
 static int train_args(const char *fn, int in_dim, int hidden, int layers, int64_t N, int64_t E) {
@@ -1252,8 +1259,8 @@ int hf_ic_draws_host(int64_t seed, int nx, double *table, double *gauss) {
 
 int64_t hf_run_workspace_bytes(int op, int B, int nx, int T) {
   if (B < 0 || nx < 1 || T < 0 || op < HF_OP_STEP || op > HF_OP_COMPARE) return -1;
-  const int64_t S = 4LL * 3 * nx, F = 4LL * nx, al = 256;
-  auto up = [&](int64_t v) { return (v + al - 1) / al * al; };
+  const int64_t S = 4LL * 3 * nx, F = 4LL * nx;
+  auto up = [](int64_t v) { return (int64_t)hf::round256((size_t)v); };
   switch (op) {
     case HF_OP_STEP: return up(B * F);
     case HF_OP_RUN: return 2 * up(B * S) + up(B * F);
@@ -1263,33 +1270,27 @@ int64_t hf_run_workspace_bytes(int op, int B, int nx, int T) {
 
 namespace {
 
-// Scratch for the generic (non-fused) sequencing: carved from the caller's
-// workspace when given (hf_run_workspace_bytes), else one stream-ordered
-// allocation released on the same stream after the work it backs.
+// Scratch for the generic (non-fused) sequencing: the caller's workspace when
+// given (hf_workspace_need), else one stream-ordered allocation released on the
+// same stream after the work it backs.  `base` is what the call's layout
+// function (carve_* below) cuts; `need` is that function's size on a NULL base.
 struct Scratch {
-  char *base = nullptr;
+  void *base = nullptr;
   bool owned = false;
-  int64_t used = 0, cap = 0;
   hipStream_t s = nullptr;
   int init(void *ws, int64_t ws_bytes, int64_t need, hipStream_t st, const char *fn) {
     s = st;
-    cap = need;
     if (need == 0) return HF_OK;
     if (ws) {
       if (ws_bytes < need)
         return fail(HF_EINVAL, std::string(fn) + ": workspace smaller than hf_workspace_need");
-      base = static_cast<char *>(ws);
+      base = ws;
       return HF_OK;
     }
-    if (hipMallocAsync((void **)&base, need, s) != hipSuccess)
+    if (hipMallocAsync(&base, need, s) != hipSuccess)
       return fail(HF_ENOMEM, std::string(fn) + ": scratch allocation");
     owned = true;
     return HF_OK;
-  }
-  float *take(int64_t bytes) {
-    float *p = reinterpret_cast<float *>(base + used);
-    used += (bytes + 255) / 256 * 256;
-    return p;
   }
   ~Scratch() {
     if (owned) (void)hipFreeAsync(base, s);
@@ -1415,28 +1416,49 @@ bool fv_run_persistent() {
   return on;
 }
 
-int64_t up256(int64_t v) { return (v + 255) / 256 * 256; }
-
-// The scratch each path actually carves (hf_workspace_need): the fused
-// rollouts and the one-launch classical rollouts take none; the generic run
-// takes two state buffers unless the trajectory is the ping-pong, plus the
-// face flux of the hybrid step; the FFT compare one hybrid trajectory and the
-// flux; the generic compare both trajectories, a state and the flux.
-int64_t need_step(const hf_model *m, int B, int nx, bool has_ff) {
-  if (!m || fused_nx(nx) || has_ff) return 0;
-  return up256(4LL * B * nx);
+// The scratch each path actually carves (hf_workspace_need is these on a NULL
+// base): the fused rollouts and the one-launch classical rollouts take none;
+// the hybrid step takes its face flux F unless the caller's buffer holds it;
+// the generic run two state buffers unless the trajectory is the ping-pong,
+// plus F; the FFT compare the hybrid trajectory and F; the generic compare
+// both trajectories, the classical final state and F.
+struct RunWs {
+  float *buf0, *buf1, *F;
+  float *th, *tc, *fin_c;
+  int64_t bytes;
+};
+RunWs carve_step(const hf_model *m, int B, int nx, bool has_ff, void *base) {
+  hf::Carve c(base);
+  RunWs w{};
+  if (m && !fused_nx(nx) && !has_ff) w.F = c.take<float>((int64_t)B * nx);
+  w.bytes = (int64_t)c.off;
+  return w;
 }
-int64_t need_run(const hf_model *m, int B, int nx, int T, bool has_traj) {
-  if (B == 0 || T == 0 || (m && fused_nx(nx))) return 0;
-  if (!m && hf::fv_run_fused(nx) && fv_run_persistent()) return 0;
-  return (has_traj ? 0 : 2 * up256(12LL * B * nx)) + (m ? up256(4LL * B * nx) : 0);
+RunWs carve_run(const hf_model *m, int B, int nx, int T, bool has_traj, void *base) {
+  hf::Carve c(base);
+  RunWs w{};
+  const bool one_launch = m ? fused_nx(nx) : hf::fv_run_fused(nx) && fv_run_persistent();
+  if (B > 0 && T > 0 && !one_launch) {
+    if (!has_traj) w.buf0 = c.take<float>(3LL * B * nx), w.buf1 = c.take<float>(3LL * B * nx);
+    if (m) w.F = c.take<float>((int64_t)B * nx);
+  }
+  w.bytes = (int64_t)c.off;
+  return w;
 }
 bool compare_fft_twin(int nx) { return hf::poisson_uses_fft(nx) && hf::fv_run_fused(nx) && fv_run_persistent(); }
-int64_t need_compare(int B, int nx, int T) {
-  if (B == 0 || fused_nx(nx)) return 0;
-  const int64_t traj = up256(12LL * B * (T + 1) * nx), flux = up256(4LL * B * nx);
-  if (compare_fft_twin(nx)) return traj + flux;
-  return 2 * traj + up256(12LL * B * nx) + flux;
+RunWs carve_compare(int B, int nx, int T, void *base) {
+  hf::Carve c(base);
+  RunWs w{};
+  if (B > 0 && !fused_nx(nx)) {
+    w.th = c.take<float>(3LL * B * (T + 1) * nx);
+    if (!compare_fft_twin(nx)) {
+      w.tc = c.take<float>(3LL * B * (T + 1) * nx);
+      w.fin_c = c.take<float>(3LL * B * nx);
+    }
+    w.F = c.take<float>((int64_t)B * nx);
+  }
+  w.bytes = (int64_t)c.off;
+  return w;
 }
 
 // Lane streams belong to the caller's stream: lane i (1..kMaxLanes-1) of
@@ -1487,9 +1509,9 @@ int64_t hf_workspace_need(hf_model_t m, int op, int B, int nx, int T, int flags)
   if (B < 0 || nx < 1 || T < 0 || op < HF_OP_STEP || op > HF_OP_COMPARE) return -1;
   if (flags & ~(HF_WS_TRAJ | HF_WS_FLUX_FACE)) return -1;
   switch (op) {
-    case HF_OP_STEP: return need_step(m, B, nx, flags & HF_WS_FLUX_FACE);
-    case HF_OP_RUN: return need_run(m, B, nx, T, flags & HF_WS_TRAJ);
-    default: return m ? need_compare(B, nx, T) : -1;
+    case HF_OP_STEP: return carve_step(m, B, nx, flags & HF_WS_FLUX_FACE, nullptr).bytes;
+    case HF_OP_RUN: return carve_run(m, B, nx, T, flags & HF_WS_TRAJ, nullptr).bytes;
+    default: return m ? carve_compare(B, nx, T, nullptr).bytes : -1;
   }
 }
 
@@ -1521,9 +1543,8 @@ int hf_step_ex(hf_model_t m, const float *in, float *out, const float *x, const 
     return HF_OK;
   }
   Scratch sc;
-  if (int rc = sc.init(ws, ws_bytes, need_step(m, B, nx, ff != nullptr), s, "hf_step"))
-    return rc;
-  float *F = ff ? ff : sc.take(sizeof(float) * (int64_t)B * nx);
+  if (int rc = sc.init(ws, ws_bytes, carve_step(m, B, nx, ff != nullptr, nullptr).bytes, s, "hf_step")) return rc;
+  float *F = ff ? ff : carve_step(m, B, nx, false, sc.base).F;
   HF_CHECK_HIP(hf::launch_chain_flux(m->chain, nullptr, in, 3LL * nx, x, B, nx, nullptr, F, s), "hf_step(flux)");
   HF_CHECK_HIP(hf::launch_fv_step(in, 3LL * nx, out, 3LL * nx, F, pc, B, nx, c, dt, nu, dx2, nullptr, nx, metrics,
                                   HF_NUM_METRICS, pm, s),
@@ -1580,12 +1601,10 @@ int hf_run_ex(hf_model_t m, const float *state0, float *state_final, const float
     return HF_OK;
   }
   // scratch: two state buffers unless the trajectory is the ping-pong, the face flux for the hybrid step
-  const int64_t sbytes = (sizeof(float) * B * S + 255) / 256 * 256, fbytes = (sizeof(float) * B * nx + 255) / 256 * 256;
   Scratch sc;
-  if (int rc = sc.init(ws, ws_bytes, need_run(m, B, nx, T, traj != nullptr), s, "hf_run")) return rc;
-  float *buf0 = nullptr, *buf1 = nullptr;
-  if (!traj) buf0 = sc.take(sbytes), buf1 = sc.take(sbytes);
-  float *F = m ? sc.take(fbytes) : nullptr;
+  if (int rc = sc.init(ws, ws_bytes, carve_run(m, B, nx, T, traj != nullptr, nullptr).bytes, s, "hf_run")) return rc;
+  const RunWs rw = carve_run(m, B, nx, T, traj != nullptr, sc.base);
+  float *buf0 = rw.buf0, *buf1 = rw.buf1, *F = rw.F;
   int lanes = run_lanes();
   while (lanes > 1 && (int64_t)B * nx < lanes * kLaneMinCells) --lanes;
   if (!m || B < lanes) lanes = 1;
@@ -1668,13 +1687,25 @@ bool coarse_fused(int nx_f) { return hf::fv_run_fused(nx_f) && fv_run_persistent
 
 // Scratch of the chunked path for chunks of n coarse steps: the running fine
 // state, the chunk's fine trajectory (n S + 1 rows) and its fine flux (n S
-// rows).  -1: more than int64 holds.
-int64_t coarse_chunk_bytes(int B, int nx_f, int64_t n, int S) {
+// rows).  bytes -1 (nothing carved): more than int64 holds.
+struct CoarseWs {
+  float *own, *tfb, *ffb;
+  int64_t bytes;
+};
+CoarseWs carve_coarse_chunk(int B, int nx_f, int64_t n, int S, void *base) {
   const __int128 cells = (__int128)B * nx_f, steps = (__int128)n * S;
   const __int128 total = 12 * cells + 12 * cells * (steps + 1) + 4 * cells * steps + 3 * 256;
-  return total > (__int128)INT64_MAX ? -1 : up256(12LL * B * nx_f) + up256((int64_t)(12 * cells * (steps + 1))) +
-                                                up256((int64_t)(4 * cells * steps));
+  CoarseWs w{};
+  w.bytes = -1;
+  if (total > (__int128)INT64_MAX) return w;
+  hf::Carve c(base);
+  w.own = c.take<float>((size_t)(3 * cells));
+  w.tfb = c.take<float>((size_t)(3 * cells * (steps + 1)));
+  w.ffb = c.take<float>((size_t)(cells * steps));
+  w.bytes = (int64_t)c.off;
+  return w;
 }
+int64_t coarse_chunk_bytes(int B, int nx_f, int64_t n, int S) { return carve_coarse_chunk(B, nx_f, n, S, nullptr).bytes; }
 
 // Without a caller's workspace the chunked path allocates at most this much (but always one coarse step's worth).
 constexpr int64_t kCoarseOwnScratch = 256LL << 20;
@@ -1757,10 +1788,9 @@ int hf_run_coarse(const float *state0, float *state_final, const double *pc, int
   }
   Scratch sc;
   if (int rc = sc.init(ws, ws_bytes, coarse_chunk_bytes(B, nx_f, chunk, S), s, "hf_run_coarse")) return rc;
-  float *own = sc.take(sizeof(float) * B * Sf);
-  float *cur = state_final ? state_final : own;  // the running fine state
-  float *tfb = sc.take(sizeof(float) * B * (chunk * S + 1) * Sf);
-  float *ffb = sc.take(sizeof(float) * B * chunk * S * nx_f);
+  const CoarseWs cw = carve_coarse_chunk(B, nx_f, chunk, S, sc.base);
+  float *cur = state_final ? state_final : cw.own;  // the running fine state
+  float *tfb = cw.tfb, *ffb = cw.ffb;
   if (cur != state0)
     HF_CHECK_HIP(hipMemcpyAsync(cur, state0, sizeof(float) * B * Sf, hipMemcpyDeviceToDevice, s), "hf_run_coarse copy");
   for (int64_t k0 = 0; k0 < T_c; k0 += chunk) {
@@ -1801,18 +1831,17 @@ int hf_run_compare_ex(hf_model_t m, const float *state0, float *state_final, con
                  "hf_run_compare(fused)");
     return HF_OK;
   }
+  Scratch sc;
+  if (int rc = sc.init(ws, ws_bytes, carve_compare(B, nx, T, nullptr).bytes, s, "hf_run_compare")) return rc;
+  const RunWs cw = carve_compare(B, nx, T, sc.base);
+  float *th = cw.th, *tc = cw.tc, *fin_c = cw.fin_c, *F = cw.F;
+  const int64_t fbytes = carve_run(m, B, nx, T, true, nullptr).bytes;  // what the hybrid run takes from F
   if (compare_fft_twin(nx)) {
     // FFT nx <= 1024: the hybrid rollout first, recording its trajectory; then
     // the classical twin as one launch from that trajectory's row 0 (state0,
     // also when state_final aliases it), scoring each step against the hybrid
     // row as it goes: no classical trajectory, no MSE pass.  Same bits as below.
-    Scratch sc;
-    if (int rc = sc.init(ws, ws_bytes, need_compare(B, nx, T), s, "hf_run_compare"))
-      return rc;
     const int64_t S = 3LL * nx, ldT = (T + 1) * S;
-    float *th = sc.take(sizeof(float) * (int64_t)B * ldT);
-    const int64_t fbytes = (sizeof(float) * (int64_t)B * nx + 255) / 256 * 256;
-    float *F = sc.take(fbytes);
     int rc =
         hf_run_ex(m, state0, state_final, x, pc, pm, B, nx, T, c, dt, nu, dx2, th, nullptr, metrics, F, fbytes, stream);
     if (rc != HF_OK) return rc;
@@ -1827,13 +1856,6 @@ int hf_run_compare_ex(hf_model_t m, const float *state0, float *state_final, con
   // generic nx: both trajectories through HBM, then the MSE reduction.  The
   // classical twin runs first: state_final may alias state0, and the hybrid
   // run is the one that writes it.
-  Scratch sc;
-  if (int rc = sc.init(ws, ws_bytes, need_compare(B, nx, T), s, "hf_run_compare"))
-    return rc;
-  const int64_t traj_bytes = sizeof(float) * (int64_t)B * (T + 1) * 3 * nx;
-  float *th = sc.take(traj_bytes), *tc = sc.take(traj_bytes), *fin_c = sc.take(sizeof(float) * (int64_t)B * 3 * nx);
-  const int64_t fbytes = (sizeof(float) * (int64_t)B * nx + 255) / 256 * 256;
-  float *F = sc.take(fbytes);
   // with a trajectory buffer hf_run needs scratch only for the hybrid face flux
   int rc = hf_run_ex(nullptr, state0, fin_c, x, pc, pm, B, nx, T, c, dt, nu, dx2, tc, nullptr, metrics_cl, nullptr, 0,
                      stream);
@@ -2042,6 +2064,34 @@ int score_args(const char *fn, const void *params, const void *state0, const voi
   return HF_OK;
 }
 
+// One [B][T+1][S] float trajectory in bytes; -1: more than 2^60.
+int64_t score_traj_bytes(int64_t B, int T, int64_t S) {
+  const unsigned __int128 n = (unsigned __int128)sizeof(float) * (uint64_t)B * (uint64_t)((int64_t)T + 1) * (uint64_t)S;
+  return n > ((unsigned __int128)1 << 60) ? -1 : (int64_t)n;
+}
+
+// The scored rollouts' workspace off the one-launch shapes (score_sequenced):
+// the model's own rollout workspace, the model's and the classical trajectory
+// [B][T+1][S] and the classical final state [B][S].  bytes -1 (nothing
+// carved): a piece past 2^60 bytes.
+struct ScoreWs {
+  float *tm, *tc, *fin_c;  // behind the model's workspace, which starts the buffer
+  int64_t bytes;
+};
+ScoreWs carve_score(int64_t model_ws_bytes, int64_t B, int T, int64_t S, void *base) {
+  const int64_t tb = score_traj_bytes(B, T, S);
+  ScoreWs w{};
+  w.bytes = -1;
+  if (tb < 0 || model_ws_bytes < 0 || model_ws_bytes > (int64_t(1) << 60)) return w;
+  hf::Carve c(base);
+  c.take<char>((size_t)model_ws_bytes);
+  w.tm = reinterpret_cast<float *>(c.take<char>((size_t)tb));
+  w.tc = reinterpret_cast<float *>(c.take<char>((size_t)tb));
+  w.fin_c = c.take<float>((size_t)(B * S));
+  w.bytes = (int64_t)c.off;
+  return w;
+}
+
 // Shapes without a one-launch kernel: the model's rollout into a trajectory
 // (the caller's, or one in the workspace), the classical hf_run into a second,
 // then hf_traj_metrics and hf_traj_mse — hf_run_compare's generic sequence.
@@ -2053,10 +2103,9 @@ int score_sequenced(const char *fn, const RunModel &run_model, const float *stat
                     float *metrics_cl, void *ws, int64_t model_ws_bytes, void *stream) {
   if ((int64_t)B * (T + 1) > 0x7fffffffLL) return fail(HF_EUNSUPPORTED, std::string(fn) + ": > 2^31 states");
   hipStream_t s = as_stream(stream);
-  const int64_t S = 3LL * nx, tb = hf::score_traj_bytes(B, T, S);
-  char *p = static_cast<char *>(ws) + (model_ws_bytes + 255) / 256 * 256;
-  float *tm = traj ? traj : reinterpret_cast<float *>(p);
-  float *tc = reinterpret_cast<float *>(p + tb), *fin_c = reinterpret_cast<float *>(p + 2 * tb);
+  const int64_t S = 3LL * nx;
+  const ScoreWs sw = carve_score(model_ws_bytes, B, T, S, ws);
+  float *tm = traj ? traj : sw.tm, *tc = sw.tc, *fin_c = sw.fin_c;
   if (mse) {
     int rc = hf_run_ex(nullptr, state0, fin_c, nullptr, pc, pm, B, nx, T, c, dt, nu, dx2, tc, nullptr, metrics_cl,
                        nullptr, 0, stream);
@@ -2075,7 +2124,8 @@ extern "C" {
 
 int64_t hf_pure_gnn_score_workspace_bytes(int hidden, int B, int nx, int T) {
   if (hidden < 1 || B < 0 || nx < 1 || T < 0) return -1;
-  return hf::pure_score_ws_bytes(hidden, B, nx, T);
+  const int64_t run = hf::pure_gnn_run_ws_bytes(hidden, B, nx, T);  // all a one-launch shape needs
+  return B == 0 || hf::pure_score_fused(hidden, nx) ? run : carve_score(run, B, T, 3LL * nx, nullptr).bytes;
 }
 
 int hf_pure_gnn_run_scored(const float *params, int hidden, int layers, const float *state0, float *final_state,
@@ -2084,7 +2134,7 @@ int hf_pure_gnn_run_scored(const float *params, int hidden, int layers, const fl
                            int64_t ws_bytes, void *stream) {
   const char *fn = "hf_pure_gnn_run_scored";
   if (hidden < 1 || layers < 0 || B < 0 || nx < 1 || T < 0) return fail(HF_EINVAL, std::string(fn) + ": bad argument");
-  const int64_t need = hf::pure_score_ws_bytes(hidden, B, nx, T);
+  const int64_t need = hf_pure_gnn_score_workspace_bytes(hidden, B, nx, T);
   if (int rc = score_args(fn, params, state0, final_state, pc, pm, nx, B, metrics, mse, metrics_cl, ws, ws_bytes, need))
     return rc;
   if (B == 0) return HF_OK;
@@ -2108,7 +2158,8 @@ int hf_pure_gnn_run_scored(const float *params, int hidden, int layers, const fl
 
 int64_t hf_pinn_score_workspace_bytes(int dim, int hidden, int64_t B, int T) {
   if (dim < 1 || dim % 3 != 0 || hidden < 1 || B < 0 || T < 0) return -1;
-  return hf::pinn_score_ws_bytes(dim, hidden, B, T);
+  const int64_t run = hf::pinn_run_ws_bytes(dim, hidden, B);  // all a one-launch shape needs
+  return B == 0 || hf::pinn_score_fused(dim, hidden) ? run : carve_score(run, B, T, dim, nullptr).bytes;
 }
 
 int hf_pinn_run_scored(const float *params, int dim, int hidden, int layers, const float *state0, float *final_state,
@@ -2120,7 +2171,7 @@ int hf_pinn_run_scored(const float *params, int dim, int hidden, int layers, con
   if (T < 0) return fail(HF_EINVAL, std::string(fn) + ": T < 0");
   if (dim % 3 != 0) return fail(HF_EINVAL, std::string(fn) + ": dim must be 3 * nx");
   const int nx = dim / 3;
-  const int64_t need = hf::pinn_score_ws_bytes(dim, hidden, B, T);
+  const int64_t need = hf_pinn_score_workspace_bytes(dim, hidden, B, T);
   if (int rc = score_args(fn, params, state0, final_state, pc, pm, nx, B, metrics, mse, metrics_cl, ws, ws_bytes, need))
     return rc;
   if (B == 0) return HF_OK;

@@ -347,18 +347,6 @@ __global__ void agg_backward_kernel(const float *__restrict__ dX, const int64_t 
   delta[t] = h[t] > 0.f ? v : 0.f;
 }
 
-inline size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
-
-struct Carve {
-  char *p;
-  template <class T>
-  T *take(size_t n) {
-    T *r = reinterpret_cast<T *>(p);
-    p += align256(sizeof(T) * n);
-    return r;
-  }
-};
-
 hipError_t linear(const float *A1, int K1, const int64_t *i1, const float *A2, int K2, const int64_t *i2,
                   WView W, const float *b, float *out, int64_t M, int O, int act, hipStream_t s,
                   const float *mask = nullptr, const float *resid = nullptr) {
@@ -429,9 +417,12 @@ __global__ void chain_csr_kernel(int64_t N, int nx, int by_col, int *__restrict_
   perm[2 * j + 1] = (int)(base + nx + (by_col ? i : im));
 }
 
+}  // namespace
+
 // CSR of edges bucketed by key[e] (row or col), segments sorted by edge id.
-hipError_t build_csr(const int64_t *key, int64_t E, int64_t N, int *deg, int *off, int *cur, int *perm,
-                     hipStream_t s, int chain_nx = 0, bool by_col = false) {
+hipError_t edge_buckets(const int64_t *key, int64_t E, int64_t N, const EdgeBuckets &b, hipStream_t s, int chain_nx,
+                        bool by_col) {
+  int *deg = b.deg, *off = b.off, *cur = b.cur, *perm = b.perm;
   hipError_t err;
   if (chain_nx > 0) {
     hipLaunchKernelGGL(chain_csr_kernel, dim3((unsigned)((N + 1 + 255) / 256)), dim3(256), 0, s, N, chain_nx,
@@ -446,6 +437,8 @@ hipError_t build_csr(const int64_t *key, int64_t E, int64_t N, int *deg, int *of
   hipLaunchKernelGGL(sort_segments_kernel, dim3(nb), dim3(256), 0, s, off, N, perm);
   return hipGetLastError();
 }
+
+namespace {
 
 // Forward over a CSR already built; h[l] for l = 0..L are separate buffers
 // when `keep` (training tape), or ping-pong h[0]/h[1] otherwise.
@@ -484,23 +477,58 @@ inline int64_t param_count(const GraphW &w) {
 }
 
 struct Tape {
-  int *deg, *off, *cur, *perm;  // CSR by row (forward aggregation)
+  EdgeBuckets csr;              // by row (forward aggregation)
   float *h[kMaxChainLayers + 1];
   float *agg[kMaxChainLayers];
   float *z;                     // relu(z) of the edge readout [E][H]
+  size_t bytes;
 };
 
 Tape carve_tape(const GraphW &w, int64_t N, int64_t E, void *base) {
-  Carve c{static_cast<char *>(base)};
+  Carve c(base);
   Tape t{};
-  t.deg = c.take<int>(N);
-  t.off = c.take<int>(N + 1);
-  t.cur = c.take<int>(N);
-  t.perm = c.take<int>(E);
+  t.csr = carve_edge_buckets(c, N, E);
   for (int l = 0; l <= w.layers; ++l) t.h[l] = c.take<float>(N * w.hidden);
   for (int l = 0; l < w.layers; ++l) t.agg[l] = c.take<float>(N * w.hidden);
   t.z = c.take<float>(E * w.hidden);
+  t.bytes = c.off;
   return t;
+}
+
+// launch_graph_flux's workspace: the CSR by row, the ping-pong h[0..1], one agg, z
+Tape carve_flux_ws(const GraphW &w, int64_t N, int64_t E, void *base) {
+  Carve c(base);
+  Tape f{};
+  f.csr = carve_edge_buckets(c, N, E);
+  f.h[0] = c.take<float>(N * w.hidden);
+  f.h[1] = c.take<float>(N * w.hidden);
+  f.agg[0] = c.take<float>(N * w.hidden);
+  f.z = c.take<float>(E * w.hidden);
+  f.bytes = c.off;
+  return f;
+}
+
+// launch_graph_backward's workspace on the CSR path
+struct BackwardWs {
+  float *dz;      // [E][H]
+  float *buf[3];  // S_row, S_col, deltas: [N][H] each
+  float *dX;      // [N][2H]
+  float *part;    // split-K partials
+  EdgeBuckets csr;  // by col
+  size_t bytes;
+};
+
+BackwardWs carve_backward_ws(const GraphW &w, int64_t N, int64_t E, void *base) {
+  const int64_t H = w.hidden;
+  Carve c(base);
+  BackwardWs b{};
+  b.dz = c.take<float>(E * H);
+  for (float *&p : b.buf) p = c.take<float>(N * H);
+  b.dX = c.take<float>(N * 2 * H);
+  b.part = c.take<float>(wgrad_part_floats(w, N, E));
+  b.csr = carve_edge_buckets(c, N, E);
+  b.bytes = c.off;
+  return b;
 }
 
 }  // namespace
@@ -520,27 +548,6 @@ hipError_t gemm_wgrad(const float *D, int O, const float *X, int K, int64_t M, f
 int64_t gemm_wgrad_part_floats(int64_t M, int O, int K) {
   const int64_t R = split_rows(M > 0 ? M : 1);
   return ((M + R - 1) / R) * O * (K + 1);
-}
-
-hipError_t edge_buckets(const int64_t *key, int64_t E, int64_t N, int chain_nx, bool by_col, void *ws,
-                        int **off, int **perm, hipStream_t s) {
-  Carve c{static_cast<char *>(ws)};
-  int *deg = c.take<int>(N), *o = c.take<int>(N + 1), *cur = c.take<int>(N), *p = c.take<int>(E);
-  *off = o;
-  *perm = p;
-  return build_csr(key, E, N, deg, o, cur, p, s, chain_nx, by_col);
-}
-
-void edge_buckets_view(void *ws, int64_t N, int64_t E, int **off, int **perm) {
-  Carve c{static_cast<char *>(ws)};
-  c.take<int>(N);
-  *off = c.take<int>(N + 1);
-  c.take<int>(N);
-  *perm = c.take<int>(E);
-}
-
-int64_t edge_buckets_bytes(int64_t N, int64_t E) {
-  return (int64_t)(2 * align256(sizeof(int) * N) + align256(sizeof(int) * (N + 1)) + align256(sizeof(int) * E));
 }
 
 GraphW graph_view_state_dict(const float *p, int in_dim, int hidden, int layers) {
@@ -564,58 +571,36 @@ GraphW graph_view_state_dict(const float *p, int in_dim, int hidden, int layers)
 }
 
 int64_t graph_workspace_bytes(const GraphW &w, int64_t N, int64_t E) {
-  const int64_t H = w.hidden;
-  size_t b = 0;
-  b += align256(sizeof(int) * (size_t)N);              // deg
-  b += align256(sizeof(int) * (size_t)(N + 1));        // off
-  b += align256(sizeof(int) * (size_t)N);              // cursor
-  b += align256(sizeof(int) * (size_t)E);              // perm
-  b += 3 * align256(sizeof(float) * (size_t)(N * H));  // h, h', agg
-  b += align256(sizeof(float) * (size_t)(E * H));      // z
-  return (int64_t)b;
+  return (int64_t)carve_flux_ws(w, N, E, nullptr).bytes;
 }
 
 hipError_t launch_graph_flux(const GraphW &w, const float *nf, int64_t N, const int64_t *ei, int64_t E,
                              float *flux, void *ws, hipStream_t s) {
   if (E <= 0) return hipSuccess;
-  const int H = w.hidden;
-  Carve c{static_cast<char *>(ws)};
-  int *deg = c.take<int>(N), *off = c.take<int>(N + 1), *cur = c.take<int>(N), *perm = c.take<int>(E);
-  float *h[2] = {c.take<float>(N * H), c.take<float>(N * H)};
-  float *agg[1] = {c.take<float>(N * H)};
-  float *z = c.take<float>(E * H);
+  const Tape f = carve_flux_ws(w, N, E, ws);
   hipError_t err;
-  if ((err = build_csr(ei, E, N, deg, off, cur, perm, s))) return err;
-  return forward_core(w, nf, N, ei, E, off, perm, h, agg, false, z, flux, s);
+  if ((err = edge_buckets(ei, E, N, f.csr, s))) return err;
+  return forward_core(w, nf, N, ei, E, f.csr.off, f.csr.perm, f.h, f.agg, false, f.z, flux, s);
 }
 
 // ------------------------------------------------------------------ training
 int64_t graph_tape_bytes(const GraphW &w, int64_t N, int64_t E) {
-  const int64_t H = w.hidden;
-  size_t b = align256(sizeof(int) * N) * 2 + align256(sizeof(int) * (N + 1)) + align256(sizeof(int) * E);
-  b += (size_t)(2 * w.layers + 1) * align256(sizeof(float) * N * H);
-  b += align256(sizeof(float) * E * H);
-  return std::max((int64_t)b, chain_tape_bytes(w, N));  // either path (tagged chains: train_chain.hip)
+  // either path (tagged chains: train_chain.hip)
+  return std::max((int64_t)carve_tape(w, N, E, nullptr).bytes, chain_tape_bytes(w, N));
 }
 
 int64_t graph_backward_ws_bytes(const GraphW &w, int64_t N, int64_t E) {
-  const int64_t H = w.hidden;
-  size_t b = align256(sizeof(float) * E * H);                    // dz
-  b += 3 * align256(sizeof(float) * N * H);                      // S_row, S_col, deltas
-  b += align256(sizeof(float) * N * 2 * H);                      // dX
-  b += align256(sizeof(float) * wgrad_part_floats(w, N, E));     // split-K partials
-  b += align256(sizeof(int) * N) * 2 + align256(sizeof(int) * (N + 1)) + align256(sizeof(int) * E);  // CSR by col
-  return std::max((int64_t)b, chain_backward_ws_bytes(w, N));
+  return std::max((int64_t)carve_backward_ws(w, N, E, nullptr).bytes, chain_backward_ws_bytes(w, N));
 }
 
 hipError_t launch_graph_forward_train(const GraphW &w, const float *nf, int64_t N, const int64_t *ei, int64_t E,
                                       int chain_nx, float *flux, void *tape, hipStream_t s) {
   if (E <= 0) return hipSuccess;  // no flux to compute; the backward returns zeros
   if (chain_train_ok(w, chain_nx, N)) return launch_chain_forward_train(w, nf, N, chain_nx, flux, tape, s);
-  Tape t = carve_tape(w, N, E, tape);
+  const Tape t = carve_tape(w, N, E, tape);
   hipError_t err;
-  if ((err = build_csr(ei, E, N, t.deg, t.off, t.cur, t.perm, s, chain_nx, false))) return err;
-  return forward_core(w, nf, N, ei, E, t.off, t.perm, t.h, t.agg, true, t.z, flux, s);
+  if ((err = edge_buckets(ei, E, N, t.csr, s, chain_nx, false))) return err;
+  return forward_core(w, nf, N, ei, E, t.csr.off, t.csr.perm, t.h, t.agg, true, t.z, flux, s);
 }
 
 // Reverse of forward_core (autograd of src/flux_gnn.py:40-67).  grad_params
@@ -639,21 +624,19 @@ hipError_t launch_graph_backward(const GraphW &w, const float *nf, int64_t N, co
   }
   if (chain_train_ok(w, chain_nx, N))
     return launch_chain_backward(w, nf, N, chain_nx, tape, grad_flux, grad_params, grad_nf, ws, s);
-  Carve c{static_cast<char *>(ws)};
-  float *dz = c.take<float>(E * H);
-  float *buf[3] = {c.take<float>(N * H), c.take<float>(N * H), c.take<float>(N * H)};
-  float *dX = c.take<float>(N * 2 * H);
-  float *part = c.take<float>(wgrad_part_floats(w, N, E));
-  int *deg_c = c.take<int>(N), *off_c = c.take<int>(N + 1), *cur_c = c.take<int>(N), *perm_c = c.take<int>(E);
+  const BackwardWs b = carve_backward_ws(w, N, E, ws);
+  float *dz = b.dz, *dX = b.dX, *part = b.part;
+  float *const *buf = b.buf;
+  const int *off_c = b.csr.off, *perm_c = b.csr.perm;
   const unsigned nb = (unsigned)((N * H + 255) / 256);
 
-  if ((err = build_csr(col, E, N, deg_c, off_c, cur_c, perm_c, s, chain_nx, true))) return err;
+  if ((err = edge_buckets(col, E, N, b.csr, s, chain_nx, true))) return err;
   // readout: flux = w2 . relu(z) + b2, z = W_e [h[row] ; h[col]] + b_e        (:62-66)
   if ((err = wgrad(grad_flux, 1, t.z, H, nullptr, nullptr, 0, nullptr, E, gw_2, gb_2, part, s))) return err;
   hipLaunchKernelGGL(readout_delta_kernel, dim3((unsigned)((E * H + 255) / 256)), dim3(256), 0, s, grad_flux, t.z,
                      w.w_2, E, H, dz);
   if ((err = wgrad(dz, H, t.h[L], H, row, t.h[L], H, col, E, gw_e, gb_e, part, s))) return err;
-  hipLaunchKernelGGL(edge_scatter_kernel, dim3(nb), dim3(256), 0, s, dz, t.off, t.perm, off_c, perm_c, N, H, buf[0],
+  hipLaunchKernelGGL(edge_scatter_kernel, dim3(nb), dim3(256), 0, s, dz, t.csr.off, t.csr.perm, off_c, perm_c, N, H, buf[0],
                      buf[1]);
   // dh_L = W_a^T S_row + W_b^T S_col, masked by relu'(h_L): the delta of layer L-1 (or of the input MLP)
   const WView wet{w.w_e, w.w_e + H, 1, 2 * H};
@@ -669,7 +652,7 @@ hipError_t launch_graph_backward(const GraphW &w, const float *nf, int64_t N, co
                       2 * H, kActNone, s)))
       return err;
     const int nxt = cur == 0 ? 1 : 0;
-    hipLaunchKernelGGL(agg_backward_kernel, dim3(nb), dim3(256), 0, s, dX, row, t.off, off_c, perm_c, t.h[l], N, H,
+    hipLaunchKernelGGL(agg_backward_kernel, dim3(nb), dim3(256), 0, s, dX, row, t.csr.off, off_c, perm_c, t.h[l], N, H,
                        buf[nxt]);
     cur = nxt;
   }

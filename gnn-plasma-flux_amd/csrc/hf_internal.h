@@ -8,6 +8,54 @@
 
 namespace hf {
 
+// Device scratch (workspaces, tapes): every piece starts 256-byte aligned, and
+// the one piece of code that cuts a buffer also gives its size.  A layout is a
+// function carve_<thing>(shape..., void *base) that takes its pieces from a
+// Carve in order and returns their pointers and `bytes`; on a NULL base the
+// pointers are NULL and `bytes` is the size query's answer.
+inline size_t round256(size_t v) { return (v + 255) & ~size_t(255); }
+
+struct Carve {
+  char *base;  // NULL: a size query
+  size_t off = 0;
+  explicit Carve(void *b) : base(static_cast<char *>(b)) {}
+  template <class T>
+  T *take(size_t n) {
+    T *r = base ? reinterpret_cast<T *>(base + off) : nullptr;
+    off += round256(sizeof(T) * n);
+    return r;
+  }
+};
+
+// a buffer of one piece, n elements of T
+template <class T>
+struct OnePiece {
+  T *p;
+  size_t bytes;
+};
+template <class T>
+inline OnePiece<T> carve_one(size_t n, void *base) {
+  Carve c(base);
+  T *p = c.take<T>(n);
+  return {p, c.off};
+}
+
+inline unsigned blocks_of(int64_t n) { return (unsigned)((n + 255) / 256); }
+
+// Edges bucketed by key (row or col): the CSR's degree, offset, cursor and
+// permutation arrays, a sub-layout of every buffer that holds one.
+struct EdgeBuckets {
+  int *deg, *off, *cur, *perm;
+};
+inline EdgeBuckets carve_edge_buckets(Carve &c, int64_t N, int64_t E) {
+  EdgeBuckets b{};
+  b.deg = c.take<int>(N);
+  b.off = c.take<int>(N + 1);
+  b.cur = c.take<int>(N);
+  b.perm = c.take<int>(E);
+  return b;
+}
+
 // Width of the fused chain kernels: MODEL_CONFIG (src/config.py:19-23) is
 // input_dim 4, hidden 128, 4 layers.  16x16x4 f32 MFMA tiles => 8 feature
 // tiles of 16 and 32 k-steps of 4 per 128-wide half of a [h ; agg] input.
@@ -102,12 +150,9 @@ hipError_t gemm_linear(const float *A1, int K1, const int64_t *i1, const float *
 hipError_t gemm_wgrad(const float *D, int O, const float *X, int K, int64_t M, float *gw, int64_t ldw, float *gb,
                       float *part, hipStream_t s);
 int64_t gemm_wgrad_part_floats(int64_t M, int O, int K);
-// Edges bucketed by key (row or col), ascending edge id per bucket; chain_nx > 0: arithmetic buckets.
-int64_t edge_buckets_bytes(int64_t N, int64_t E);
-hipError_t edge_buckets(const int64_t *key, int64_t E, int64_t N, int chain_nx, bool by_col, void *ws, int **off,
-                        int **perm, hipStream_t s);
-// off / perm of buckets that edge_buckets built in ws earlier
-void edge_buckets_view(void *ws, int64_t N, int64_t E, int **off, int **perm);
+// Fills b (carve_edge_buckets) by key, ascending edge id per bucket (b.off, b.perm); chain_nx > 0: arithmetic buckets.
+hipError_t edge_buckets(const int64_t *key, int64_t E, int64_t N, const EdgeBuckets &b, hipStream_t s, int chain_nx = 0,
+                        bool by_col = false);
 
 // PureGNN / PINN inference (baselines.hip).
 // View of PureGNN's flat float32 parameters in state-dict order.
@@ -128,7 +173,6 @@ hipError_t launch_pure_gnn_forward(const float *params, int in_dim, int H, int L
                                    const int64_t *ei, int64_t E, int chain_nx, float *delta, void *ws, hipStream_t s);
 hipError_t launch_pure_gnn_run(const float *params, int H, int L, const float *state0, float *final_state,
                                const float *x, int B, int nx, int T, float *traj, void *ws, hipStream_t s);
-int64_t pinn_ws_bytes(int D, int H, int64_t B);
 // scratch the rollouts actually use: the packed weights on their one-launch paths (baselines.hip)
 int64_t pure_gnn_run_ws_bytes(int H, int B, int nx, int T);
 // the one-launch PureGNN rollout also runs with no workspace (on nn.Linear's rows, unpacked)
@@ -148,10 +192,6 @@ hipError_t launch_pinn_run(const float *params, int D, int H, int L, const float
 // kernels on the others.  tri: the twin's Poisson mode is HF_POISSON_TRIDIAG.
 bool pure_score_fused(int H, int nx);
 bool pinn_score_fused(int D, int H);
-int64_t score_traj_bytes(int64_t B, int T, int64_t S);  // one [B][T+1][S] float trajectory, 256-aligned
-int64_t score_state_bytes(int64_t B, int64_t S);
-int64_t pure_score_ws_bytes(int H, int B, int nx, int T);
-int64_t pinn_score_ws_bytes(int D, int H, int64_t B, int T);
 hipError_t launch_pure_gnn_score(const float *params, int H, int L, const float *state0, float *final_state,
                                  const float *x, const double *pc, int tri, int B, int nx, int T, float c, float dt,
                                  float nu, float dx2, float *traj, float *metrics, float *mse, float *metrics_cl,

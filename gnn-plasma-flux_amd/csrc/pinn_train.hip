@@ -39,20 +39,6 @@ namespace {
 
 using namespace tg;
 
-inline size_t a256(size_t v) { return (v + 255) & ~size_t(255); }
-
-// base == NULL: a size query (off ends at the bytes needed)
-struct Carve {
-  char *base;
-  size_t off = 0;
-  template <class T>
-  T *take(size_t n) {
-    T *r = base ? reinterpret_cast<T *>(base + off) : nullptr;
-    off += a256(sizeof(T) * n);
-    return r;
-  }
-};
-
 struct PinnV {
   const float *w[kMaxChainLayers], *b[kMaxChainLayers];
   int in[kMaxChainLayers], out[kMaxChainLayers];
@@ -83,7 +69,7 @@ struct PinnTape {
   size_t bytes;
 };
 PinnTape carve_pinn_tape(int H, int L, int64_t B, void *base) {
-  Carve c{static_cast<char *>(base)};
+  Carve c(base);
   PinnTape t{};
   for (int l = 0; l + 1 < L; ++l) t.a[l] = c.take<float>(B * H);
   t.bytes = c.off;
@@ -97,7 +83,7 @@ struct PinnBws {
   size_t bytes;
 };
 PinnBws carve_pinn_bws(int D, int H, int L, int64_t B, void *base) {
-  Carve c{static_cast<char *>(base)};
+  Carve c(base);
   PinnBws w{};
   for (int l = 0; l + 1 < L; ++l) w.g[l] = c.take<float>(B * H);
   if (pinn_gemm_path(D, H, B)) {
@@ -173,15 +159,13 @@ __global__ __launch_bounds__(256) void pinn_part_reduce_kernel(PinnRed r, int S)
   else r.gb[l][t - n] = v;
 }
 
-inline unsigned blocks_of(int64_t n) { return (unsigned)((n + 255) / 256); }
-
 inline VPlain mat(const float *p, int64_t rows, int cols) { return VPlain{p, cols, rows, kNoSplit, 0, cols}; }
 
 // ------------------------------------------------------------------- the loss
 constexpr int kLossThreads = 256;
-// Workspace: [0, 256) the arrival counter (zeroed by the launcher's memset
-// node before every launch), then four float64 partials per IC (data, cont, mom, pois).
-constexpr size_t kLossCounterBytes = 256;
+// Workspace (unroll_common.h LossWs): the arrival counter, then four float64
+// partials per IC (data, cont, mom, pois).
+LossWs carve_pinn_loss_ws(int B, void *base) { return carve_loss_ws(4 * (size_t)B, 0, base); }
 
 struct PinnLossArgs {
   const float *p, *s, *sn;  // pred, state_t, state_next [B][3][nx]
@@ -373,10 +357,7 @@ hipError_t launch_pinn_backward(const float *params, int D, int H, int L, const 
 
 bool pinn_loss_nx_ok(int nx) { return nx >= 1 && nx <= kFvLdsMaxNx; }
 
-int64_t pinn_loss_ws_bytes(int B, int nx) {
-  (void)nx;
-  return (int64_t)(kLossCounterBytes + a256(sizeof(double) * 4 * (size_t)B));
-}
+int64_t pinn_loss_ws_bytes(int B, int) { return (int64_t)carve_pinn_loss_ws(B, nullptr).bytes; }
 
 hipError_t launch_pinn_loss(const float *pred, const float *st, const float *sn, int B, int nx, double dt, double dx,
                             double nu, const float *w, const double *pc, float *losses, float *grad_pred, void *ws,
@@ -396,12 +377,13 @@ hipError_t launch_pinn_loss(const float *pred, const float *st, const float *sn,
   a.gp = 2.0 * a.w[3] / n1;
   a.inv_n3 = 1.0 / n3;
   a.inv_n1 = 1.0 / n1;
-  a.cnt = static_cast<unsigned *>(ws);
-  a.part = reinterpret_cast<double *>(static_cast<char *>(ws) + kLossCounterBytes);
+  const LossWs lw = carve_pinn_loss_ws(B, ws);
+  a.cnt = lw.cnt;
+  a.part = lw.part;
   a.losses = losses;
   a.g = grad_pred;
   // the arrival counter starts every launch at 0 (a memset node, not a kernel)
-  if (hipError_t e = hipMemsetAsync(ws, 0, 16, s)) return e;
+  if (hipError_t e = hipMemsetAsync(lw.cnt, 0, 16, s)) return e;
   hipLaunchKernelGGL(pinn_loss_kernel, dim3((unsigned)B), dim3(kLossThreads), pinn_loss_lds_bytes(nx), s, a);
   return hipGetLastError();
 }

@@ -298,14 +298,12 @@ inline size_t lds_bytes(const Phys &f, int nx) { return f.on ? (size_t)nx * 16 :
 
 bool pinn_unroll_nx_ok(int nx) { return nx >= 1 && nx <= kFvLdsMaxNx; }
 
-int64_t pinn_unroll_ws_bytes(int B, int nx) {
-  (void)nx;
-  return (int64_t)(kCounterBytes + al256(sizeof(double) * 4 * (size_t)B));
+// four loss partials per IC (data, cont, mom, pois); cons: two more (energy, charge)
+static LossWs carve_pinn_unroll_ws(int B, bool cons, void *base) {
+  return carve_loss_ws(4 * (size_t)B, cons ? 2 * (size_t)B : 0, base);
 }
-
-int64_t pinn_unroll_ws_bytes_ex(int B, int nx) {
-  return pinn_unroll_ws_bytes(B, nx) + (int64_t)al256(2 * sizeof(double) * (size_t)B);
-}
+int64_t pinn_unroll_ws_bytes(int B, int) { return (int64_t)carve_pinn_unroll_ws(B, false, nullptr).bytes; }
+int64_t pinn_unroll_ws_bytes_ex(int B, int) { return (int64_t)carve_pinn_unroll_ws(B, true, nullptr).bytes; }
 
 namespace {
 
@@ -324,12 +322,13 @@ hipError_t loss_launch(const float *pred, const float *state, const float *targe
     a.sm = (double)phys_scale * (double)phys[1];
     a.sp = (double)phys_scale * (double)phys[2];
   }
-  a.cnt = static_cast<unsigned *>(ws);
-  a.part = reinterpret_cast<double *>(static_cast<char *>(ws) + kCounterBytes);
+  const LossWs lw = carve_pinn_unroll_ws(B, cons != nullptr, ws);
+  a.cnt = lw.cnt;
+  a.part = lw.part;
   a.losses = losses;
-  if (cons) cons_setup(a.c, *cons, ws, pinn_unroll_ws_bytes(B, nx));
+  if (cons) cons_setup(a.c, *cons, lw.cons_part);
   // the arrival counter starts every launch at 0 (a memset node, not a kernel)
-  if (hipError_t e = hipMemsetAsync(ws, 0, 16, s)) return e;
+  if (hipError_t e = hipMemsetAsync(lw.cnt, 0, 16, s)) return e;
   hipLaunchKernelGGL(pinn_unroll_loss_kernel<EX>, dim3((unsigned)B), dim3(kPuThreads), lds_bytes(a.f, nx), s, a);
   return hipGetLastError();
 }

@@ -8,7 +8,7 @@
 // the backward recomputes no tanh.
 //
 // Tape (PureTape; every piece 256-byte aligned, in this order):
-//   buckets   edge_buckets_bytes(N, E): the CSR of the edges by dst (general
+//   buckets   carve_edge_buckets(N, E): the CSR of the edges by dst (general
 //             graphs only; chains find their neighbours arithmetically)
 //   h[0..L]   [N][H] each: h_0 = tanh(W_in nf + b_in), h_{l+1} = h_l + sum of messages
 //   z         [N][H]: tanh(W_o1 h_L + b_o1)
@@ -47,22 +47,8 @@ namespace {
 
 using namespace tg;
 
-inline size_t a256(size_t v) { return (v + 255) & ~size_t(255); }
-
-// base == NULL: a size query (off ends at the bytes needed)
-struct Carve {
-  char *base;
-  size_t off = 0;
-  template <class T>
-  T *take(size_t n) {
-    T *r = base ? reinterpret_cast<T *>(base + off) : nullptr;
-    off += a256(sizeof(T) * n);
-    return r;
-  }
-};
-
 struct PureTape {
-  void *buckets;
+  EdgeBuckets buckets;
   float *h[kMaxChainLayers + 1];
   float *z;
   float *m[kMaxChainLayers];
@@ -71,9 +57,9 @@ struct PureTape {
 };
 
 PureTape carve_pure_tape(int H, int L, int64_t N, int64_t E, void *base) {
-  Carve c{static_cast<char *>(base)};
+  Carve c(base);
   PureTape t{};
-  t.buckets = c.take<char>((size_t)edge_buckets_bytes(N, E));
+  t.buckets = carve_edge_buckets(c, N, E);
   for (int l = 0; l <= L; ++l) t.h[l] = c.take<float>(N * H);
   t.z = c.take<float>(N * H);
   for (int l = 0; l < L; ++l) t.m[l] = c.take<float>(E * H);
@@ -295,7 +281,7 @@ bool pure_train_chain(int H, int chain_nx, int64_t N) {
 }
 
 struct PureBws {
-  void *buckets;                 // CSR by src
+  EdgeBuckets buckets;           // CSR by src
   float *a, *g[2];               // [N][H]
   float *gpq[kMaxChainLayers];   // [N][2H] per layer ([gP | gQ]; generic path: gP then gQ, [N][H] each, in gpq[0])
   float *gpart;                  // generic split-K partials
@@ -305,9 +291,9 @@ struct PureBws {
 };
 
 PureBws carve_pure_bws(int in_dim, int H, int L, int64_t N, int64_t E, void *base) {
-  Carve c{static_cast<char *>(base)};
+  Carve c(base);
   PureBws w{};
-  w.buckets = c.take<char>((size_t)edge_buckets_bytes(N, E));
+  w.buckets = carve_edge_buckets(c, N, E);
   w.a = c.take<float>(N * H);
   w.g[0] = c.take<float>(N * H);
   w.g[1] = c.take<float>(N * H);
@@ -367,7 +353,8 @@ __global__ __launch_bounds__(256) void state_mse_final_kernel(const float *__res
   if (threadIdx.x == 0) loss[0] = __fmul_rn(r, inv_n);
 }
 
-inline unsigned blocks_of(int64_t n) { return (unsigned)((n + 255) / 256); }
+// state_mse_kernel's blocks over n elements; its workspace: one partial each
+inline int mse_blocks(int64_t n) { return (int)std::min<int64_t>(kMseBlocks, (n + 255) / 256); }
 
 }  // namespace
 
@@ -403,8 +390,11 @@ hipError_t launch_pure_forward_train(const float *params, int in_dim, int H, int
     return gemm_linear(t.z, H, nullptr, nullptr, 0, nullptr, wv_rows(w.w_o2, H, H), w.b_o2, delta, N, 3, kActNone,
                        nullptr, s);
   }
-  int *off = nullptr, *perm = nullptr;
-  if (!chain_nx && L > 0 && (e = edge_buckets(ei + E, E, N, 0, true, t.buckets, &off, &perm, s))) return e;  // by dst
+  const int *off = nullptr, *perm = nullptr;
+  if (!chain_nx && L > 0) {  // by dst
+    if ((e = edge_buckets(ei + E, E, N, t.buckets, s, 0, true))) return e;
+    off = t.buckets.off, perm = t.buckets.perm;
+  }
   float *P = t.z, *Q = t.q;  // (z itself is written after the last layer)
   for (int l = 0; l < L; ++l) {
     const float *W = w.w_l + l * w.ls;
@@ -490,11 +480,12 @@ hipError_t launch_pure_backward(const float *params, int in_dim, int H, int L, c
     if ((e = gemm_linear(b.a, H, nullptr, nullptr, 0, nullptr, wv_t(w.w_o1, H), nullptr, b.g[cur], N, H, kActNone,
                          nullptr, s)))
       return e;
-    int *off_d = nullptr, *perm_d = nullptr, *off_s = nullptr, *perm_s = nullptr;
+    const int *off_d = nullptr, *perm_d = nullptr, *off_s = nullptr, *perm_s = nullptr;
     if (!chain_nx && L > 0) {
       // the CSR by dst is the tape's; by src: built here
-      edge_buckets_view(t.buckets, N, E, &off_d, &perm_d);
-      if ((e = edge_buckets(ei, E, N, 0, false, b.buckets, &off_s, &perm_s, s))) return e;
+      off_d = t.buckets.off, perm_d = t.buckets.perm;
+      if ((e = edge_buckets(ei, E, N, b.buckets, s))) return e;
+      off_s = b.buckets.off, perm_s = b.buckets.perm;
     }
     float *gP = b.gpq[0], *gQ = b.gpq[0] + N * H;
     for (int l = L - 1; l >= 0; --l) {
@@ -529,15 +520,14 @@ hipError_t launch_pure_backward(const float *params, int in_dim, int H, int L, c
 }
 
 int64_t state_mse_ws_bytes(int B, int nx) {
-  const int64_t n = 3LL * B * nx;
-  return (int64_t)a256(sizeof(float) * std::min<int64_t>(kMseBlocks, (n + 255) / 256));
+  return (int64_t)carve_one<float>(mse_blocks(3LL * B * nx), nullptr).bytes;
 }
 
 hipError_t launch_state_mse(const float *delta, const float *st, const float *sn, int B, int nx, float *loss,
                             float *grad_delta, void *ws, hipStream_t s) {
   const int64_t n = 3LL * B * nx;
-  const int nb = (int)std::min<int64_t>(kMseBlocks, (n + 255) / 256);
-  float *part = static_cast<float *>(ws);
+  const int nb = mse_blocks(n);
+  float *part = carve_one<float>(nb, ws).p;
   hipLaunchKernelGGL(state_mse_kernel, dim3(nb), dim3(256), 0, s, delta, st, sn, n, nx, (float)(2.0 / (double)n), grad_delta,
                      part);
   hipLaunchKernelGGL(state_mse_final_kernel, dim3(1), dim3(256), 0, s, part, nb, (float)(1.0 / (double)n), loss);

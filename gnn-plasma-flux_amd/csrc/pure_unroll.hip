@@ -198,6 +198,12 @@ __global__ __launch_bounds__(kPuThreads) void pure_unroll_adjoint_kernel(const f
   }
 }
 
+// one loss partial per tile; cons: three more (sum u^2, sum E^2, sum n)
+LossWs carve_pure_unroll_ws(int B, int nx, bool cons, void *base) {
+  const size_t n = (size_t)((int64_t)B * tiles_of(nx));
+  return carve_loss_ws(n, cons ? 3 * n : 0, base);
+}
+
 template <bool EX>
 hipError_t update_launch(const float *delta, const float *st, const float *x, int B, int nx, float *st_next,
                          float *nf_next, const float *target, const float *w, float scale, float *loss, void *ws,
@@ -207,7 +213,7 @@ hipError_t update_launch(const float *delta, const float *st, const float *x, in
   LossArgs la{};
   ConsArgs ca{};
   if (target) {
-    const hipError_t e = state_loss_setup(la, ca, target, w, scale, loss, ws, cons, pure_unroll_ws_bytes(B, nx), s);
+    const hipError_t e = state_loss_setup(la, ca, target, w, scale, loss, carve_pure_unroll_ws(B, nx, cons != nullptr, ws), cons, s);
     if (e) return e;
     if (ca.on) ca.B = B, ca.nx = nx, ca.tiles = tiles;
   }
@@ -230,12 +236,8 @@ hipError_t adjoint_launch(const float *st_next, const float *target, const float
 
 }  // namespace
 
-int64_t pure_unroll_ws_bytes(int B, int nx) {
-  return (int64_t)(kCounterBytes + al256(sizeof(double) * (size_t)((int64_t)B * tiles_of(nx))));
-}
-int64_t pure_unroll_ws_bytes_ex(int B, int nx) {
-  return pure_unroll_ws_bytes(B, nx) + (int64_t)al256(3 * sizeof(double) * (size_t)((int64_t)B * tiles_of(nx)));
-}
+int64_t pure_unroll_ws_bytes(int B, int nx) { return (int64_t)carve_pure_unroll_ws(B, nx, false, nullptr).bytes; }
+int64_t pure_unroll_ws_bytes_ex(int B, int nx) { return (int64_t)carve_pure_unroll_ws(B, nx, true, nullptr).bytes; }
 
 // one workgroup per tile: B * tiles of them must fit a grid
 bool pure_unroll_shape_ok(int B, int nx) { return B >= 1 && nx >= 1 && (int64_t)B * tiles_of(nx) <= 0x7fffffffLL; }

@@ -958,20 +958,31 @@ __global__ __launch_bounds__(256, 2) void wgrad_stencil_kernel(WgStencilBatch bt
 inline int64_t wgs_rsplit(int64_t N) { return ((N + kWgsSplits - 1) / kWgsSplits + kWsKC - 1) / kWsKC * kWsKC; }
 inline int64_t wgs_splits(int64_t N) { return (N + wgs_rsplit(N) - 1) / wgs_rsplit(N); }
 
-inline size_t al256(size_t v) { return (v + 255) & ~size_t(255); }
-
+// h[0..L] | pq | with `fused` (FluxGNN(4, 128, L <= 8)): the fused forward's
+// packed weights, its ReLU' bits and the backward's packed transposed weights
+// (written by the forward's pack launch).  The size query does not know the
+// chain length and keeps the fused pieces whenever the width allows them.
 struct ChainTape {
   float *h[kMaxChainLayers + 1];
   float *pq;
+  void *pack;
+  unsigned *mbits;
+  void *bpack;
+  int64_t hstride;  // h[l] = h[0] + l * hstride
+  size_t bytes;
 };
-ChainTape carve_chain_tape(const GraphW &w, int64_t N, void *base) {
-  char *p = static_cast<char *>(base);
+ChainTape carve_chain_tape(const GraphW &w, int64_t N, bool fused, void *base) {
+  Carve c(base);
   ChainTape t{};
-  for (int l = 0; l <= w.layers; ++l) {
-    t.h[l] = reinterpret_cast<float *>(p);
-    p += al256(sizeof(float) * N * w.hidden);
+  for (int l = 0; l <= w.layers; ++l) t.h[l] = c.take<float>(N * w.hidden);
+  t.hstride = (int64_t)(round256(sizeof(float) * N * w.hidden) / 4);
+  t.pq = c.take<float>(N * 2 * w.hidden);
+  if (fused) {
+    t.pack = c.take<char>((size_t)chain_train_pack_bytes(w.layers));
+    t.mbits = reinterpret_cast<unsigned *>(c.take<char>((size_t)chain_train_mask_bytes(w.layers, N)));
+    t.bpack = c.take<char>((size_t)chain_train_bwd_pack_bytes(w.layers));
   }
-  t.pq = reinterpret_cast<float *>(p);
+  t.bytes = c.off;
   return t;
 }
 
@@ -989,58 +1000,62 @@ bool chain_train_ok(const GraphW &w, int chain_nx, int64_t N) {
          w.in_dim <= 8 && N > 0 && N * 2 * H + 2 * H < (int64_t(1) << 31);
 }
 
-// h[0..L] | pq | (FluxGNN(4, 128, L <= 8): the fused forward's packed weights
-// and ReLU' bits; the chain length is unknown here, so the space is kept for
-// every chain)
+// the width of the fused path, whatever the chain length
 bool fused_width(const GraphW &w) { return chain_train_fused_ok(w, 64); }
-int64_t chain_tape_bytes(const GraphW &w, int64_t N) {
-  return (int64_t)((w.layers + 1) * al256(sizeof(float) * N * w.hidden) + al256(sizeof(float) * N * 2 * w.hidden) +
-                   (fused_width(w) ? al256((size_t)chain_train_pack_bytes(w.layers)) +
-                                         al256((size_t)chain_train_mask_bytes(w.layers, N)) +
-                                         al256((size_t)chain_train_bwd_pack_bytes(w.layers))
-                                   : 0));
-}
-// the fused forward's packed weights, ReLU' bits, and the backward's packed
-// transposed weights (written by the forward's pack launch)
-struct FusedTape {
-  void *pack;
-  unsigned *mbits;
-  void *bpack;
-};
-FusedTape fused_tape(const GraphW &w, int64_t N, const ChainTape &t) {
-  char *p = reinterpret_cast<char *>(t.pq) + al256(sizeof(float) * N * 2 * w.hidden);
-  char *m = p + al256((size_t)chain_train_pack_bytes(w.layers));
-  return FusedTape{p, reinterpret_cast<unsigned *>(m), m + al256((size_t)chain_train_mask_bytes(w.layers, N))};
-}
 bool fused_chain(const GraphW &w, int nx, int64_t N) { return chain_train_fused_ok(w, nx) && N % nx == 0; }
+int64_t chain_tape_bytes(const GraphW &w, int64_t N) {
+  return (int64_t)carve_chain_tape(w, N, fused_width(w), nullptr).bytes;
+}
+
+// launch_chain_backward's workspace.  fused: g[0..L] side by side (g[l] = G +
+// l * gstride); wg_batch: every update layer's weight-gradient and bias
+// partials of SB splits (layer l at lpart + l * lpstride, lbpart + l * lbstride).
+// The size query keeps both whenever the width allows, at the larger split count.
+struct ChainBws {
+  float *dPQ, *dl[2];
+  float *part, *bpart;  // weight-gradient partials (largest: 2H x H or H x 2H) and bias partials of S splits
+  float *epart, *ipart;
+  float *G, *lpart, *lbpart;
+  int64_t gstride, lpstride, lbstride;
+  size_t bytes;
+};
+ChainBws carve_chain_bws(const GraphW &w, int64_t N, bool fused, bool wg_batch, int64_t SB, void *base) {
+  const int64_t H = w.hidden, L = w.layers;
+  const int64_t S = tgemm_splits(N, kWgradSplits);
+  Carve c(base);
+  ChainBws b{};
+  b.gstride = (int64_t)(round256(sizeof(float) * N * H) / 4);
+  b.lpstride = (int64_t)(round256(sizeof(float) * SB * 2 * H * H) / 4);
+  b.lbstride = (int64_t)(round256(sizeof(float) * SB * 2 * H) / 4);
+  b.dPQ = c.take<float>(N * 2 * H);
+  b.dl[0] = c.take<float>(N * H);
+  b.dl[1] = c.take<float>(N * H);
+  b.part = c.take<float>(S * 2 * H * H);
+  b.bpart = c.take<float>(S * 2 * H);
+  b.epart = c.take<float>(kEdgeBlocks * (H + 1));
+  b.ipart = c.take<float>(kInputSplits * H * (w.in_dim + 1));
+  if (fused) b.G = c.take<float>((L + 1) * b.gstride);
+  if (wg_batch) {
+    b.lpart = c.take<float>(L * b.lpstride);
+    b.lbpart = c.take<float>(L * b.lbstride);
+  }
+  b.bytes = c.off;
+  return b;
+}
 
 int64_t chain_backward_ws_bytes(const GraphW &w, int64_t N) {
-  const int64_t H = w.hidden;
-  size_t b = al256(sizeof(float) * N * 2 * H);  // dPQ
-  b += 2 * al256(sizeof(float) * N * H);        // deltas
-  const int64_t S = tgemm_splits(N, kWgradSplits);
-  b += al256(sizeof(float) * S * 2 * H * H);    // weight-gradient partials (largest: 2H x H or H x 2H)
-  b += al256(sizeof(float) * S * 2 * H);        // bias partials
-  b += al256(sizeof(float) * kEdgeBlocks * (H + 1));
-  b += al256(sizeof(float) * kInputSplits * H * (w.in_dim + 1));
-  if (fused_width(w)) {  // fused backward: g[0..L] side by side
-    b += (w.layers + 1) * al256(sizeof(float) * N * H);
-    // + every update layer's weight-gradient partials (the layers' GEMMs in one launch)
-    const int64_t SB = std::max(tgemm_splits(N, kWgradBatchSplits), wgs_splits(N));
-    b += w.layers * (al256(sizeof(float) * SB * 2 * H * H) + al256(sizeof(float) * SB * 2 * H));
-  }
-  return (int64_t)b;
+  const bool fused = fused_width(w);
+  const int64_t SB = fused ? std::max(tgemm_splits(N, kWgradBatchSplits), wgs_splits(N)) : 0;
+  return (int64_t)carve_chain_bws(w, N, fused, fused, SB, nullptr).bytes;
 }
 
 hipError_t launch_chain_forward_train(const GraphW &w, const float *nf, int64_t N, int nx, float *flux, void *tape,
                                       hipStream_t s) {
   const int H = w.hidden, L = w.layers, hsh = __builtin_ctz(H);
-  const ChainTape t = carve_chain_tape(w, N, tape);
-  if (fused_chain(w, nx, N)) {  // (N = B * nx on a tagged chain)
-    const FusedTape f = fused_tape(w, N, t);
-    return launch_chain_train_fwd_fused(w, nf, N / nx, nx, flux, t.h[0], (int64_t)(al256(sizeof(float) * N * H) / 4),
-                                        t.pq, f.mbits, f.pack, f.bpack, s);
-  }
+  const bool fused = fused_chain(w, nx, N);  // (N = B * nx on a tagged chain)
+  const ChainTape t = carve_chain_tape(w, N, fused, tape);
+  if (fused)
+    return launch_chain_train_fwd_fused(w, nf, N / nx, nx, flux, t.h[0], t.hstride, t.pq, t.mbits, t.pack, t.bpack, s);
 #define HF_IN_FWD(FF)                                                                                      \
   hipLaunchKernelGGL(input_forward_kernel<FF>, dim3((unsigned)((N * (H / 4) + 255) / 256)), dim3(256), 0, s, nf, \
                      w.w_in, w.b_in, H, N, t.h[0])
@@ -1074,7 +1089,6 @@ static_assert(pr_job_ok(2 * kH, kH, kH) && pr_job_ok(kH, 2 * kH, kH) && pr_job_o
 hipError_t launch_chain_backward(const GraphW &w, const float *nf, int64_t N, int nx, const void *tape,
                                  const float *grad_flux, float *grad_params, float *grad_nf, void *ws, hipStream_t s) {
   const int H = w.hidden, L = w.layers, F = w.in_dim, hsh = __builtin_ctz(H);
-  const ChainTape t = carve_chain_tape(w, N, const_cast<void *>(tape));
   const GraphW g = graph_view_state_dict(grad_params, F, H, L);
   // The two paths and the fused path's launch shapes:
   // fused: FluxGNN(4, 128) on nx in {16, 32, 48, 64}: every layer's data gradient in one
@@ -1087,26 +1101,15 @@ hipError_t launch_chain_backward(const GraphW &w, const float *nf, int64_t N, in
   const bool wg_batch = fused && L >= 1;
   const bool wgs = wg_batch && nx % kWsKC == 0 && N % kWsKC == 0 && N * kWsH < (int64_t(1) << 31);
   const bool one_reduce = wgs, in_fold = wgs;
-  char *p = static_cast<char *>(ws);
-  auto take = [&](size_t bytes) {
-    float *r = reinterpret_cast<float *>(p);
-    p += al256(bytes);
-    return r;
-  };
+  const ChainTape t = carve_chain_tape(w, N, fused, const_cast<void *>(tape));
   const int64_t S = tgemm_splits(N, kWgradSplits);
   const int64_t SB = wgs ? wgs_splits(N) : tgemm_splits(N, kWgradBatchSplits);
-  const int64_t gstride = (int64_t)(al256(sizeof(float) * N * H) / 4);
-  const int64_t lpstride = (int64_t)(al256(sizeof(float) * SB * 2 * H * H) / 4),
-                lbstride = (int64_t)(al256(sizeof(float) * SB * 2 * H) / 4);
-  float *dPQ = take(sizeof(float) * N * 2 * H);
-  float *dl[2] = {take(sizeof(float) * N * H), take(sizeof(float) * N * H)};
-  float *part = take(sizeof(float) * S * 2 * H * H);
-  float *bpart = take(sizeof(float) * S * 2 * H);
-  float *epart = take(sizeof(float) * kEdgeBlocks * (H + 1));
-  float *ipart = take(sizeof(float) * kInputSplits * H * (F + 1)), *ipb = ipart + (int64_t)kInputSplits * H * F;
-  float *G = fused ? take((L + 1) * al256(sizeof(float) * N * H)) : nullptr;  // g[l] = G + l * gstride
-  float *lpart = wg_batch ? take(L * al256(sizeof(float) * SB * 2 * H * H)) : nullptr;
-  float *lbpart = wg_batch ? take(L * al256(sizeof(float) * SB * 2 * H)) : nullptr;
+  const ChainBws b = carve_chain_bws(w, N, fused, wg_batch, SB, ws);
+  const int64_t gstride = b.gstride, lpstride = b.lpstride, lbstride = b.lbstride;
+  float *dPQ = b.dPQ, *part = b.part, *bpart = b.bpart, *epart = b.epart;
+  float *const *dl = b.dl;
+  float *ipart = b.ipart, *ipb = ipart + (int64_t)kInputSplits * H * F;
+  float *G = b.G, *lpart = b.lpart, *lbpart = b.lbpart;
   hipError_t e;
   PrJobs jobs{};
   // the reduction of part / bpart's splits: a job of the final launch, or a launch of its own
@@ -1150,8 +1153,8 @@ hipError_t launch_chain_backward(const GraphW &w, const float *nf, int64_t N, in
   const float *d0;  // g[0], the input layer's delta
   if (fused) {
     // g[L] = ReLU'(h[L]) * [W_a ; W_b]^T dPQ and every layer's data gradient below it, in one pass
-    const FusedTape f = fused_tape(w, N, t);  // (bpack: packed by the forward)
-    if ((e = launch_chain_train_bwd_fused(w, N / nx, nx, G, gstride, f.mbits, f.bpack, dPQ, s))) return e;
+    // (bpack: packed by the forward)
+    if ((e = launch_chain_train_bwd_fused(w, N / nx, nx, G, gstride, t.mbits, t.bpack, dPQ, s))) return e;
     d0 = G;
     if (wgs) {  // dW_l, db_l of every update layer: one launch
       WgStencilBatch bt{};
@@ -1248,18 +1251,31 @@ hipError_t launch_chain_backward(const GraphW &w, const float *nf, int64_t N, in
   return hipGetLastError();
 }
 
-int64_t ablation_loss_ws_bytes(int B, int nx) {
-  return (int64_t)(2 * al256(sizeof(float) * (size_t)B * nx) + al256(sizeof(float) * (size_t)B * kLossParts));
+namespace {
+// the unfused loss's n' and detached E' [B][nx], and every IC's term partials
+struct AblationWs {
+  float *nn, *En, *part;
+  size_t bytes;
+};
+AblationWs carve_ablation_ws(int B, int nx, void *base) {
+  Carve c(base);
+  AblationWs a{};
+  a.nn = c.take<float>((size_t)B * nx);
+  a.En = c.take<float>((size_t)B * nx);
+  a.part = c.take<float>((size_t)B * kLossParts);
+  a.bytes = c.off;
+  return a;
 }
+}  // namespace
+
+int64_t ablation_loss_ws_bytes(int B, int nx) { return (int64_t)carve_ablation_ws(B, nx, nullptr).bytes; }
 
 hipError_t launch_ablation_loss(const float *fe, const float *st, const float *ft, const float *sn, int B, int nx,
                                 float c, float dx, const float *lam, int roll, float dt, const double *pc, float *loss,
                                 float *flux_loss, float *dfe, void *ws, hipStream_t s) {
   const int r = lam[4] > 0.f ? roll : 0;  // the rollout energy term (K <= kLossMaxRollout)
-  char *p = static_cast<char *>(ws);
-  float *nn = reinterpret_cast<float *>(p);
-  float *En = reinterpret_cast<float *>(p + al256(sizeof(float) * (size_t)B * nx));
-  float *part = reinterpret_cast<float *>(p + 2 * al256(sizeof(float) * (size_t)B * nx));
+  const AblationWs a = carve_ablation_ws(B, nx, ws);
+  float *nn = a.nn, *En = a.En, *part = a.part;
   if (!poisson_uses_fft(nx) && nx <= kLossFusedMaxNx) {
     hipLaunchKernelGGL(loss_step_kernel, dim3((unsigned)B), dim3(256), (size_t)nx * (sizeof(double) + 2 * sizeof(float)),
                        s, fe, st, ft, sn, pc, B, nx, c, lam[0], dt, r, part, dfe);

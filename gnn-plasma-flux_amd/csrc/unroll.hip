@@ -382,11 +382,10 @@ hipError_t adjoint_fft_launch(const float *st, const AdjIn &g, const double *pc,
 
 bool unroll_nx_ok(int nx) { return nx >= 1 && nx <= kFvLdsMaxNx; }
 
-int64_t unroll_ws_bytes(int B, int nx) {
-  (void)nx;
-  return (int64_t)(kCounterBytes + al256(sizeof(double) * (size_t)B));
-}
-int64_t unroll_ws_bytes_ex(int B, int nx) { return unroll_ws_bytes(B, nx) + (int64_t)al256(2 * sizeof(double) * (size_t)B); }
+// one loss partial per IC; cons: two more (energy, charge)
+static LossWs carve_unroll_ws(int B, bool cons, void *base) { return carve_loss_ws((size_t)B, cons ? 2 * (size_t)B : 0, base); }
+int64_t unroll_ws_bytes(int B, int) { return (int64_t)carve_unroll_ws(B, false, nullptr).bytes; }
+int64_t unroll_ws_bytes_ex(int B, int) { return (int64_t)carve_unroll_ws(B, true, nullptr).bytes; }
 
 hipError_t launch_unroll_update(bool ex, const float *fe, const float *st, const float *x, const double *pc, int B,
                                 int nx, float c, float dt, float *st_next, float *nf_next, const float *target,
@@ -397,8 +396,8 @@ hipError_t launch_unroll_update(bool ex, const float *fe, const float *st, const
   LossArgs la{};
   ConsArgs ca{};
   if (target) {
-    const hipError_t e =
-        state_loss_setup(la, ca, target, w, scale, loss, ws, ex ? cons : nullptr, unroll_ws_bytes(B, nx), s);
+    if (!ex) cons = nullptr;
+    const hipError_t e = state_loss_setup(la, ca, target, w, scale, loss, carve_unroll_ws(B, cons != nullptr, ws), cons, s);
     if (e) return e;
   }
   switch (poisson_uses_fft(nx) ? nx : 0) {

@@ -10,11 +10,24 @@
 namespace hf {
 namespace {
 
-inline size_t al256(size_t b) { return (b + 255) / 256 * 256; }
-
 // Every workspace starts with the arrival counter: [0, 256), zeroed by the
-// launcher's memset node before every launch; the float64 partials follow.
+// launcher's memset node before every launch; the float64 loss partials
+// follow, and behind them the conservation terms' partials of an _ex call.
 constexpr size_t kCounterBytes = 256;
+struct LossWs {
+  unsigned *cnt;
+  double *part, *cons_part;
+  size_t bytes;
+};
+inline LossWs carve_loss_ws(size_t parts, size_t cons_parts, void *base) {
+  Carve c(base);
+  LossWs w{};
+  w.cnt = reinterpret_cast<unsigned *>(c.take<char>(kCounterBytes));
+  w.part = c.take<double>(parts);
+  w.cons_part = c.take<double>(cons_parts);
+  w.bytes = c.off;
+  return w;
+}
 
 __device__ __forceinline__ double wave_sum(double a) {
 #pragma unroll
@@ -68,7 +81,7 @@ struct StateConsArgs {
   double lam_e, lam_q, scale;  // scale = cons_scale
   const double *ref;           // [B][2] (eref, qref)
   float *coef;                 // [B][2] (ce, cq)
-  double *part;                // the terms' partials, cons_off bytes into ws
+  double *part;                // the terms' partials (LossWs::cons_part)
 };
 
 // The energy and charge terms of IC b (include/hybridflux.h) from its complete
@@ -87,28 +100,27 @@ __device__ __forceinline__ void cons_terms(const StateConsArgs &ca, I b, double 
   pq = ca.lam_q * (rq * rq);
 }
 
-// Turns the terms on: their partials lie cons_off bytes into ws.
-inline void cons_setup(StateConsArgs &ca, const ConsTerms &cons, void *ws, int64_t cons_off) {
+// Turns the terms on.
+inline void cons_setup(StateConsArgs &ca, const ConsTerms &cons, double *cons_part) {
   ca.on = true;
   ca.lam_e = (double)cons.lam_e, ca.lam_q = (double)cons.lam_q, ca.scale = (double)cons.scale;
   ca.ref = cons.ref, ca.coef = cons.coef;
-  ca.part = reinterpret_cast<double *>(static_cast<char *>(ws) + cons_off);
+  ca.part = cons_part;
 }
 
 // Fills both for a launch with a target (cons NULL: the terms stay off) and
 // enqueues the counter's reset.
 inline hipError_t state_loss_setup(StateLossArgs &la, StateConsArgs &ca, const float *target, const float *w,
-                                   float scale, float *loss, void *ws, const ConsTerms *cons, int64_t cons_off,
-                                   hipStream_t s) {
+                                   float scale, float *loss, const LossWs &ws, const ConsTerms *cons, hipStream_t s) {
   la.tgt = target;
   la.w0 = w[0], la.w1 = w[1], la.w2 = w[2];
   la.scale = (double)scale;
-  la.cnt = static_cast<unsigned *>(ws);
-  la.part = reinterpret_cast<double *>(static_cast<char *>(ws) + kCounterBytes);
+  la.cnt = ws.cnt;
+  la.part = ws.part;
   la.loss = loss;
-  if (cons) cons_setup(ca, *cons, ws, cons_off);
+  if (cons) cons_setup(ca, *cons, ws.cons_part);
   // the arrival counter starts every launch at 0 (a memset node, not a kernel)
-  return hipMemsetAsync(ws, 0, 16, s);
+  return hipMemsetAsync(ws.cnt, 0, 16, s);
 }
 
 }  // namespace

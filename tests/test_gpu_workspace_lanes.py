@@ -86,6 +86,29 @@ def test_workspace_need_exact(hf, nx):
     torch.cuda.synchronize(DEV)
 
 
+def test_recorded_device_sizes(hf):
+    """The size queries that take a handle return what tests/workspace_sizes.json
+    recorded under "device" (tools/dump_workspace_sizes.py names the handles and
+    builds them): handles only, no rollout."""
+    import json
+    import os
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, "tools"))
+    import dump_workspace_sizes as table
+    from hybridflux._lib import lib
+    with open(os.path.join(root, "tests", "workspace_sizes.json")) as f:
+        recorded = json.load(f)["device"]
+    assert sorted(recorded) == sorted(table.HANDLE_QUERIES)
+    handles, keep = table.device_handles()
+    for name, rows in recorded.items():
+        f = getattr(lib(), name)
+        assert rows
+        bad = [(row[:-1], row[-1], got) for row in rows for got in [f(handles[row[0]], *row[1:-1])] if got != row[-1]]
+        assert not bad, f"{name}: {len(bad)} of {len(rows)} rows differ (args, recorded, got): {bad[:5]}"
+    del keep
+
+
 @pytest.mark.timeout(300)
 def test_lanes_per_caller_stream(hf):
     """3-lane rollouts (B*nx >= 3*2^20 cells) on two caller streams at once,
