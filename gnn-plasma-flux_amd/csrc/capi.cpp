@@ -1257,6 +1257,45 @@ int hf_ic_draws_host(int64_t seed, int nx, double *table, double *gauss) {
   return HF_OK;
 }
 
+int hf_state_noise(const int64_t *seeds, int B, int nx, const float *sigma, int flags, const float *state_in,
+                   float *state_out, const double *plan, int pm, const float *x, float *nf, float *noise,
+                   void *stream) {
+  const char *fn = "hf_state_noise";
+  if (B < 0 || nx < 1) return fail(HF_EINVAL, "hf_state_noise: bad shape");
+  if (!sigma) return fail(HF_EINVAL, "hf_state_noise: NULL pointer (sigma)");
+  for (int ch = 0; ch < 3; ++ch)
+    if (!(sigma[ch] >= 0.0f)) return fail(HF_EINVAL, "hf_state_noise: sigma must be >= 0 (and not NaN)");
+  if (flags & ~HF_NOISE_ZERO_MEAN) return fail(HF_EINVAL, "hf_state_noise: unknown flags");
+  if (nf && !x) return fail(HF_EINVAL, "hf_state_noise: node features need dev_x");
+  if (B > 0 && (!seeds || !state_in || !state_out)) return fail(HF_EINVAL, "hf_state_noise: NULL pointer");
+  if (plan) {
+    if (sigma[2] != 0.0f)
+      return fail(HF_EINVAL, "hf_state_noise: with a Poisson plan E is recomputed from n: sigma[2] must be 0");
+    if (int rc = check_mode(pm, nx, fn)) return rc;
+  }
+  if (nx > hf::kIcMaxNx) return fail(HF_EUNSUPPORTED, "hf_state_noise: nx > 2^24");
+  const bool zero_mean = (flags & HF_NOISE_ZERO_MEAN) != 0;
+  if (zero_mean && nx > hf::kNoiseZeroMeanMaxNx)
+    return fail(HF_EUNSUPPORTED, "hf_state_noise: HF_NOISE_ZERO_MEAN needs nx <= 6144");
+  if (B == 0) return HF_OK;
+  hipStream_t s = as_stream(stream);
+  HF_CHECK_HIP(hf::launch_state_noise(seeds, B, nx, sigma, zero_mean, plan != nullptr, state_in, state_out, noise, s),
+               fn);
+  if (plan)
+    HF_CHECK_HIP(hf::launch_poisson(state_out, 3 * nx, state_out + 2 * (int64_t)nx, 3 * nx, plan, B, nx, pm, s), fn);
+  HF_CHECK_HIP(hf::launch_state_finish(state_out, x, B, nx, plan != nullptr, nf, s), fn);
+  return HF_OK;
+}
+
+int hf_gauss_host(int64_t seed, int64_t count, double *gauss) {
+  if (seed < 0 || seed > 0xffffffffLL) return fail(HF_EINVAL, "hf_gauss_host: Seed must be between 0 and 2**32 - 1");
+  if (count < 0) return fail(HF_EINVAL, "hf_gauss_host: count < 0");
+  if (count > 3LL * hf::kIcMaxNx) return fail(HF_EUNSUPPORTED, "hf_gauss_host: count > 3 * 2^24");
+  if (count > 0 && !gauss) return fail(HF_EINVAL, "hf_gauss_host: NULL pointer");
+  if (!hf::gauss_host(seed, count, gauss)) return fail(HF_EINVAL, "hf_gauss_host: bad argument");
+  return HF_OK;
+}
+
 int64_t hf_run_workspace_bytes(int op, int B, int nx, int T) {
   if (B < 0 || nx < 1 || T < 0 || op < HF_OP_STEP || op > HF_OP_COMPARE) return -1;
   const int64_t S = 4LL * 3 * nx, F = 4LL * nx;

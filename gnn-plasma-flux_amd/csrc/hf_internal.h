@@ -492,6 +492,19 @@ constexpr int kIcMaxNx = 1 << 24;
 hipError_t launch_initial_conditions(const int64_t *seeds, int B, int nx, const double *x, float *state, double *table,
                                      hipStream_t s);
 bool ic_draws_host(int64_t seed, int nx, double *table, double *gauss);
+// Seeded Gaussian state noise (initial_conditions.hip, on the same draw code;
+// include/hybridflux.h hf_state_noise): out = in + f32(sig[ch]) * f32(d), one
+// wave per sample; rows with sig[ch] == 0 are copied, row E is left to the
+// caller's Poisson launch when skip_E.  zero_mean holds g_n in LDS: nx <=
+// kNoiseZeroMeanMaxNx.  launch_state_finish, behind the Poisson launch: seal
+// (with skip_E) turns the samples the noise kernel marked as failed NaN (their
+// n row stayed finite for the solve); nf (or NULL) [B*nx][4] = [n, u, E, x].
+// gauss_host: standard_normal(count) of RandomState(seed); false: bad seed or count.
+constexpr int kNoiseZeroMeanMaxNx = 6144;
+hipError_t launch_state_noise(const int64_t *seeds, int B, int nx, const float *sig, bool zero_mean, bool skip_E,
+                              const float *in, float *out, float *noise, hipStream_t s);
+hipError_t launch_state_finish(float *state, const float *x, int B, int nx, bool seal, float *nf, hipStream_t s);
+bool gauss_host(int64_t seed, int64_t count, double *gauss);
 
 int64_t graph_workspace_bytes(const GraphW &w, int64_t N, int64_t E);
 // Training forward (activation tape) and backward, graph_train section of graph.hip.

@@ -6,7 +6,9 @@ points (step_batch / run_batch), HybridEnsemble (a set of checkpoints rolled
 out in one launch), the engine module and the multi-GPU IC-sharded rollout
 driver, and FineReference (the classical solver on a refined grid with
 substeps, coarse-grained onto the training grid in one launch: the data and
-the score behind the reference README's fine-baseline claims).
+the score behind the reference README's fine-baseline claims), and
+StateNoise (seeded Gaussian noise on a training step's start state, drawn on
+the device; the K-step trainers' noise= option).
 """
 from .baseline_solver import BaselineSolver
 from .baselines import PINN, PureGNN
@@ -15,6 +17,7 @@ from .fine_reference import FineReference
 from .flux_gnn import FluxGNN
 from .graph_constructor import build_chain_graph, build_chain_graph_batch, chain_edge_index
 from .hybrid_solver import HybridEnsemble, HybridSolver
+from .training import StateNoise
 
 __all__ = [
     "BaselineSolver",
@@ -24,6 +27,7 @@ __all__ = [
     "FluxGNN",
     "HybridSolver",
     "HybridEnsemble",
+    "StateNoise",
     "build_chain_graph",
     "build_chain_graph_batch",
     "chain_edge_index",

@@ -30,6 +30,7 @@ HF_WS_FLUX_FACE = 2
 HF_POISSON_SPECTRAL = 0
 HF_POISSON_TRIDIAG = 1
 HF_IC_TABLE_LEN = 23
+HF_NOISE_ZERO_MEAN = 1
 HF_OPT_NUM_STATS = 4
 
 # name -> (restype, argtypes); mirrors include/hybridflux.h exactly.
@@ -97,6 +98,9 @@ SIGNATURES = {
     "hf_poisson_ex": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "hf_initial_conditions": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hf_ic_draws_host": (c_int, [c_int64, c_int, c_void_p, c_void_p]),
+    "hf_state_noise": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                               c_void_p, c_void_p, c_void_p]),
+    "hf_gauss_host": (c_int, [c_int64, c_int64, c_void_p]),
     "hf_run_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
     "hf_workspace_need": (c_int64, [c_void_p, c_int, c_int, c_int, c_int, c_int]),
     "hf_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,

@@ -823,6 +823,70 @@ def initial_conditions(grid, seeds, debug=False, device=None):
     return (st, table) if debug else st
 
 
+def noise_sigma(sigma):
+    """(sigma_n, sigma_u, sigma_E) -> host float32 [3]; each >= 0."""
+    s = np.ascontiguousarray(np.asarray(sigma, dtype=np.float32).reshape(-1))
+    if s.size != 3 or not (s >= 0).all():
+        raise ValueError(f"sigma must be (sigma_n, sigma_u, sigma_E), each >= 0, got {sigma!r}")
+    return s
+
+
+def state_noise(state, seeds, sigma, zero_mean=True, grid=None, x=None, out=None, return_noise=False):
+    """hf_state_noise: state [B,3,nx] (contiguous float32 on the device) plus
+    seeded Gaussian noise, sample b from np.random.RandomState(seeds[b])
+    .standard_normal(3 nx) (blocks n, u, E) drawn on the device, one wave per
+    sample: out[ch] = state[ch] + f32(sigma[ch]) * f32(g_ch), a channel with
+    sigma 0 copied bit for bit.  zero_mean: the mean of the n noise is removed
+    (float64, fixed order), so the charge stays; needs nx <= 6144.  grid (an
+    engine.Grid): E is recomputed from the perturbed n by the grid's Poisson
+    solve, and sigma_E must be 0.  x [nx] (float32 on the device): also the node
+    features [B*nx,4] = [n', u', E', x].  seeds: integers on the host (validated
+    as numpy validates a seed, uploaded once) or an int64 tensor [B] on the
+    device, used as it is (no host sync; a seed outside [0, 2^32) gives a NaN
+    sample).  out: the tensor to write, `state` itself for an in-place call.
+    Returns out, then the node features (with x), then the added float32 values
+    [B,3,nx] (with return_noise)."""
+    require_device(state, "state")
+    if state.dim() != 3 or state.shape[1] != 3 or state.shape[2] < 1 or state.dtype != torch.float32 \
+            or not state.is_contiguous():
+        raise ValueError(f"state must be contiguous float32 [B,3,nx], got {tuple(state.shape)} {state.dtype}")
+    B, _, nx = state.shape
+    dev = state.device
+    sig = noise_sigma(sigma)
+    if isinstance(seeds, torch.Tensor) and seeds.is_cuda:
+        if seeds.dtype != torch.int64 or seeds.device != dev:
+            raise ValueError(f"device seeds must be int64 on {dev}, got {seeds.dtype} on {seeds.device}")
+        sd = seeds.reshape(-1).contiguous()
+    else:
+        sd = torch.as_tensor(ic_seeds(seeds), device=dev)
+    if sd.numel() != B:
+        raise ValueError(f"need one seed per sample: {sd.numel()} seeds for {B} states")
+    if out is None:
+        out = torch.empty_like(state)
+    elif out is not state and (out.shape != state.shape or out.dtype != state.dtype or out.device != dev
+                               or not out.is_contiguous()):
+        raise ValueError(f"out must be contiguous float32 {tuple(state.shape)} on {dev}")
+    plan, pmode = None, 0
+    if grid is not None:
+        if grid.nx != nx:
+            raise ValueError(f"grid.nx = {grid.nx} but the states have nx = {nx}")
+        if sig[2] != 0:
+            raise ValueError("with a grid E is recomputed from the perturbed n: sigma_E must be 0")
+        plan, pmode = grid.on(dev)[1], grid.pmode
+    nf = None
+    if x is not None:
+        require_device(x, "x")
+        if x.dtype != torch.float32 or x.numel() != nx or not x.is_contiguous():
+            raise ValueError(f"x must be contiguous float32 [{nx}], got {tuple(x.shape)} {x.dtype}")
+        nf = torch.empty(B * nx, 4, dtype=torch.float32, device=dev)
+    noise = torch.empty_like(state) if return_noise else None
+    with torch.cuda.device(dev):
+        check(lib().hf_state_noise(ptr(sd), B, nx, ptr(sig), _lib.HF_NOISE_ZERO_MEAN if zero_mean else 0, ptr(state),
+                                   ptr(out), ptr(plan), pmode, ptr(x), ptr(nf), ptr(noise), stream_of(dev)))
+    res = (out,) + ((nf,) if x is not None else ()) + ((noise,) if return_noise else ())
+    return res[0] if len(res) == 1 else res
+
+
 def _series(t, shape_tail, what):
     require_device(t, what)
     if t.dim() == 4:  # [M,B,T+1,.] of a model set: the rows are independent, so M*B of them

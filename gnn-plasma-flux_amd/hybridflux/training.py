@@ -48,6 +48,11 @@ terms on the predicted states, which under a K-step loss carry a gradient (the
 reference's never do), formed inside the launches the driver already makes (the
 _ex entry points) from per-IC float64 sums; _Cons, _cons_refs and the
 workspace_ex hook of _Rollout are all the driver needs for them.
+
+All three K-step trainers take noise=StateNoise(...): every window starts from
+its first state plus seeded Gaussian noise drawn on the device
+(engine.state_noise, hf_state_noise) against the clean targets; the datasets'
+batch(..., noise=, seeds=) is where it is applied.
 """
 import json
 import os
@@ -249,6 +254,40 @@ def train_flop_per_sample(cfg, nx=64, H=128, L=4, F=4):
     return ((fwd + bwd) + extra * fwd) * nx
 
 
+class StateNoise:
+    """Seeded Gaussian noise on a training step's start state (the targets stay
+    clean, so the model learns to pull a drifted state back):
+    engine.state_noise with sigma = (sigma_n, sigma_u, sigma_E), one
+    np.random.RandomState(seed).standard_normal(3 nx) per sample, drawn on the
+    device.  zero_mean: the n noise loses its mean, so the charge is kept.  grid
+    (an engine.Grid): E is recomputed from the perturbed n with the grid's
+    Poisson solve, so the start is a consistent solver state; sigma_E must then
+    be 0.  Passed as noise= to WindowDataset.batch, FluxDataset.batch and the
+    K-step trainers."""
+
+    def __init__(self, sigma_n, sigma_u, sigma_E=0.0, zero_mean=True, grid=None):
+        self.sigma = engine.noise_sigma((sigma_n, sigma_u, sigma_E))
+        self.zero_mean, self.grid = bool(zero_mean), grid
+        if grid is not None and self.sigma[2] != 0:
+            raise ValueError("StateNoise: with a grid E is recomputed from the perturbed n: sigma_E must be 0")
+
+    def with_grid(self, grid):
+        """This noise with E recomputed on grid."""
+        return StateNoise(*self.sigma, zero_mean=self.zero_mean, grid=grid)
+
+    def apply(self, state, seeds, x=None):
+        """state [B,3,nx] perturbed with one seed per sample (a new tensor);
+        with x [nx] also the node features [B*nx,4] of the perturbed state."""
+        return engine.state_noise(state, seeds, self.sigma, self.zero_mean, self.grid, x)
+
+
+def _noise_seeds(noise, seeds):
+    if noise is not None and seeds is None:
+        raise ValueError("noise needs seeds: one integer in [0, 2**32) per sample of the batch")
+    if noise is None and seeds is not None:
+        raise ValueError("seeds given without noise")
+
+
 class FluxDataset:
     """Device-resident (state_t, flux_t, state_next) triples (train_ablation.py:27-44)."""
 
@@ -268,7 +307,7 @@ class FluxDataset:
         if idx.numel() and (int(idx.min()) < -self.N or int(idx.max()) >= self.N):
             raise IndexError(f"sample index out of range for a dataset of {self.N} samples")
 
-    def batch(self, idx, x=None, check=True):
+    def batch(self, idx, x=None, check=True, noise=None, seeds=None):
         """(state_t, flux_t, state_next)[idx]; with x (the grid positions [nx])
         also the batch's chain node features, all four from one HIP pass
         (engine.chain_batch): (st, ft, sn, node_features).  Indices outside
@@ -276,12 +315,21 @@ class FluxDataset:
         (check_indices: a host sync); check=False skips that for indices the
         caller has already checked (train_steps checks a pass's order once),
         and then the device gather clamps an out-of-range index to [0, N)
-        instead of raising (include/hybridflux.h hf_chain_batch_gather)."""
+        instead of raising (include/hybridflux.h hf_chain_batch_gather).
+        noise (a StateNoise) with seeds (one per sample of the batch): state_t
+        is perturbed and the node features are rebuilt from it; flux_t and
+        state_next stay clean."""
+        _noise_seeds(noise, seeds)
         if check:
             self.check_indices(idx)
         if x is None:
-            return self.state_t[idx], self.flux_t[idx], self.state_next[idx]
-        return engine.chain_batch(idx, self.state_t, self.flux_t, self.state_next, x)
+            st, ft, sn = self.state_t[idx], self.flux_t[idx], self.state_next[idx]
+            return (st if noise is None else noise.apply(st.contiguous(), seeds)), ft, sn
+        st, ft, sn, nf = engine.chain_batch(idx, self.state_t, self.flux_t, self.state_next, x)
+        if noise is not None:
+            x32 = torch.as_tensor(x, dtype=torch.float32, device=st.device).reshape(-1).contiguous()
+            st, nf = noise.apply(st, seeds, x=x32)
+        return st, ft, sn, nf
 
 
 class FlatAdam(torch.optim.Optimizer):
@@ -1047,7 +1095,7 @@ def _rollout_step(m, model, opt, traj, x, grid, channel_weights, through_state, 
 
 
 def _train_windows(m, model, data, x, grid, init, epochs, lr, batch_size, seed, channel_weights, through_state,
-                   device, save_dir, log, guard=(0.0, None, False, None), cons=None):
+                   device, save_dir, log, guard=(0.0, None, False, None), cons=None, noise=None, noise_seed=0):
     """The K-step trainers' loop: Adam(lr) over shuffled batches of batch_size
     windows of data (a WindowDataset), one direct step each (the autograd step
     where that does not apply), one host sync per epoch.  model: the freshly
@@ -1057,7 +1105,11 @@ def _train_windows(m, model, data, x, grid, init, epochs, lr, batch_size, seed, 
     of the steps that were applied, and the history gains grad_norm_max and
     skipped_steps.  cons (a _Cons): the energy and charge terms are on, and the
     history gains energy_loss and charge_loss, the epoch's means of the two
-    terms' values, weighted as loss."""
+    terms' values, weighted as loss.  noise (a StateNoise): every window starts
+    from its perturbed first state (WindowDataset.batch); once per epoch one
+    seed per sample is drawn from a generator of its own seeded with noise_seed
+    (the shuffle's order does not change) and indexed by sample on the device,
+    and the history gains noise, the sigmas."""
     K = data.K
     x_dev = torch.as_tensor(np.asarray(x, dtype=np.float32), device=device) if x is not None else None
     if init is not None:
@@ -1068,17 +1120,23 @@ def _train_windows(m, model, data, x, grid, init, epochs, lr, batch_size, seed, 
     opt, sched = _guarded_optimizer(model.parameters(), lr, *guard, device)
     gen = torch.Generator().manual_seed(0 if seed is None else seed)
     history = {"epoch": [], "loss": [], "seconds": []}
+    if noise is not None:
+        noise_gen = torch.Generator().manual_seed(noise_seed)
+        history["noise"] = [float(v) for v in noise.sigma]
     if cons is not None:
         history["energy_loss"], history["charge_loss"] = [], []
     stats = _StepStats(opt, history)
     model.train()
     for epoch in range(1, epochs + 1):
         order = torch.randperm(len(data), generator=gen).to(device)
+        if noise is not None:
+            seeds = torch.randint(0, 2 ** 32, (len(data),), dtype=torch.int64, generator=noise_gen).to(device)
         t0 = time.perf_counter()
         losses = []
         rows = [] if cons is not None else None  # the steps' loss rows [K, terms]
         for b0 in range(0, len(order), batch_size):
-            win = data.batch(order[b0:b0 + batch_size])
+            idx = order[b0:b0 + batch_size]
+            win = data.batch(idx) if noise is None else data.batch(idx, noise, seeds[idx])
             loss = _rollout_step(m, model, opt, win, x_dev, grid, channel_weights, through_state, cons, rows)
             if loss is None:
                 if cons is None:
@@ -1207,20 +1265,27 @@ class WindowDataset:
     def __len__(self):
         return self.N * self.per_ic
 
-    def batch(self, idx):
-        """Windows [B,K+1,3,nx] of the sample indices idx (each in [0, len))."""
+    def batch(self, idx, noise=None, seeds=None):
+        """Windows [B,K+1,3,nx] of the sample indices idx (each in [0, len)).
+        noise (a StateNoise) with seeds (one per window of the batch): the
+        window's first state is perturbed; rows 1..K, the targets, stay the
+        clean classical states."""
+        _noise_seeds(noise, seeds)
         idx = torch.as_tensor(idx, device=self.traj.device).to(torch.long).reshape(-1)
         if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= len(self)):
             raise IndexError(f"sample index out of range for a dataset of {len(self)} windows")
         ic = torch.div(idx, self.per_ic, rounding_mode="floor")
         t0 = idx - ic * self.per_ic
-        return self.traj[ic[:, None], t0[:, None] + self._steps[None, :]]
+        win = self.traj[ic[:, None], t0[:, None] + self._steps[None, :]]
+        if noise is not None:
+            win[:, 0] = noise.apply(win[:, 0].contiguous(), seeds)
+        return win
 
 
 def train_unrolled(trajectories, x, dt, dx, nu, K=4, epochs=10, lr=1e-3, batch_size=32, seed=None, init=None,
                    channel_weights=(1.0, 1.0, 1.0), through_state=True, device="cuda", save_dir="checkpoints",
                    log=print, weight_decay=0.0, max_grad_norm=None, skip_nonfinite=False, scheduler=None,
-                   conservation=None, conservation_ref="target", graph_radius=1):
+                   conservation=None, conservation_ref="target", graph_radius=1, noise=None, noise_seed=0):
     """Train (or fine-tune) FluxGNN on K-step windows of classical trajectories
     [N,T+1,3,nx] (datagen.generate_trajectories) with the unrolled loss: Adam(lr)
     over shuffled batches of batch_size windows, one unrolled_step each.  init:
@@ -1233,7 +1298,12 @@ def train_unrolled(trajectories, x, dt, dx, nu, K=4, epochs=10, lr=1e-3, batch_s
     turning every parameter into NaN.  conservation = (lam_e, lam_q),
     conservation_ref "target" or "start": unrolled_loss's energy and charge
     terms; the history then also holds energy_loss and charge_loss.
-    graph_radius: 1 only (ValueError otherwise)."""
+    graph_radius: 1 only (ValueError otherwise).  noise (a StateNoise with
+    sigma_E = 0), noise_seed: every window starts from its first state plus
+    seeded Gaussian noise, E recomputed from the perturbed n on the step's grid,
+    against the clean targets; one seed per sample and epoch from a generator
+    seeded with noise_seed, apart from the shuffle's; the history then also holds
+    noise, the sigmas.  None (the default): the calls and bits without it."""
     _radius_one_only("train_unrolled", graph_radius)
     cons = _conservation(conservation, conservation_ref, trainer=True)
     engine.require_device(torch.empty(0, device=device), "device")
@@ -1246,7 +1316,8 @@ def train_unrolled(trajectories, x, dt, dx, nu, K=4, epochs=10, lr=1e-3, batch_s
     model = FluxGNN(MODEL_CONFIG["input_dim"], MODEL_CONFIG["hidden_dim"], MODEL_CONFIG["num_layers"])
     return _train_windows(_FLUX, model, data, x, grid, init, epochs, lr, batch_size, seed, channel_weights,
                           through_state, device, save_dir, log,
-                          (weight_decay, max_grad_norm, skip_nonfinite, scheduler), cons)
+                          (weight_decay, max_grad_norm, skip_nonfinite, scheduler), cons,
+                          None if noise is None else noise.with_grid(grid), noise_seed)
 
 
 def pure_unrolled_loss(model, traj, x, channel_weights=(1.0, 1.0, 1.0), through_state=True, return_states=False,
@@ -1303,7 +1374,8 @@ def pure_unrolled_train_flop_per_sample(K=4, nx=64, H=128, L=4, F=4):
 def train_pure_gnn_unrolled(trajectories, x, K=4, epochs=10, lr=1e-3, batch_size=32, hidden_dim=None, num_layers=None,
                             seed=None, init=None, channel_weights=(1.0, 1.0, 1.0), through_state=True, device="cuda",
                             save_dir="checkpoints", log=print, weight_decay=0.0, max_grad_norm=None,
-                            skip_nonfinite=False, scheduler=None, conservation=None, conservation_ref="target"):
+                            skip_nonfinite=False, scheduler=None, conservation=None, conservation_ref="target",
+                            noise=None, noise_seed=0):
     """Train (or fine-tune) PureGNN on K-step windows of classical trajectories
     [N,T+1,3,nx] (datagen.generate_trajectories) with the unrolled loss:
     train_unrolled's loop -- Adam(lr) over shuffled batches of batch_size windows
@@ -1315,7 +1387,9 @@ def train_pure_gnn_unrolled(trajectories, x, K=4, epochs=10, lr=1e-3, batch_size
     windows), seconds, and writes checkpoints/pure_gnn_unrolled_K<K>.pt (a state
     dict the reference's PureGNN loads) and history_pure_gnn_unrolled_K<K>.json
     (save_dir=None skips).  weight_decay, max_grad_norm, skip_nonfinite,
-    scheduler, conservation, conservation_ref: as train_unrolled's."""
+    scheduler, conservation, conservation_ref, noise, noise_seed: as
+    train_unrolled's, except that the StateNoise is used as given (its own
+    sigma_E, or its own grid to recompute E)."""
     cons = _conservation(conservation, conservation_ref, trainer=True)
     engine.require_device(torch.empty(0, device=device), "device")
     if seed is not None:
@@ -1325,7 +1399,7 @@ def train_pure_gnn_unrolled(trajectories, x, K=4, epochs=10, lr=1e-3, batch_size
                     MODEL_CONFIG["num_layers"] if num_layers is None else num_layers)
     return _train_windows(_PURE, model, data, x, None, init, epochs, lr, batch_size, seed, channel_weights,
                           through_state, device, save_dir, log,
-                          (weight_decay, max_grad_norm, skip_nonfinite, scheduler), cons)
+                          (weight_decay, max_grad_norm, skip_nonfinite, scheduler), cons, noise, noise_seed)
 
 
 # --------------------------------------------------------------------- PINN
@@ -1679,7 +1753,7 @@ def train_pinn_unrolled(trajectories, dx, dt, nu, K=4, epochs=10, lr=1e-3, batch
                         physics_weights=None, seed=None, init=None, channel_weights=(1.0, 1.0, 1.0),
                         through_state=True, device="cuda", save_dir="checkpoints", log=print, weight_decay=0.0,
                         max_grad_norm=None, skip_nonfinite=False, scheduler=None, conservation=None,
-                        conservation_ref="target"):
+                        conservation_ref="target", noise=None, noise_seed=0):
     """Train (or fine-tune) PINN(3 nx, hidden_dim, num_layers) on K-step windows
     of classical trajectories [N,T+1,3,nx] with pinn_unrolled_loss:
     train_unrolled's loop -- Adam(lr) over shuffled batches of batch_size windows
@@ -1690,8 +1764,9 @@ def train_pinn_unrolled(trajectories, dx, dt, nu, K=4, epochs=10, lr=1e-3, batch
     Returns (model, history) with history keys epoch, loss, seconds, and writes
     checkpoints/pinn_unrolled_K<K>.pt (the reference PINN's keys) and
     history_pinn_unrolled_K<K>.json (save_dir=None skips).  weight_decay,
-    max_grad_norm, skip_nonfinite, scheduler, conservation, conservation_ref: as
-    train_unrolled's."""
+    max_grad_norm, skip_nonfinite, scheduler, conservation, conservation_ref,
+    noise, noise_seed: as train_unrolled's, except that the StateNoise is used as
+    given (its own sigma_E, or its own grid to recompute E)."""
     cons = _conservation(conservation, conservation_ref, trainer=True)
     engine.require_device(torch.empty(0, device=device), "device")
     if seed is not None:
@@ -1702,4 +1777,4 @@ def train_pinn_unrolled(trajectories, dx, dt, nu, K=4, epochs=10, lr=1e-3, batch
     model = PINN(3 * data.nx, hidden_dim, num_layers)
     return _train_windows(_PINN, model, data, None, phys, init, epochs, lr, batch_size, seed, channel_weights,
                           through_state, device, save_dir, log,
-                          (weight_decay, max_grad_norm, skip_nonfinite, scheduler), cons)
+                          (weight_decay, max_grad_norm, skip_nonfinite, scheduler), cons, noise, noise_seed)

@@ -896,6 +896,78 @@ int hf_initial_conditions(const int64_t *dev_seeds, int B, int nx, const double 
 int hf_ic_draws_host(int64_t seed, int nx, double *host_table, double *host_gauss);
 
 /*
+ * Training noise on the device: a seeded Gaussian perturbation of a batch of
+ * states, for training on perturbed start states against clean targets.
+ *
+ * Draws.  For sample b, g = np.random.RandomState(seed_b).standard_normal(3 nx):
+ * the legacy polar method from word 0 of a freshly seeded MT19937 stream (four
+ * words per attempt, an accepted attempt yields f x2 then f x1), the draw code
+ * of hf_initial_conditions without the mode draws, one wave per sample.  The
+ * blocks are g_n = g[0:nx], g_u = g[nx:2nx], g_E = g[2nx:3nx].  All 3 nx values
+ * are always drawn, whatever sigma and flags say: the stream does not depend on
+ * the options.
+ *
+ * Arithmetic, per channel ch with s = sigma[ch] (3 HOST floats: n, u, E):
+ *   out[ch][i] = in[ch][i] + (float)s * (float)d[i]
+ * one float32 product, then one float32 add, no FMA.  d = g_ch in float64.
+ * With HF_NOISE_ZERO_MEAN, and for ch = n only, d[i] = g_n[i] - m with
+ * m = (float64 sum of g_n) / nx, so the perturbation leaves the charge sum n
+ * alone up to float32 rounding.  The sum is taken in one fixed order: lane l of
+ * the wave adds its cells l, l + 64, l + 128, ... in ascending order from 0.0,
+ * then the 64 lane sums are combined in a fixed tree (v[l] += v[l ^ o] for o =
+ * 32, 16, 8, 4, 2, 1): two calls give the same bits.  sigma[ch] == 0: the row
+ * is copied bit for bit (no add happens: -0.0 and NaN payloads survive).
+ *
+ * Poisson.  With dev_plan not NULL sigma[2] must be 0, and row E of the output
+ * is hf_poisson_ex(poisson_mode) of the perturbed n row, bit for bit (the
+ * existing launcher on the row with stride 3 nx): the perturbed state is a
+ * consistent solver state.  Without a plan E follows the rule above.  (At the
+ * FFT sizes, power-of-two nx in [256, 2048], that launcher transforms samples
+ * 2k and 2k+1 as one complex row, so a sample's float64 path depends on its
+ * pair partner.  E' has been bit-equal alone and in any batch wherever tested,
+ * because the rounding to float32 absorbs the difference; that is observed, not
+ * true by construction, and is hf_poisson_ex's property, not this call's.)
+ *
+ * dev_state_in, dev_state_out: [B][3][nx]; dev_state_out may be dev_state_in
+ * (any other overlap is not allowed).  dev_node_features (or NULL; needs dev_x
+ * [nx] float32): [B nx][4] = [n', u', E', x], exact copies, written after E' is
+ * final.  dev_noise (or NULL): [B][3][nx], the float32 values (float)s *
+ * (float)d[i] that were added; 0 on a copied row and on a recomputed E row.
+ *
+ * A seed outside [0, 2^32), or draws that give up (after 2 (3 nx) + 256
+ * attempts, as in hf_initial_conditions), make rows n, u, E of that sample NaN
+ * (dev_noise and its node features too) and leave the other samples intact.
+ * With a plan the failed sample enters the Poisson solve with n = 1 (a NaN row
+ * would reach its pair partner at the FFT sizes); the draws mark it by filling
+ * its u row with the quiet NaN 0x7fd0bad5, and the last launch turns every
+ * sample whose u row holds that word in every cell NaN.  (An input whose u row
+ * is that word throughout, under a plan, is therefore treated as failed.)
+ *
+ * At most three launches on `stream` (the draws; the Poisson solve; the failed
+ * samples' NaN and the node features), no allocation, no host synchronisation:
+ * capturable.
+ *
+ * HF_EINVAL before any device call: a NULL dev_seeds, sigma, dev_state_in or
+ * dev_state_out (with B > 0); B < 0 or nx < 1; a negative or NaN sigma; unknown
+ * flags; sigma[2] != 0 or an unknown Poisson mode with a plan;
+ * dev_node_features without dev_x.  HF_EUNSUPPORTED: nx > 2^24; nx > 6144 with
+ * HF_NOISE_ZERO_MEAN (g_n is held in LDS for the second pass); a Poisson mode
+ * that does not take this nx.  B = 0 is HF_OK without a launch.
+ *
+ * hf_gauss_host: host only (no device work), the same draw code:
+ * host_gauss[0..count) = RandomState(seed).standard_normal(count).  -1
+ * (HF_EINVAL) for a seed outside [0, 2^32), count < 0 or a NULL host_gauss with
+ * count > 0.
+ */
+#define HF_NOISE_ZERO_MEAN 1   /* remove the mean of the n noise: charge is kept */
+int hf_state_noise(const int64_t *dev_seeds, int B, int nx, const float *sigma /* 3 HOST floats: n, u, E */,
+                   int flags, const float *dev_state_in, float *dev_state_out /* may be dev_state_in */,
+                   const double *dev_plan /* or NULL */, int poisson_mode,
+                   const float *dev_x /* or NULL */, float *dev_node_features /* or NULL */,
+                   float *dev_noise /* or NULL */, void *stream);
+int hf_gauss_host(int64_t seed, int64_t count, double *host_gauss);   /* host only, no device work */
+
+/*
  * Scratch of the generic (non-fused) sequencing.  hf_step, hf_run and
  * hf_run_compare take (dev_workspace, workspace_bytes): a device buffer of at
  * least hf_workspace_need(model, op, B, nx, T, flags) bytes (or the upper
